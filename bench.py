@@ -22,6 +22,10 @@ Rank 0 prints ONE JSON line with the contract fields plus
     command (profiles/, file named in the line);
   * `cpu_baseline` (N=1 only): the CPU oracle (our port of the reference path, oracle/) timed on this box's host cores as
     BASELINE.md section 4 prescribes (physical cores stated; the benched model and the C1 model; 3 warm-up + 10 timed, median).
+
+`--dump-outputs DIR`: rank 0 writes what the last timed step computed to DIR/*.npy (float32: loss, loss items and seeded samples of
+the gradients, updated parameters and BatchNorm statistics, under 20 MB).  Inputs and initial weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -54,7 +58,12 @@ def parse_args():
                          "source images uploaded every step (PCIe-inclusive), rendered on the device")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -171,19 +180,22 @@ def cpu_baseline(model_name, nc, S):
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     phys, logical = physical_cores()
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    cap = int(omp) if omp.isdigit() and int(omp) > 0 else logical       # a job's CPU share, when it names one, caps the pool
+    threads, eight = min(phys, cap), min(8, logical, cap)
     _, scale = split_model_name(model_name)
     big = scale in "mlx"
-    legs = [cpu_leg(model_name, nc, S, 1 if big else 4, phys, budget_s=45.0)]
+    legs = [cpu_leg(model_name, nc, S, 1 if big else 4, threads, budget_s=45.0)]
     if os.path.basename(model_name) != "yolov8nori.yaml":
-        legs.append(cpu_leg("yolov8nori.yaml", nc, 640, 4, phys, budget_s=20.0))
-    if phys != 8:
-        legs.append(cpu_leg("yolov8nori.yaml", nc, 640, 4, min(8, logical), budget_s=20.0))
+        legs.append(cpu_leg("yolov8nori.yaml", nc, 640, 4, threads, budget_s=20.0))
+    if eight != threads:
+        legs.append(cpu_leg("yolov8nori.yaml", nc, 640, 4, eight, budget_s=20.0))
     main = legs[0]
-    return dict(value=main["img_per_s"], unit="img/s", cores=phys, kind="port", logical_cpus=logical, legs=legs,
+    return dict(value=main["img_per_s"], unit="img/s", cores=phys, threads=threads, kind="port", logical_cpus=logical, legs=legs,
                 sample=f"oracle (CPU port of the reference path, fp32, torch {torch.__version__}): fwd+loss+bwd+SGD of {model_name} at "
                        f"{S}x{S}, batch {main['batch']}, {main['timed']} timed steps after {main['warmup']} warm-up (median), "
-                       f"{phys} threads = physical cores of this box's CPU share ({logical} logical); legs: benched model, C1 "
-                       "(yolov8nori.yaml@n B=4) at all cores and at 8 threads")
+                       f"{threads} threads = physical cores of this box's CPU share ({phys} physical, {logical} logical), capped by "
+                       "OMP_NUM_THREADS when set; legs: benched model, C1 (yolov8nori.yaml@n B=4) at that thread count and at 8 threads")
 
 
 def kernel_profile(trainer, batches, steps=3):
@@ -217,6 +229,32 @@ def kernel_profile(trainer, batches, steps=3):
             a["meta_n"] += 1
             a["dtype"] = meta["dtype"].replace("torch.", "")
     return agg, steps
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of each flat state vector (4 MiB in f32)
+
+
+def dump_outputs(out_dir, trainer, loss, items):
+    """What the last timed step computed, as float32 .npy files in `out_dir`: what train_step returned (the loss and its items) and
+    what the step left in the flat state -- the gradients of its backward, the parameters after its optimizer update, the BatchNorm
+    running statistics of its forward.  The state vectors are sampled at the same seeded indices (numpy default_rng(0), sorted)
+    whenever the model is the same, so that two builds can be compared file by file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    f = trainer.flat
+
+    def sample(v):
+        n = v.numel()
+        if n <= DUMP_SAMPLE:
+            return v
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        return v[torch.from_numpy(idx).to(v.device)]
+
+    arrays = dict(loss=loss, loss_items=items, grads_sample=sample(f.g), params_sample=sample(f.p),
+                  bn_buffers_sample=sample(f.buf_flat))
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), torch.as_tensor(t).detach().float().cpu().numpy())
 
 
 def workload_tag(args):
@@ -327,6 +365,7 @@ def main():
         return b, gammas[state["k"] % len(gammas)]
 
     def run(n):
+        loss = items = None
         for i in range(n):
             if loader is None:
                 b = dict(batches[i % len(batches)])
@@ -334,7 +373,7 @@ def main():
             else:
                 b, trainer.args.dark_param = next_loader_batch()
             loss, items = trainer.train_step(b)
-        return loss
+        return loss, items
 
     run(args.warmup)
     torch.cuda.synchronize()
@@ -343,7 +382,7 @@ def main():
         trainer.buckets.exposed_events = []       # events around the compute stream's waits for the bucketed all-reduce
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    loss = run(args.steps)
+    loss, items = run(args.steps)
     torch.cuda.synchronize()
     el_own = time.perf_counter() - t0             # this rank, before it waits for the others
     if world > 1:
@@ -354,6 +393,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t)
+    if args.dump_outputs and rank == 0:           # before the roofline's extra steps move the state on
+        dump_outputs(args.dump_outputs, trainer, loss, items)
     per_rank = None
     if world > 1:
         ev, trainer.buckets.exposed_events = trainer.buckets.exposed_events, None

@@ -118,6 +118,28 @@ def test_bench_shards_are_rank_distinct():
     assert bench.split_model_name("yolov8l.yaml") == ("yolov8.yaml", "l")
 
 
+def test_bench_dump_outputs_is_fixed_and_small(tmp_path):
+    """bench.py --dump-outputs: f32 .npy files, the flat state vectors sampled at the same indices in every run (two builds are
+    compared file by file), small vectors kept whole, well under 64 MB for a model of the C3 size (~45 M flat elements)."""
+    from types import SimpleNamespace
+    import bench
+    n = 3 * bench.DUMP_SAMPLE + 5
+    flat = SimpleNamespace(g=torch.arange(n, dtype=torch.float32), p=-torch.arange(n, dtype=torch.float32), buf_flat=torch.ones(10))
+    tr = SimpleNamespace(flat=flat)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), tr, torch.tensor(2.5), torch.tensor([1.0, 2.0, 3.0]))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_buffers_sample.npy", "grads_sample.npy", "loss.npy", "loss_items.npy", "params_sample.npy"]
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    g = np.load(tmp_path / "a" / "grads_sample.npy")
+    assert g.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(g) > 0) and g.max() < n       # distinct sorted indices
+    assert np.array_equal(np.load(tmp_path / "a" / "params_sample.npy"), -g)               # same indices for every vector
+    assert np.load(tmp_path / "a" / "bn_buffers_sample.npy").shape == (10,) and float(np.load(tmp_path / "a" / "loss.npy")) == 2.5
+    assert 5 * 4 * bench.DUMP_SAMPLE < 64 << 20
+
+
 def _epoch_worker(rank, world, port, q):
     """The epoch loop of DetectionTrainer.train with the device work stubbed out (no GPU here): what is under test is the
     reference's epoch-boundary protocol (engine/trainer.py:366-395) -- rank 0 validates / stops, the flag reaches every rank."""
