@@ -69,6 +69,10 @@ _SIGS = {
     "dy_upsample_nearest_bwd": [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_copy2d": [vp, i64, vp, i64, i64, i32, i32, i32, vp],
     "dy_cast": [vp, i32, vp, i32, i64, vp],
+    "dy_pconv_pack": [vp, vp, i32, i32, i32, vp],
+    "dy_pconv_fwd": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "dy_pconv_dgrad": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
+    "dy_pconv_wgrad": [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, i64, i32, vp],
     "dy_asff_fuse_fwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, i32, vp],
     "dy_asff_fuse_bwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32,
                          i32, i32, vp],

@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "Concat", "Bottleneck", "C2f", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
+__all__ = ("Conv", "Concat", "Bottleneck", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
            "AsffDetect",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
@@ -287,6 +287,98 @@ class C2f(DyModule):
         for i in reversed(range(n)):
             self.m[i]._bwd(tape, dY[:, (2 + i) * c:(3 + i) * c], dx_out=dY[:, (1 + i) * c:(2 + i) * c], accumulate=True)
         return self.cv1._bwd(tape, dY[:, :2 * c], needs=needs)
+
+
+class PConv(DyModule):
+    """FasterNet partial convolution, split_cat mode (reference conv.py:157-190): 3x3 conv on the first dim // n_div channels, the
+    rest passed through -- one HIP kernel per direction (ops.pconv_forward / pconv_backward).  The inference-only 'slicing' mode
+    is not provided."""
+
+    def __init__(self, dim, n_div, forward="split_cat"):
+        super().__init__()
+        if forward != "split_cat":
+            raise NotImplementedError("PConv: only the split_cat forward is implemented")
+        self.dim_conv3 = dim // n_div
+        self.dim_untouched = dim - self.dim_conv3
+        self.patial_conv3 = nn.Conv2d(self.dim_conv3, self.dim_conv3, 3, 1, 1, bias=False)
+
+    def _fwd(self, tape, x, out=None):
+        return ops.pconv_forward(tape, x, self.patial_conv3.weight, out=out)
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False, add_src=None):
+        return ops.pconv_backward(tape, dy, dx_out=dx_out, accumulate=accumulate, add_src=add_src)
+
+
+class _PconvBottleneckBase(DyModule):
+    """fasterblock (PConv -> Conv [-> bias-free 1x1]) -> bias-free 1x1 [+ x].  The last 1x1 conv writes straight into `out`; the
+    shortcut is then added in place (one pass; conv_forward's residual route without BatchNorm would stage the conv output in a
+    temporary).  Backward routes the shortcut and C2f's gradient-buffer accumulate through PConv's data gradient."""
+
+    def _last(self):
+        raise NotImplementedError
+
+    def _fwd(self, tape, x, out=None):
+        fb = self.fasterblock
+        t = fb[1]._fwd(tape, fb[0]._fwd(tape, x))
+        y = conv_forward(tape, t, self._last().weight, None, None, ACT_NONE, 1, 0, 1, False, out=out)
+        if self.add:
+            copy2d(x, y, accumulate=True)
+            ops.emu_round(y)
+        return y
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        fb = self.fasterblock
+        du = conv_backward(tape, dy)
+        dt = fb[1]._bwd(tape, du)
+        return fb[0]._bwd(tape, dt, dx_out=dx_out, accumulate=accumulate, add_src=dy if self.add else None)
+
+
+class PconvBottleneck(_PconvBottleneckBase):
+    """PConv -> Conv 3x3 -> 1x1 [+ x] (reference block.py:568-587)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        if g != 1:
+            raise NotImplementedError("grouped convolution is outside the Dedark-YOLO hot path")
+        c_ = int(c2 * e)
+        self.fasterblock = nn.Sequential(PConv(dim=c1, n_div=4), Conv(c1=c1, c2=c_, k=3, s=1, p=1))
+        self.conv = nn.Conv2d(c_, c2, 1, 1, autopad(1, None, 1), groups=g, bias=False)
+        self.add = shortcut and c1 == c2
+
+    def _last(self):
+        return self.conv
+
+
+class PconvBottleneck_n(_PconvBottleneckBase):
+    """PConv -> Conv 1x1 (2c_) -> 1x1 [+ x], all inside `fasterblock` (reference block.py:590-607)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        if g != 1:
+            raise NotImplementedError("grouped convolution is outside the Dedark-YOLO hot path")
+        c_ = int(c2 * e)
+        self.fasterblock = nn.Sequential(PConv(dim=c1, n_div=4), Conv(c1=c1, c2=2 * c_, k=1, s=1),
+                                         nn.Conv2d(2 * c_, c2, 1, 1, autopad(1, None, 1), groups=g, bias=False))
+        self.add = shortcut and c1 == c2
+
+    def _last(self):
+        return self.fasterblock[2]
+
+
+class FasterC2f_N(C2f):
+    """C2f with PconvBottleneck_n blocks (reference block.py:396-405); same single-buffer dataflow as C2f."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(PconvBottleneck_n(self.c, self.c, shortcut, g=g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
+
+
+class FasterC2f(C2f):
+    """C2f with PconvBottleneck blocks (reference block.py:408-415)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(PconvBottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
 
 
 class SPPF(DyModule):

@@ -15,8 +15,8 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2f, Concat, Conv, Detect, DyModule, MFRU, RFBblock, SPPF, Tape,
-                      Upsample, lowlight_recovery)
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
+                      PconvBottleneck, PconvBottleneck_n, RFBblock, SPPF, Tape, Upsample, lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
 # reverse, adding the gradients of a multi-consumer output itself -- no autograd.Function per yaml node, no ATen `add` for the fan-outs.
@@ -26,7 +26,8 @@ _GRAPH_BACKWARD = os.environ.get("DY_GRAPH_BACKWARD", "1") != "0"
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 
 _REGISTRY = dict(Conv=Conv, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
-                 AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery)
+                 AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
+                 FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -83,6 +84,8 @@ def _rule_c2f(row):                       # the row's repeat count becomes the n
 
 _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
+    FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                                              # tasks.py:743-753
+    PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
     AsffTribeLevel: lambda r: (r.args, 512 if r.args[0] in (0, 1) else 256, r.repeats),       # tasks.py:892-896
@@ -94,7 +97,7 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2f, SPPF, Upsample)          # top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2f, SPPF, Upsample)          # (C2f covers FasterC2f / FasterC2f_N) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):

@@ -729,6 +729,92 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
     return dxb if cin_pad == Cin else dxb[:, :Cin]
 
 
+# ------------------------------------------------------------------------------------------------ PConv
+def _nhwc_like(B, Cc, H, W, dtype, device):
+    """[B, Cc, H, W] NHWC tensor whose vector-padding lanes (if any) are zero, so a conv may read it (padded_channels)."""
+    Cp = round_up(Cc, vec_elems(dtype))
+    if Cp == Cc:
+        return empty_nhwc(B, Cc, H, W, dtype, device)
+    return zeros_nhwc(B, Cp, H, W, dtype, device)[:, :Cc]
+
+
+def _pconv_packed(weight, w32, transposed, dtype):
+    """MFMA operand image of a PConv weight for the 16-bit route (dy_pconv_pack; None where the VALU route runs), cached on the
+    parameter and re-packed when the weights changed (optimizer step, load_state_dict)."""
+    c3 = weight.shape[0]
+    if dtype == torch.float32 or c3 < 16:
+        return None
+    cache = weight.__dict__.setdefault("_dy_pconv_pack", {})
+    key, tag = (bool(transposed), dtype), (_weights_epoch, weight._version, weight.data_ptr())
+    hit = cache.get(key)
+    if hit is not None and hit[0] == tag:
+        return hit[1]
+    out = hit[1] if hit is not None else torch.empty(9 * ((c3 + 31) // 32) * ((c3 + 15) // 16) * 512, dtype=dtype, device=weight.device)
+    call("dy_pconv_pack", ptr(w32), ptr(out), c3, 1 if transposed else 0, dt_id(dtype), stream())
+    cache[key] = (tag, out)
+    return out
+
+
+def pconv_forward(tape, x, weight, out=None):
+    """PConv split_cat (reference conv.py:157-190): y[:, :c3] = conv3x3(x[:, :c3]), y[:, c3:] = x[:, c3:] in one kernel.
+    x / out: NHWC views of C channels (channel slices of wider buffers are fine: exactly the lanes [0, C) are touched)."""
+    B, Cc, H, W = x.shape
+    c3 = weight.shape[0]
+    if tuple(weight.shape) != (c3, c3, 3, 3) or c3 > Cc:
+        raise RuntimeError(f"pconv: weight {tuple(weight.shape)} does not fit {Cc} channels")
+    y = out if out is not None else _nhwc_like(B, Cc, H, W, x.dtype, x.device)
+    w32 = weight.detach()
+    if w32.dtype != torch.float32 or not w32.is_contiguous():
+        w32 = w32.float().contiguous()
+    es = x.element_size()
+    _C._prof is not None and _C.set_meta(kind="pconv_fwd", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(x.dtype),
+                                         flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(2 * B * H * W * Cc * es + 9 * c3 * c3 * 4))
+    wp = _pconv_packed(weight, w32, False, x.dtype)
+    call("dy_pconv_fwd", ptr(x), ld_of(x), ptr(y), ld_of(y), ptr(w32), ptr(wp), B, H, W, Cc, c3, dt_id(x.dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        tape.push((x, weight))
+    return y
+
+
+def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
+    """Backward of the matching pconv_forward (pops its context): weight gradient (deterministic, f32) and
+    dx = [dx_out +] split/cat adjoint of dy [+ add_src], one launch each.  Returns dx."""
+    x, weight = tape.pop()
+    B, Cc, H, W = x.shape
+    c3 = weight.shape[0]
+    dtype, dev, st = x.dtype, x.device, stream()
+    es = x.element_size()
+    if tuple(dy.shape) != (B, Cc, H, W) or dy.dtype != dtype:
+        raise RuntimeError("pconv_backward: gradient does not match the forward's output")
+    if weight.requires_grad:
+        gd = _grad_dst(weight)
+        gw = gd if gd is not None else torch.empty(weight.shape, dtype=torch.float32, device=dev)
+        scratch = wgrad_scratch(dev, tag=st)
+        _C._prof is not None and _C.set_meta(kind="pconv_wgrad", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(dtype),
+                                             flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(2 * B * H * W * c3 * es + 9 * c3 * c3 * 4))
+        call("dy_pconv_wgrad", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(gw), B, H, W, c3, ptr(scratch), scratch.numel(), dt_id(dtype), st)
+        if gd is None:
+            _add_pgrad(tape, weight, gw)
+    if dx_out is None:
+        dx, accumulate = _nhwc_like(B, Cc, H, W, dtype, dev), False
+    else:
+        dx = dx_out
+    if add_src is not None and (tuple(add_src.shape) != (B, Cc, H, W) or add_src.dtype != dtype):
+        raise RuntimeError("pconv_backward: add_src must be an NHWC view of dx's shape and dtype")
+    w32 = weight.detach()
+    if w32.dtype != torch.float32 or not w32.is_contiguous():
+        w32 = w32.float().contiguous()
+    n_rw = 2 + (1 if accumulate else 0) + (1 if add_src is not None else 0)
+    _C._prof is not None and _C.set_meta(kind="pconv_dgrad", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(dtype),
+                                         flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(n_rw * B * H * W * Cc * es + 9 * c3 * c3 * 4))
+    wp = _pconv_packed(weight, w32, True, dtype)
+    call("dy_pconv_dgrad", ptr(dy), ld_of(dy), ptr(dx), ld_of(dx), ptr(w32), ptr(wp), B, H, W, Cc, c3, 1 if accumulate else 0,
+         ptr(add_src), 0 if add_src is None else ld_of(add_src), dt_id(dtype), st)
+    emu_round(dx)
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ small ops
 def copy2d(src, dst, accumulate=False):
     B, Cc, H, W = src.shape

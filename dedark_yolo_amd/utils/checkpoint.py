@@ -205,9 +205,10 @@ def intersect_dicts(da, db, exclude=()):
 # CPU against tests/golden/g12_ref_skeleton.json (what the reference itself pickles) and, in the build container, by loading the
 # file with the reference (tests/golden/make_ckpt_interop.py).
 _REF_HOME = {"DetectionModel": "ultralytics.nn.tasks"}
-_REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d")})
+_REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
-                                                               "RFBblock")})
+                                                               "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
+                                                               "PconvBottleneck")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
@@ -232,7 +233,9 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2f": ("c",), "Bottleneck": ("add",
               "AsffTribeLevel": ("level", "dim", "inter_dim"), "AsffDoubLevel": ("level", "dim", "inter_dim"), "MFRU": (), "RFBblock": (),
               "SCConv": (), "SRU": ("gate_treshold",), "CRU": ("up_channel", "low_channel"), "GroupBatchnorm2d": ("group_num", "eps"),
               "Detect": ("nc", "nl", "reg_max", "no", "stride"), "AsffDetect": ("nc", "nl", "reg_max", "no", "stride"),
-              "lowlight_recovery": (), "ExtractParameters2": ("output_dim", "channels"), "ConvBlock": ()}
+              "lowlight_recovery": (), "ExtractParameters2": ("output_dim", "channels"), "ConvBlock": (),
+              "PConv": ("dim_conv3", "dim_untouched"), "FasterC2f_N": ("c",), "FasterC2f": ("c",), "PconvBottleneck_n": ("add",),
+              "PconvBottleneck": ("add",)}
 
 _STANDINS = {}
 
@@ -246,6 +249,16 @@ def _standin_type(module, name, base=_StandIn):
     if t is None:
         t = _STANDINS[(module, name)] = type(name, (base,), {"__module__": module, "__qualname__": name, "_dy_standin": True})
     return t
+
+
+class _RefMethod:
+    """A bound method of a stand-in object, pickled the way pickle stores any bound method: getattr(obj, name)."""
+
+    def __init__(self, obj, name):
+        self.obj, self.name = obj, name
+
+    def __reduce__(self):
+        return getattr, (self.obj, self.name)
 
 
 class _RefPickler(pickle._Pickler):
@@ -389,6 +402,8 @@ class _RefWriter:
             kids["sigomid"] = self.torch_leaf(nn.Sigmoid(), "")
         elif name == "CRU":
             kids["advavg"] = self.torch_leaf(nn.AdaptiveAvgPool2d(1), "")
+        elif name == "PConv":                             # the constructor binds the split_cat forward per instance (conv.py:169-172)
+            state["forward"] = _RefMethod(obj, "forward_split_cat")
         elif name in ("Detect", "AsffDetect"):
             state["inplace"] = True
             state["anchors"] = torch.empty(0, dtype=torch.float16)       # BaseModel._apply moves stride / anchors / strides

@@ -148,6 +148,29 @@ int dy_upsample_nearest_bwd(const void* dy, int64_t dy_ld, void* dx, int64_t dx_
 int dy_copy2d(const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int64_t pixels, int C, int accumulate, int dtype,
               void* stream);
 int dy_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------ PConv (FasterNet partial convolution)
+ * Replaces PConv.forward_split_cat (U/nn/modules/conv.py:157-190, n_div=4): torch.split -> bias-free 3x3 s1 p1 nn.Conv2d on the
+ * first c3 = C/4 channels -> torch.cat with the untouched C - c3 channels, and its autograd backward.  Views are NHWC over
+ * N*H*W pixels with their own pixel strides; C and c3 (1..128) need no vector padding: only lanes [0, C) of a row are read or
+ * written (the conv part reads [0, c3)), so the views may be channel slices of C2f / Concat buffers with live neighbours.
+ * w / dw: f32 OIHW [c3][c3][3][3] (the state_dict layout; no packing). */
+/* MFMA operand layout of w for the 16-bit route (dtype bf16 / f16, 16 <= c3 <= 128): wp holds
+ * 9 * ceil(c3/32) * ceil(c3/16) * 512 elements of dtype; transposed = 1 packs the data gradient's (ci <-> co, flipped) weights */
+int dy_pconv_pack(const float* w, void* wp, int c3, int transposed, int dtype, void* stream);
+/* y[.., :c3] = conv3x3(x[.., :c3], w), y[.., c3:] = x[.., c3:]  (U/nn/modules/conv.py:185-190).  wp: dy_pconv_pack(transposed=0)
+ * of w, required for 16-bit c3 >= 16 (ignored otherwise) */
+int dy_pconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* w, const void* wp, int N, int H, int W, int C, int c3,
+                 int dtype, void* stream);
+/* dx[.., :c3] = [dx +] conv3x3^T(dy[.., :c3], w) [+ add_src], dx[.., c3:] = [dx +] dy[.., c3:] [+ add_src]: the split/cat
+ * adjoint; accumulate adds into C2f's gradient buffer, add_src (optional view of dx's shape) is PconvBottleneck's shortcut
+ * gradient (U/nn/modules/block.py:587,606).  wp: dy_pconv_pack(transposed=1) of w, required for 16-bit c3 >= 16 */
+int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, const float* w, const void* wp, int N, int H, int W, int C,
+                   int c3, int accumulate, const void* add_src, int64_t add_ld, int dtype, void* stream);
+/* dw = sum over pixels of dy[.., :c3] x x[.., :c3] at each tap (overwrite), f32.  Deterministic: per-chunk partials in `scratch`
+ * (>= 9*c3*c3 floats; more allows more chunks), summed in chunk order by a second launch; no atomics */
+int dy_pconv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw, int N, int H, int W, int c3, float* scratch,
+                   int64_t scratch_elems, int dtype, void* stream);
 /* ASFF blend (block.py:103-111): w = softmax(logits[.,3]); out = sum_i w_i * x_i */
 int dy_asff_fuse_fwd(const void* x0, int64_t ld0, const void* x1, int64_t ld1, const void* x2, int64_t ld2,
                      const void* logits, int64_t ldl, void* out, int64_t ldo, int64_t pixels, int C, int dtype, void* stream);
