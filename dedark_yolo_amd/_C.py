@@ -36,6 +36,12 @@ class DetMaps(C.Structure):
                 ("nc", i32), ("n_levels", i32), ("dtype", i32)]
 
 
+class DetMaps4(DetMaps):
+    """dy_det_maps4 (include/dedark_yolo.h): a dy_det_maps followed by the fourth level (ctypes appends a subclass's fields
+    after its base's, the C layout of `base` + tail); accepted wherever a DetMaps pointer is."""
+    _fields_ = [("map3", vp), ("map_ld3", i64), ("h3", i32), ("w3", i32), ("stride3", f32)]
+
+
 class AugSample(C.Structure):
     """dy_aug_sample (include/dedark_yolo.h)"""
     _fields_ = [("src", vp * 4), ("sh", i32 * 4), ("sw", i32 * 4), ("pitch", i64 * 4), ("rect", (i32 * 6) * 4), ("n_src", i32),
@@ -102,7 +108,7 @@ _SIGS = {
     "dy_dfl_loss": [vp, vp, i64, vp, vp, vp],
     "dy_loss_fwd": [C.POINTER(DetMaps), vp, vp, vp, vp, vp, vp, vp],
     "dy_loss_finish": [vp, vp, f32, f32, f32, f32, i32, vp, vp, vp],
-    "dy_loss_bwd": [C.POINTER(DetMaps), vp * 3, i64 * 3, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp],
+    "dy_loss_bwd": [C.POINTER(DetMaps), C.POINTER(vp), C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp],
     "dy_detect_decode": [C.POINTER(DetMaps), vp, vp],
     "dy_nms_candidates": [vp, i32, i32, i32, f32, i32, vp, vp, i64, vp],
     "dy_nms_sort": [vp, vp, vp, i32, i64, vp, vp, vp],

@@ -16,11 +16,13 @@ namespace {
 constexpr int REG = 16;
 constexpr int TOPK = 10;
 
+// up to DY_DET_MAX_LEVELS pyramid levels (P2..P5 / P3..P6 heads have four); off[l] = first anchor of level l, and every
+// slot from nl on holds A, so the level of an anchor is the number of level starts <= a past the first
 struct Maps {
-  const char* map[3];
-  long ld[3];
-  int h[3], w[3], off[4];
-  float stride[3];
+  const char* map[DY_DET_MAX_LEVELS];
+  long ld[DY_DET_MAX_LEVELS];
+  int h[DY_DET_MAX_LEVELS], w[DY_DET_MAX_LEVELS], off[DY_DET_MAX_LEVELS + 1];
+  float stride[DY_DET_MAX_LEVELS];
   int B, nc, nl, A;
   // decoded-input mode of the assigner (dy_tal_assign_decoded = TaskAlignedAssigner.forward's own arguments): class probabilities
   // [B, A, nc] f32 and anchor points [A, 2] in pixels; the predicted boxes are then in pixels too.  Both null otherwise.
@@ -29,8 +31,7 @@ struct Maps {
 };
 
 __device__ inline void anchor_of(const Maps& m, int a, int& lvl, int& cell, float& ax, float& ay) {
-  lvl = (a >= m.off[1]) + (a >= m.off[2] && m.nl > 2);
-  if (m.nl == 1) lvl = 0;
+  lvl = (a >= m.off[1]) + (a >= m.off[2]) + (a >= m.off[3]);
   cell = a - m.off[lvl];
   int yy = cell / m.w[lvl], xx = cell - yy * m.w[lvl];
   ax = xx + 0.5f;
@@ -495,7 +496,7 @@ __global__ void loss_finish_kernel(const double* acc, const float* recovery, flo
 
 // ---- loss backward: d loss / d maps ----------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(256) void loss_bwd_kernel(Maps m, char* d0, char* d1, char* d2, long dl0, long dl1, long dl2,
+__global__ __launch_bounds__(256) void loss_bwd_kernel(Maps m, char* d0, char* d1, char* d2, char* d3, long dl0, long dl1, long dl2, long dl3,
                                                         const float* __restrict__ pred, const uint8_t* __restrict__ fg,
                                                         const float* __restrict__ norm, const int* __restrict__ label,
                                                         const float* __restrict__ tbox, const double* __restrict__ acc,
@@ -508,8 +509,8 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Maps m, char* d0, char* d
   float ax, ay;
   anchor_of(m, a, lvl, cell, ax, ay);
   const T* r = row_ptr<T>(m, b, lvl, cell);
-  char* dbase = lvl == 0 ? d0 : (lvl == 1 ? d1 : d2);
-  long dld = lvl == 0 ? dl0 : (lvl == 1 ? dl1 : dl2);
+  char* dbase = lvl == 0 ? d0 : (lvl == 1 ? d1 : (lvl == 2 ? d2 : d3));
+  long dld = lvl == 0 ? dl0 : (lvl == 1 ? dl1 : (lvl == 2 ? dl2 : dl3));
   T* o = reinterpret_cast<T*>(dbase) + ((long)b * m.h[lvl] * m.w[lvl] + cell) * dld;
   const float tss = fmaxf((float)acc[0], 1.f);
   const float go = (grad_out ? grad_out[0] : 1.f) * (float)m.B / tss;
@@ -651,25 +652,28 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
   if (threadIdx.x == 0 && mse_acc) atomic_add_f64(mse_acc, (double)part);
 }
 
+// d points at a dy_det_maps4 when d->n_levels == 4 (its tail is read only then)
 int make_maps(const dy_det_maps* d, Maps& m, const char* who) {
-  DY_CHECK(d && d->n_levels >= 1 && d->n_levels <= 3, "%s: bad maps", who);
+  DY_CHECK(d && d->n_levels >= 1 && d->n_levels <= DY_DET_MAX_LEVELS, "%s: bad maps", who);
   DY_CHECK(d->dtype == DY_F32 || d->dtype == DY_BF16 || d->dtype == DY_F16, "%s: bad dtype", who);
   m.B = d->B; m.nc = d->nc; m.nl = d->n_levels;
   m.dec_scores = nullptr; m.dec_anchors = nullptr;
+  const dy_det_maps4* d4 = d->n_levels == 4 ? reinterpret_cast<const dy_det_maps4*>(d) : nullptr;
   int off = 0;
-  for (int l = 0; l < 3; ++l) {
+  for (int l = 0; l < DY_DET_MAX_LEVELS; ++l) {
     m.off[l] = off;
     if (l < d->n_levels) {
-      DY_CHECK(d->map[l] && d->h[l] > 0 && d->w[l] > 0 && d->map_ld[l] >= 4 * REG + d->nc, "%s: bad level %d", who, l);
-      m.map[l] = (const char*)d->map[l]; m.ld[l] = d->map_ld[l]; m.h[l] = d->h[l]; m.w[l] = d->w[l]; m.stride[l] = d->stride[l];
-      off += d->h[l] * d->w[l];
+      const void* map = l < 3 ? d->map[l] : d4->map3;
+      const long ld = l < 3 ? d->map_ld[l] : d4->map_ld3;
+      const int h = l < 3 ? d->h[l] : d4->h3, w = l < 3 ? d->w[l] : d4->w3;
+      DY_CHECK(map && h > 0 && w > 0 && ld >= 4 * REG + d->nc, "%s: bad level %d", who, l);
+      m.map[l] = (const char*)map; m.ld[l] = ld; m.h[l] = h; m.w[l] = w; m.stride[l] = l < 3 ? d->stride[l] : d4->stride3;
+      off += h * w;
     } else {
       m.map[l] = nullptr; m.ld[l] = 0; m.h[l] = 1; m.w[l] = 1; m.stride[l] = 1.f;
     }
   }
-  m.off[3] = off;
-  if (d->n_levels < 3) m.off[2] = off;
-  if (d->n_levels < 2) m.off[1] = off;
+  for (int l = d->n_levels; l <= DY_DET_MAX_LEVELS; ++l) m.off[l] = off;
   m.A = off;
   DY_CHECK(m.B > 0 && m.nc > 0 && m.A >= TOPK, "%s: empty problem (A=%d)", who, m.A);
   return 0;
@@ -753,8 +757,8 @@ extern "C" int dy_tal_assign_decoded(const float* pd_scores, const float* pd_bbo
            "dy_tal_assign_decoded: null");
   DY_CHECK(B > 0 && nc > 0 && A >= TOPK && n_max >= 0, "dy_tal_assign_decoded: empty problem (A=%d)", A);
   Maps m;
-  for (int l = 0; l < 3; ++l) { m.map[l] = nullptr; m.ld[l] = 0; m.h[l] = 1; m.w[l] = 1; m.stride[l] = 1.f; m.off[l] = l ? A : 0; }
-  m.off[3] = A;
+  for (int l = 0; l < DY_DET_MAX_LEVELS; ++l) { m.map[l] = nullptr; m.ld[l] = 0; m.h[l] = 1; m.w[l] = 1; m.stride[l] = 1.f; m.off[l] = l ? A : 0; }
+  m.off[DY_DET_MAX_LEVELS] = A;
   m.B = B; m.nc = nc; m.nl = 1; m.A = A;
   m.dec_scores = pd_scores; m.dec_anchors = anc_points;
   return run_assigner(m, DY_F32, pd_bboxes, gt, counts, n_max, work_f, work_i, work_b, target_gt_idx, fg_mask, norm, target_label,
@@ -783,14 +787,14 @@ extern "C" int dy_loss_finish(const double* acc, const float* recovery, float hy
   return 0;
 }
 
-extern "C" int dy_loss_bwd(const dy_det_maps* d, void* const dmap[3], const int64_t dmap_ld[3], const float* pred_boxes,
+extern "C" int dy_loss_bwd(const dy_det_maps* d, void* const* dmap, const int64_t* dmap_ld, const float* pred_boxes,
                            const uint8_t* fg_mask, const float* norm, const int32_t* target_label, const float* target_box,
                            const double* acc, const float* grad_out, float hyp_box, float hyp_cls, float hyp_dfl, void* stream) {
   Maps m;
   if (int e = make_maps(d, m, "dy_loss_bwd")) return e;
   DY_CHECK(dmap && dmap_ld && pred_boxes && fg_mask && norm && target_label && target_box && acc, "dy_loss_bwd: null");
-  char* dp[3] = {nullptr, nullptr, nullptr};
-  long dl[3] = {0, 0, 0};
+  char* dp[DY_DET_MAX_LEVELS] = {nullptr, nullptr, nullptr, nullptr};
+  long dl[DY_DET_MAX_LEVELS] = {0, 0, 0, 0};
   int pad_to = 1 << 30;
   for (int l = 0; l < m.nl; ++l) {
     DY_CHECK(dmap[l] && dmap_ld[l] >= 4 * REG + m.nc, "dy_loss_bwd: bad dmap %d", l);
@@ -800,15 +804,15 @@ extern "C" int dy_loss_bwd(const dy_det_maps* d, void* const dmap[3], const int6
   }
   int blocks = dy_cdiv((long)m.B * m.A, 256);
   if (d->dtype == DY_F32)
-    loss_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dl[0], dl[1], dl[2], pred_boxes, fg_mask,
+    loss_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
                                                                     norm, target_label, target_box, acc, grad_out, hyp_box, hyp_cls,
                                                                     hyp_dfl, pad_to);
   else if ((d->dtype) == DY_F16)
-    loss_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dl[0], dl[1], dl[2], pred_boxes, fg_mask,
+    loss_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
                                                                      norm, target_label, target_box, acc, grad_out, hyp_box,
                                                                      hyp_cls, hyp_dfl, pad_to);
   else
-    loss_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dl[0], dl[1], dl[2], pred_boxes, fg_mask,
+    loss_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
                                                                      norm, target_label, target_box, acc, grad_out, hyp_box,
                                                                      hyp_cls, hyp_dfl, pad_to);
   DY_LAUNCH_CHECK();

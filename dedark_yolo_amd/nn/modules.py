@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "Concat", "Bottleneck", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
+__all__ = ("Conv", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
            "AsffDetect",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
@@ -259,6 +259,43 @@ class Bottleneck(DyModule):
         dt = self.cv2._bwd(tape, dy)
         # shortcut: dx = d cv1 + dy, added inside cv1's data gradient (dy_conv_desc.add_src) instead of by a copy pass
         return self.cv1._bwd(tape, dt, dx_out=dx_out, accumulate=accumulate, add_src=dy if self.add else None)
+
+
+class C2(DyModule):
+    """CSP bottleneck with two convolutions (reference block.py:355-370): a, b = chunk(cv1(x)); cv2(cat(m(a), b)), m a chain of
+    n Bottlenecks.  cv1 writes [a | b] into one buffer and the last Bottleneck writes m(a) straight into the first half of
+    cv2's input buffer; the reference order (m(a), b) is not a slice of cv1's output, so b is copied next to m(a) (one
+    c-channel dy_copy2d forward, one for its gradient backward)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        self.c = int(c2 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c2, 1)
+        self.m = nn.Sequential(*(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n)))
+
+    def _fwd(self, tape, x, out=None):
+        c, n = self.c, len(self.m)
+        B, _, H, W = x.shape
+        Y = empty_nhwc(B, 2 * c, H, W, x.dtype, x.device)              # cv1: [a | b]
+        Z = empty_nhwc(B, 2 * c, H, W, x.dtype, x.device)              # cv2's input: [m(a) | b]
+        self.cv1._fwd(tape, x, out=Y)
+        t = Y[:, :c]
+        for i, m in enumerate(self.m):
+            t = m._fwd(tape, t, out=Z[:, :c] if i == n - 1 else None)
+        copy2d(Y[:, c:], Z[:, c:])
+        return self.cv2._fwd(tape, Z, out=out)
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        c, n = self.c, len(self.m)
+        dZ = self.cv2._bwd(tape, dy)                                   # [d m(a) | d b]
+        B, _, H, W = dZ.shape
+        dY = empty_nhwc(B, 2 * c, H, W, dZ.dtype, dZ.device)
+        copy2d(dZ[:, c:], dY[:, c:])
+        g = dZ[:, :c]
+        for i in reversed(range(n)):
+            g = self.m[i]._bwd(tape, g, dx_out=dY[:, :c] if i == 0 else None)
+        return self.cv1._bwd(tape, dY, needs=needs)
 
 
 class C2f(DyModule):

@@ -15,7 +15,7 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
                       PconvBottleneck, PconvBottleneck_n, RFBblock, SPPF, Tape, Upsample, lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
@@ -25,7 +25,7 @@ _GRAPH_BACKWARD = os.environ.get("DY_GRAPH_BACKWARD", "1") != "0"
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 
-_REGISTRY = dict(Conv=Conv, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
+_REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
@@ -84,7 +84,7 @@ def _rule_c2f(row):                       # the row's repeat count becomes the n
 
 _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
-    FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                                              # tasks.py:743-753
+    C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
     PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
@@ -97,7 +97,7 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2f, SPPF, Upsample)          # (C2f covers FasterC2f / FasterC2f_N) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):
@@ -369,6 +369,7 @@ class BaseModel(nn.Module):
         else:
             self.current_dedark_A = None
             self.current_IcA = None
+        self._check_imgsz(x)
         ops.arena.reset()
         plan = self.__dict__.get("_plan")
         if plan is None or len(plan.nodes) != len(self.model):
@@ -395,6 +396,15 @@ class BaseModel(nn.Module):
                 return m(inp, self.current_dedark_A, self.current_IcA)
             return m(inp) if out is None else m(inp, out=out)
         return plan.run(x, call_layer)
+
+    def _check_imgsz(self, x):
+        """Height and width must be multiples of the largest Detect stride (64 for the P6 graphs): a P6 model fed a 640 image
+        would otherwise fail on a shape mismatch deep inside a head Concat."""
+        m = self.model[-1]
+        if torch.is_tensor(x) and x.dim() == 4 and isinstance(m, Detect):
+            s = int(max(m.strides_as_floats()))
+            if x.shape[2] % s or x.shape[3] % s:
+                raise ValueError(f"image size {x.shape[2]}x{x.shape[3]} is not a multiple of the model's largest stride {s}")
 
     def train(self, mode=True):
         self.__dict__.pop("_graph_params", None)          # (requires_grad flags are read when the mode is set)

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _C
-from ._C import ACT_LEAKY, ACT_NONE, ACT_SILU, ConvDesc, DetMaps, call
+from ._C import ACT_LEAKY, ACT_NONE, ACT_SILU, ConvDesc, DetMaps, DetMaps4, call
 
 _compute_dtype = torch.float32
 _pack_generation = 0        # bumped whenever _pack() allocates a new packed copy
@@ -613,7 +613,8 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
         pa, sa = aff.data_ptr(), 4 * cout_pad                               # rows of aff: scale, shift, mean, invstd
         dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
         gw_, gb_ = _grad_dst(bn.weight), _grad_dst(bn.bias)
-        direct = gw_ is not None and gb_ is not None
+        # the kernels write cout_pad entries: a padded channel count (a 20-class Detect branch in 16-bit) goes through a temporary
+        direct = gw_ is not None and gb_ is not None and cout_pad == Cout
         if not direct:
             dgb = torch.empty((2, cout_pad), dtype=torch.float32, device=dev)
             gw_, gb_ = dgb[0], dgb[1]
@@ -629,8 +630,13 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
                  ptr(bn.weight), ctx.act, 1, ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cout_pad, did, st)
         emu_round(dz)
         if not direct:
-            _add_pgrad(tape, bn.weight, gw_)
-            _add_pgrad(tape, bn.bias, gb_)
+            gd_w, gd_b = _grad_dst(bn.weight), _grad_dst(bn.bias)
+            if gd_w is not None and gd_b is not None:
+                gd_w.copy_(gw_[:Cout])
+                gd_b.copy_(gb_[:Cout])
+            else:
+                _add_pgrad(tape, bn.weight, gw_[:Cout])
+                _add_pgrad(tape, bn.bias, gb_[:Cout])
     else:
         y = ctx.y
         need_bias = ctx.bias is not None and ctx.bias.requires_grad
@@ -859,14 +865,23 @@ def upsample_bwd(dy, scale, dx_out=None, accumulate=False):
     return dx
 
 
+DET_MAX_LEVELS = 4          # DY_DET_MAX_LEVELS
+
+
 def det_maps(maps, strides, nc):
-    """Build the dy_det_maps descriptor for 1-3 NHWC Detect maps [B, 64+nc, h, w]."""
-    m = DetMaps()
+    """Build the descriptor for 1-4 NHWC Detect maps [B, 64+nc, h, w]: a dy_det_maps for up to three levels, a
+    dy_det_maps4 (a DetMaps subclass, passed the same way) for four."""
+    if not 1 <= len(maps) <= DET_MAX_LEVELS:
+        raise ValueError(f"det_maps: {len(maps)} maps; the loss and decode kernels take 1-{DET_MAX_LEVELS}")
+    m = DetMaps4() if len(maps) == 4 else DetMaps()
     m.B, m.nc, m.n_levels = maps[0].shape[0], nc, len(maps)
     m.dtype = dt_id(maps[0].dtype)
-    for i, t in enumerate(maps):
+    for i, t in enumerate(maps[:3]):
         m.map[i] = t.data_ptr()
         m.map_ld[i] = ld_of(t)
         m.h[i], m.w[i] = t.shape[2], t.shape[3]
         m.stride[i] = float(strides[i])
+    if len(maps) == 4:
+        t = maps[3]
+        m.map3, m.map_ld3, m.h3, m.w3, m.stride3 = t.data_ptr(), ld_of(t), t.shape[2], t.shape[3], float(strides[3])
     return m

@@ -206,7 +206,7 @@ def intersect_dicts(da, db, exclude=()):
 # file with the reference (tests/golden/make_ckpt_interop.py).
 _REF_HOME = {"DetectionModel": "ultralytics.nn.tasks"}
 _REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
-_REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
+_REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
                                                                "PconvBottleneck")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
@@ -229,7 +229,7 @@ _FILTERS = (("DeDarkFilter", dict(num_filter_parameters=1, short_name="DF", filt
 
 # plain (non-module, non-parameter) attributes an instance of each reference class carries (g12_ref_skeleton.json); the product's
 # modules hold the same names with the same values plus a few of their own, which must not travel
-_REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2f": ("c",), "Bottleneck": ("add",), "SPPF": (), "DFL": ("c1",),
+_REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottleneck": ("add",), "SPPF": (), "DFL": ("c1",),
               "AsffTribeLevel": ("level", "dim", "inter_dim"), "AsffDoubLevel": ("level", "dim", "inter_dim"), "MFRU": (), "RFBblock": (),
               "SCConv": (), "SRU": ("gate_treshold",), "CRU": ("up_channel", "low_channel"), "GroupBatchnorm2d": ("group_num", "eps"),
               "Detect": ("nc", "nl", "reg_max", "no", "stride"), "AsffDetect": ("nc", "nl", "reg_max", "no", "stride"),

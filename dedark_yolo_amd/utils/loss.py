@@ -137,8 +137,8 @@ class _DetLossFn(torch.autograd.Function):
         dm = ops.det_maps(maps, ctx.strides, crit.nc)
         width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
         dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
-        arr_p = (C.c_void_p * 3)(*[d.data_ptr() for d in dbufs] + [None] * (3 - len(dbufs)))
-        arr_l = (C.c_int64 * 3)(*[ld_of(d) for d in dbufs] + [0] * (3 - len(dbufs)))
+        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
+        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
         g = gloss.detach().to(torch.float32).reshape(1).contiguous()
         call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
              ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), stream())

@@ -222,6 +222,20 @@ typedef struct {
   int B, nc, n_levels, dtype;
 } dy_det_maps;
 
+/* Four-level heads: Detect on P2..P5 (strides 4/8/16/32) or P3..P6 (8..64), i.e. nl = 4 in Detect (U/nn/modules/head.py:19-45)
+ * with make_anchors walking all four maps (U/utils/tal.py:246-258).  dy_det_maps4 starts with a dy_det_maps (n_levels = 4)
+ * and appends the fourth map; pass &x.base wherever a dy_det_maps* is taken.  The entry points read the tail only when
+ * base.n_levels == 4, so 1-3 level callers keep passing a plain dy_det_maps.  Anchors are numbered level by level in the
+ * order of the maps, whatever their strides. */
+#define DY_DET_MAX_LEVELS 4
+typedef struct {
+  dy_det_maps base;
+  const void* map3; /* fourth level: NHWC view [B, h3*w3, no] */
+  int64_t map_ld3;
+  int h3, w3;
+  float stride3;
+} dy_det_maps4;
+
 /* group targets per image: rows (batch_idx, cls, cx, cy, w, h normalised) -> gt[B][n_max][5] = (cls, x1,y1,x2,y2 px),
  * counts[B]; order within an image is preserved (loss.py:124-139). */
 int dy_loss_prepare_targets(const float* batch_idx, const float* cls, const float* bboxes, int n_targets, int B,
@@ -278,8 +292,9 @@ int dy_loss_fwd(const dy_det_maps* m, const float* pred_boxes, const uint8_t* fg
 /* finish: loss_out[0] = (box*hb + cls*hc + dfl*hd)*B + lrl*rec ; items[3] = (box*hb, cls*hc + lrl*rec, dfl*hd) */
 int dy_loss_finish(const double* acc, const float* recovery, float hyp_box, float hyp_cls, float hyp_dfl, float lrl,
                    int B, float* loss_out, float* items, void* stream);
-/* gradient wrt the three maps (written in `dtype`, every element), scaled by *grad_out (device scalar) */
-int dy_loss_bwd(const dy_det_maps* m, void* const dmap[3], const int64_t dmap_ld[3], const float* pred_boxes,
+/* gradient wrt the maps (written in `dtype`, every element), scaled by *grad_out (device scalar); dmap / dmap_ld hold
+ * m->n_levels entries (up to DY_DET_MAX_LEVELS) */
+int dy_loss_bwd(const dy_det_maps* m, void* const* dmap, const int64_t* dmap_ld, const float* pred_boxes,
                 const uint8_t* fg_mask, const float* norm, const int32_t* target_label, const float* target_box,
                 const double* acc, const float* grad_out, float hyp_box, float hyp_cls, float hyp_dfl, void* stream);
 /* Detect eval decode (head.py:66-93): y[B, 4+nc, A] f32 = cat(xywh*stride, sigmoid(cls)) */
