@@ -60,15 +60,20 @@ _SIGS = {
                                vp, i32, vp],
     "dy_conv2d_bn_act_fwd": [C.POINTER(ConvDesc), i64, vp, vp, vp, vp, f32, f32, vp, i32, vp, i64, vp, i64, vp],
     "dy_bn_act_bwd": [vp, i64, vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, i64, i32, i32, vp],
+    "dy_conv2d_bn_act_fwd_valid": [C.POINTER(ConvDesc), i64, vp, vp, vp, vp, f32, f32, vp, i32, vp, i64, vp, i64, i32, vp],
+    "dy_bn_act_bwd_valid": [vp, i64, vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp],
     "dy_pack_weight": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_pack_item_blocks": [i32, i32, i32, i32],
     "dy_pack_weights_multi": [vp, i32, i64, vp],
     "dy_unpack_wgrad": [vp, vp, i32, i32, i32, i32, i32, vp],
     "dy_bn_finalize": [vp, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp],
     "dy_bn_fold_eval": [vp, vp, vp, vp, f32, vp, vp, i32, vp],
+    "dy_bn_finalize_valid": [vp, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp],
+    "dy_bn_fold_eval_valid": [vp, vp, vp, vp, f32, vp, vp, i32, i32, vp],
     "dy_bn_act_fwd": [vp, i64, vp, vp, i32, vp, i64, vp, i64, i64, i32, i32, vp],
     "dy_bn_act_bwd_reduce": [vp, i64, vp, i64, vp, vp, vp, vp, i32, i32, vp, i64, i32, i32, vp],
     "dy_bn_act_bwd_apply": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, vp],
+    "dy_bn_act_bwd_apply_valid": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp],
     "dy_maxpool_fwd": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_maxpool_bwd": [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_upsample_nearest_fwd": [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp],

@@ -31,14 +31,20 @@ template <typename T, bool NTS> __device__ inline void st_s(T* p, const float* i
 
 // one wave per channel: lane r sums replica r, then a wave reduction (the old one-thread-per-channel loop over the 64
 // replicas was a chain of 128 dependent-latency loads: 10 us for a 64-channel layer)
+// Channels Cv..C-1 are vector padding: gamma / beta / running buffers are only Cv long (and may sit right in front of another
+// layer's buffers); the pad channels get scale = shift = mean = invstd = 0, so that y = act(0) = 0 there.
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ stats, double count, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* running_mean, float* running_var,
                                                            float momentum, float eps, float* scale, float* shift, float* mean_out,
-                                                           float* invstd_out, int C) {
+                                                           float* invstd_out, int C, int Cv) {
   static_assert(DY_STATS_REPLICAS == 64, "one replica per lane");
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;
+  if (c >= Cv) {
+    if (lane == 0) scale[c] = shift[c] = mean_out[c] = invstd_out[c] = 0.f;
+    return;
+  }
   double s1 = stats[(long)lane * 2 * C + c];
   double s2 = stats[(long)lane * 2 * C + C + c];
 #pragma unroll
@@ -65,9 +71,14 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
 }
 
 __global__ void bn_fold_eval_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                    float* scale, float* shift, int C) {
+                                    float* scale, float* shift, int C, int Cv) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
+  if (c >= Cv) {                               // pad channel: y = act(0)
+    scale[c] = 0.f;
+    shift[c] = 0.f;
+    return;
+  }
   float sc = gamma[c] / sqrtf(rv[c] + eps);
   scale[c] = sc;
   shift[c] = beta[c] - rm[c] * sc;
@@ -273,14 +284,14 @@ __global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(const T* __restric
                                                                const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                int act, int has_bn, const double* __restrict__ sums,
                                                                T* __restrict__ dz, long dz_ld, float* dgamma, float* dbeta,
-                                                               long pixels, long count, int C, int cgb, int rows) {
+                                                               long pixels, long count, int C, int Cv, int cgb, int rows) {
   constexpr int VE = DT<T>::VE;
   extern __shared__ float lds[];               // [7][nch]: sc, sh, mu, is, k1, K2, K3
   const int nch = cgb * VE, c0 = blockIdx.y * nch;
   const float invM = 1.f / (float)count;
   for (int i = threadIdx.x; i < nch; i += NT) {
     const int c = c0 + i;
-    const bool ok = c < C;
+    const bool ok = c < C, real = c < Cv;      // gamma / dgamma / dbeta exist for the Cv real channels only
     double t1 = 0.0, t2 = 0.0;
     if (ok) {
 #pragma unroll
@@ -288,13 +299,14 @@ __global__ __launch_bounds__(NT) void bn_act_bwd_apply_kernel(const T* __restric
         t1 += sums[(long)r * 2 * C + c];
         if (has_bn) t2 += sums[(long)r * 2 * C + C + c];
       }
-      if (blockIdx.x == 0) {
+      if (blockIdx.x == 0 && real) {
         if (dbeta) dbeta[c] = (float)t1;
         if (dgamma && has_bn) dgamma[c] = (float)t2;
       }
     }
     const float isv = (has_bn && ok) ? invstd[c] : 0.f;
-    const float k1 = has_bn ? ((gamma && ok) ? gamma[c] : 1.f) * isv : 1.f;
+    const float gm = real ? (gamma ? gamma[c] : 1.f) : 0.f;
+    const float k1 = has_bn ? gm * isv : 1.f;
     lds[i] = (scale && ok) ? scale[c] : 1.f;
     lds[nch + i] = (shift && ok) ? shift[c] : 0.f;
     lds[2 * nch + i] = (has_bn && ok) ? mean[c] : 0.f;
@@ -389,23 +401,40 @@ int check_view(const char* who, const void* p, long ld, int C, int dtype) {
 
 }  // namespace
 
+// The *_valid entries take the layer's real channel count C_valid <= C (include/dedark_yolo.h: channel padding); the entries
+// without the suffix keep their original signature and treat all C channels as real.
+extern "C" int dy_bn_finalize_valid(const double* stats, int64_t count, const float* gamma, const float* beta, float* running_mean,
+                                    float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
+                                    float* invstd, int C, int C_valid, void* stream) {
+  DY_CHECK(stats && scale && shift && mean && invstd && C > 0 && count > 0, "dy_bn_finalize: bad args");
+  DY_CHECK(C_valid > 0 && C_valid <= C, "dy_bn_finalize: C_valid=%d outside 1..C=%d", C_valid, C);
+  DY_CHECK(!running_mean == !running_var, "dy_bn_finalize: running_mean and running_var go together");
+  bn_finalize_kernel<<<dy_cdiv(C, 4), 256, 0, (hipStream_t)stream>>>(stats, (double)count, gamma, beta, running_mean,
+                                                                       running_var, momentum, eps, scale, shift, mean,
+                                                                       invstd, C, C_valid);
+  DY_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int dy_bn_finalize(const double* stats, int64_t count, const float* gamma, const float* beta, float* running_mean,
                               float* running_var, float momentum, float eps, float* scale, float* shift, float* mean,
                               float* invstd, int C, void* stream) {
-  DY_CHECK(stats && scale && shift && mean && invstd && C > 0 && count > 0, "dy_bn_finalize: bad args");
-  bn_finalize_kernel<<<dy_cdiv(C, 4), 256, 0, (hipStream_t)stream>>>(stats, (double)count, gamma, beta, running_mean,
-                                                                       running_var, momentum, eps, scale, shift, mean,
-                                                                       invstd, C);
+  return dy_bn_finalize_valid(stats, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean, invstd, C, C,
+                              stream);
+}
+
+extern "C" int dy_bn_fold_eval_valid(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                     float* scale, float* shift, int C, int C_valid, void* stream) {
+  DY_CHECK(gamma && beta && rm && rv && scale && shift && C > 0, "dy_bn_fold_eval: bad args");
+  DY_CHECK(C_valid > 0 && C_valid <= C, "dy_bn_fold_eval: C_valid=%d outside 1..C=%d", C_valid, C);
+  bn_fold_eval_kernel<<<dy_cdiv(C, 128), 128, 0, (hipStream_t)stream>>>(gamma, beta, rm, rv, eps, scale, shift, C, C_valid);
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_bn_fold_eval(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                                float* scale, float* shift, int C, void* stream) {
-  DY_CHECK(gamma && beta && rm && rv && scale && shift && C > 0, "dy_bn_fold_eval: bad args");
-  bn_fold_eval_kernel<<<dy_cdiv(C, 128), 128, 0, (hipStream_t)stream>>>(gamma, beta, rm, rv, eps, scale, shift, C);
-  DY_LAUNCH_CHECK();
-  return 0;
+  return dy_bn_fold_eval_valid(gamma, beta, rm, rv, eps, scale, shift, C, C, stream);
 }
 
 extern "C" int dy_bn_act_fwd(const void* z, int64_t z_ld, const float* scale, const float* shift, int act,
@@ -454,14 +483,15 @@ extern "C" int dy_bn_act_bwd_reduce(const void* dy, int64_t dy_ld, const void* z
   return 0;
 }
 
-extern "C" int dy_bn_act_bwd_apply(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale,
-                                   const float* shift, const float* mean, const float* invstd, const float* gamma, int act,
-                                   int has_bn, const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta,
-                                   int64_t pixels, int C, int dtype, void* stream) {
+extern "C" int dy_bn_act_bwd_apply_valid(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale,
+                                         const float* shift, const float* mean, const float* invstd, const float* gamma, int act,
+                                         int has_bn, const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta,
+                                         int64_t pixels, int C, int C_valid, int dtype, void* stream) {
   if (int e = check_view("dy_bn_act_bwd_apply(dy)", dy, dy_ld, C, dtype)) return e;
   if (int e = check_view("dy_bn_act_bwd_apply(z)", z, z_ld, C, dtype)) return e;
   if (int e = check_view("dy_bn_act_bwd_apply(dz)", dz, dz_ld, C, dtype)) return e;
   DY_CHECK(sums && (!has_bn || (mean && invstd)), "dy_bn_act_bwd_apply: null stats");
+  DY_CHECK(C_valid > 0 && C_valid <= C, "dy_bn_act_bwd_apply: C_valid=%d outside 1..C=%d", C_valid, C);
   // pixels == 0: only the parameter gradients (dgamma / dbeta) are written
   const int ve = dtype == DY_F32 ? 4 : 8;
   const Geo g = geometry(pixels > 0 ? pixels : 1, C, ve, 2);
@@ -471,7 +501,7 @@ extern "C" int dy_bn_act_bwd_apply(const void* dy, int64_t dy_ld, const void* z,
   dy_note_kernel("bn_act_bwd_apply_kernel");
 #define APPLY(T_, U_) bn_act_bwd_apply_kernel<T_, U_, (U_ == 1)><<<g.grid, NT, shm, st>>>((const T_*)dy, dy_ld, (const T_*)z, z_ld, scale, shift, mean, invstd, \
                                                                             gamma, act, has_bn, sums, (T_*)dz, dz_ld, dgamma, dbeta, pixels, \
-                                                                            pixels > 0 ? pixels : 1, C, g.cgb, g.rows)
+                                                                            pixels > 0 ? pixels : 1, C, C_valid, g.cgb, g.rows)
   if (dtype == DY_F32) { if (big) APPLY(float, 1); else APPLY(float, 2); }
   else if ((dtype) == DY_F16) { if (big) APPLY(f16_t, 1); else APPLY(f16_t, 2); }
   else { if (big) APPLY(bf16_t, 1); else APPLY(bf16_t, 2); }
@@ -480,13 +510,27 @@ extern "C" int dy_bn_act_bwd_apply(const void* dy, int64_t dy_ld, const void* z,
   return 0;
 }
 
+extern "C" int dy_bn_act_bwd_apply(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale,
+                                   const float* shift, const float* mean, const float* invstd, const float* gamma, int act,
+                                   int has_bn, const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta,
+                                   int64_t pixels, int C, int dtype, void* stream) {
+  return dy_bn_act_bwd_apply_valid(dy, dy_ld, z, z_ld, scale, shift, mean, invstd, gamma, act, has_bn, sums, dz, dz_ld, dgamma, dbeta,
+                                   pixels, C, C, dtype, stream);
+}
+
 // both backward passes behind one call (aff = [scale | shift | mean | invstd], C floats each)
-extern "C" int dy_bn_act_bwd(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* aff, const float* gamma, int act,
-                             double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C, int dtype,
-                             void* stream) {
+extern "C" int dy_bn_act_bwd_valid(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* aff, const float* gamma,
+                                   int act, double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C,
+                                   int C_valid, int dtype, void* stream) {
   DY_CHECK(aff, "dy_bn_act_bwd: null affine buffer");
   if (int e = dy_bn_act_bwd_reduce(dy, dy_ld, z, z_ld, aff, aff + C, aff + 2 * C, aff + 3 * C, act, 1, sums, pixels, C, dtype, stream))
     return e;
-  return dy_bn_act_bwd_apply(dy, dy_ld, z, z_ld, aff, aff + C, aff + 2 * C, aff + 3 * C, gamma, act, 1, sums, dz, dz_ld, dgamma, dbeta,
-                             pixels, C, dtype, stream);
+  return dy_bn_act_bwd_apply_valid(dy, dy_ld, z, z_ld, aff, aff + C, aff + 2 * C, aff + 3 * C, gamma, act, 1, sums, dz, dz_ld, dgamma,
+                                   dbeta, pixels, C, C_valid, dtype, stream);
+}
+
+extern "C" int dy_bn_act_bwd(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* aff, const float* gamma, int act,
+                             double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C, int dtype,
+                             void* stream) {
+  return dy_bn_act_bwd_valid(dy, dy_ld, z, z_ld, aff, gamma, act, sums, dz, dz_ld, dgamma, dbeta, pixels, C, C, dtype, stream);
 }

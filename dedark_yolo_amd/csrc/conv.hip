@@ -1243,16 +1243,25 @@ extern "C" int dy_unpack_wgrad(const float* dwp, float* g, int Cout, int Cin, in
 // ---- merged entries: the same launches as the separate calls, one foreign-function call instead of two or three.  The step of
 // BASELINE configs[1] issues ~700 launches from Python at ~10 us of interpreter + ctypes time each and had become host-bound
 // (tools/host_time.py: 9.6 ms to issue a step the GPU finishes in 9.9 ms).
+extern "C" int dy_conv2d_bn_act_fwd_valid(const dy_conv_desc* d, int64_t count, const float* gamma, const float* beta,
+                                          float* running_mean, float* running_var, float momentum, float eps, float* aff, int act,
+                                          const void* residual, int64_t res_ld, void* y, int64_t y_ld, int C_valid, void* stream) {
+  DY_CHECK(d && d->stats && d->dst && aff, "dy_conv2d_bn_act_fwd: needs a raw-output buffer, statistics and the affine buffer");
+  DY_CHECK(C_valid > 0 && C_valid <= d->Cd, "dy_conv2d_bn_act_fwd: C_valid=%d outside 1..Cd=%d", C_valid, d->Cd);
+  if (int e = dy_conv2d_fwd(d, stream)) return e;
+  const int C = d->Cd;
+  if (int e = dy_bn_finalize_valid(d->stats, count, gamma, beta, running_mean, running_var, momentum, eps, aff, aff + C, aff + 2 * C,
+                                   aff + 3 * C, C, C_valid, stream))
+    return e;
+  return dy_bn_act_fwd(d->dst, d->dst_ld, aff, aff + C, act, residual, res_ld, y, y_ld, (int64_t)d->N * d->Hd * d->Wd, C, d->dtype, stream);
+}
+
 extern "C" int dy_conv2d_bn_act_fwd(const dy_conv_desc* d, int64_t count, const float* gamma, const float* beta, float* running_mean,
                                     float* running_var, float momentum, float eps, float* aff, int act, const void* residual,
                                     int64_t res_ld, void* y, int64_t y_ld, void* stream) {
-  DY_CHECK(d && d->stats && d->dst && aff, "dy_conv2d_bn_act_fwd: needs a raw-output buffer, statistics and the affine buffer");
-  if (int e = dy_conv2d_fwd(d, stream)) return e;
-  const int C = d->Cd;
-  if (int e = dy_bn_finalize(d->stats, count, gamma, beta, running_mean, running_var, momentum, eps, aff, aff + C, aff + 2 * C,
-                             aff + 3 * C, C, stream))
-    return e;
-  return dy_bn_act_fwd(d->dst, d->dst_ld, aff, aff + C, act, residual, res_ld, y, y_ld, (int64_t)d->N * d->Hd * d->Wd, C, d->dtype, stream);
+  DY_CHECK(d, "dy_conv2d_bn_act_fwd: null descriptor");
+  return dy_conv2d_bn_act_fwd_valid(d, count, gamma, beta, running_mean, running_var, momentum, eps, aff, act, residual, res_ld, y, y_ld,
+                                    d->Cd, stream);
 }
 
 extern "C" int dy_conv2d_wgrad_forked(void* wait_for, const void* x, int64_t x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz,

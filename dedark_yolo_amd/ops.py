@@ -320,7 +320,7 @@ def _padded_vec(v, n):
 # ------------------------------------------------------------------------------------------------ conv + bn + act
 def bn_fold(bn, cout_pad):
     """scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale as a cached [2, cout_pad] f32 tensor on the
-    BatchNorm module.  The fold is recomputed only when a weight or buffer changed (optimizer step, load_state_dict, a training
+    BatchNorm module (0 / 0 on the pad channels past bn.num_features).  The fold is recomputed only when a weight or buffer changed (optimizer step, load_state_dict, a training
     forward): `BaseModel.fuse()` fills every cache up front, afterwards an eval forward launches no fold kernel at all."""
     tag = (_weights_epoch, bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
            bn.weight.data_ptr(), bn.running_mean.data_ptr(), cout_pad)
@@ -329,8 +329,8 @@ def bn_fold(bn, cout_pad):
         return hit[1]
     aff = hit[1] if (hit is not None and hit[1].shape[1] == cout_pad and hit[1].device == bn.weight.device) else \
         torch.empty((2, cout_pad), dtype=torch.float32, device=bn.weight.device)
-    call("dy_bn_fold_eval", ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps),
-         ptr(aff[0]), ptr(aff[1]), cout_pad, stream())
+    call("dy_bn_fold_eval_valid", ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps),
+         ptr(aff[0]), ptr(aff[1]), cout_pad, bn.weight.numel(), stream())
     bn.__dict__["_dy_fold"] = (tag, aff)
     return aff
 
@@ -413,15 +413,15 @@ def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pa
         bp = bn._parameters
         if _C._prof is None and _emulate_storage is None:
             # conv (raw z + statistics) -> finalize -> affine/activation/residual: three launches, ONE foreign call
-            call("dy_conv2d_bn_act_fwd", C.byref(d), pixels, ptr(bp["weight"]), ptr(bp["bias"]), ptr(bn.running_mean), ptr(bn.running_var),
-                 float(bn.momentum), float(bn.eps), pa, act, rp, rld, y.data_ptr(), ld_of(y), st)
+            call("dy_conv2d_bn_act_fwd_valid", C.byref(d), pixels, ptr(bp["weight"]), ptr(bp["bias"]), ptr(bn.running_mean), ptr(bn.running_var),
+                 float(bn.momentum), float(bn.eps), pa, act, rp, rld, y.data_ptr(), ld_of(y), Cout, st)
         else:                               # per-entry timing (bench.py roofline leg, tools/layer_profile.py)
             _C.set_meta(kind="conv_fwd", shape=f"{Cin}->{Cout} k{KH} s{stride} in {B}x{H}x{W}", dtype=str(dtype), flops=2.0 * pixels * Cout * KH * KW * Cin,
                         bytes=float((B * H * W * Cin + pixels * Cout + Cout * KH * KW * Cin) * x.element_size()))
             call("dy_conv2d_fwd", C.byref(d), st)
             emu_round(z)                    # (the statistics come from the f32 accumulators in every dtype)
-            call("dy_bn_finalize", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                 ptr(bn.running_var), float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cout_pad, st)
+            call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+                 ptr(bn.running_var), float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cout_pad, Cout, st)
             _C.set_meta(kind="bn_act_fwd", shape=f"{cout_pad}ch {B}x{Ho}x{Wo}", dtype=str(dtype), flops=0.0,
                         bytes=float(pixels * cout_pad * x.element_size() * (3 if residual is not None else 2)))
             call("dy_bn_act_fwd", ptr(z), ld_of(z), pa, pa + sa, act, rp, rld, ptr(y), ld_of(y), pixels, cout_pad, dt_id(dtype), st)
@@ -613,30 +613,25 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
         pa, sa = aff.data_ptr(), 4 * cout_pad                               # rows of aff: scale, shift, mean, invstd
         dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
         gw_, gb_ = _grad_dst(bn.weight), _grad_dst(bn.bias)
-        # the kernels write cout_pad entries: a padded channel count (a 20-class Detect branch in 16-bit) goes through a temporary
-        direct = gw_ is not None and gb_ is not None and cout_pad == Cout
+        # (the kernels write Cout entries of dgamma / dbeta, also when the views are padded to cout_pad channels)
+        direct = gw_ is not None and gb_ is not None
         if not direct:
-            dgb = torch.empty((2, cout_pad), dtype=torch.float32, device=dev)
+            dgb = torch.empty((2, Cout), dtype=torch.float32, device=dev)
             gw_, gb_ = dgb[0], dgb[1]
         if _C._prof is None or _emulate_storage is not None:
-            call("dy_bn_act_bwd", dy.data_ptr(), ld_of(dy), z.data_ptr(), ld_of(z), pa, ptr(bn._parameters["weight"]), ctx.act,
-                 sums.data_ptr(), dz.data_ptr(), ld_of(dz), gw_.data_ptr(), gb_.data_ptr(), pixels, cout_pad, did, st)
+            call("dy_bn_act_bwd_valid", dy.data_ptr(), ld_of(dy), z.data_ptr(), ld_of(z), pa, ptr(bn._parameters["weight"]), ctx.act,
+                 sums.data_ptr(), dz.data_ptr(), ld_of(dz), gw_.data_ptr(), gb_.data_ptr(), pixels, cout_pad, Cout, did, st)
         else:
             _C.set_meta(kind="bn_act_bwd_reduce", shape=f"{cout_pad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cout_pad * x.element_size() * 2))
             call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
                  ctx.act, 1, ptr(sums), pixels, cout_pad, did, st)
             _C.set_meta(kind="bn_act_bwd_apply", shape=f"{cout_pad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cout_pad * x.element_size() * 3))
-            call("dy_bn_act_bwd_apply", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
-                 ptr(bn.weight), ctx.act, 1, ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cout_pad, did, st)
+            call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
+                 ptr(bn.weight), ctx.act, 1, ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cout_pad, Cout, did, st)
         emu_round(dz)
         if not direct:
-            gd_w, gd_b = _grad_dst(bn.weight), _grad_dst(bn.bias)
-            if gd_w is not None and gd_b is not None:
-                gd_w.copy_(gw_[:Cout])
-                gd_b.copy_(gb_[:Cout])
-            else:
-                _add_pgrad(tape, bn.weight, gw_[:Cout])
-                _add_pgrad(tape, bn.bias, gb_[:Cout])
+            _add_pgrad(tape, bn.weight, gw_)
+            _add_pgrad(tape, bn.bias, gb_)
     else:
         y = ctx.y
         need_bias = ctx.bias is not None and ctx.bias.requires_grad
@@ -650,12 +645,12 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
             db = gb_ if gb_ is not None else torch.empty(cout_pad, dtype=torch.float32, device=dev)
             if ctx.act == ACT_NONE:
                 dz = dy
-                call("dy_bn_act_bwd_apply", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
-                     ptr(sums), ptr(dy), ld_of(dy), None, ptr(db), 0, cout_pad, did, st)      # 0 pixels: only dbias
+                call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
+                     ptr(sums), ptr(dy), ld_of(dy), None, ptr(db), 0, cout_pad, Cout, did, st)      # 0 pixels: only dbias
             else:
                 dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
-                call("dy_bn_act_bwd_apply", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
-                     ptr(sums), ptr(dz), ld_of(dz), None, ptr(db), pixels, cout_pad, did, st)
+                call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
+                     ptr(sums), ptr(dz), ld_of(dz), None, ptr(db), pixels, cout_pad, Cout, did, st)
                 emu_round(dz)
             if need_bias and gb_ is None:
                 gd = _grad_dst(ctx.bias)

@@ -113,6 +113,19 @@ int dy_bn_finalize(const double* stats, int64_t count, const float* gamma, const
 /* eval-mode fold: scale = gamma/sqrt(var+eps), shift = beta - mean*scale */
 int dy_bn_fold_eval(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
                     float* scale, float* shift, int C, void* stream);
+/* Channel padding.  The entries above and below treat all C channels as real: every per-channel buffer is C floats.  Their
+ * *_valid variants take the layer's real channel count C_valid <= C as well, for views padded to C channels (C = Cout rounded
+ * up to 4 in f32, to 8 in bf16 / f16):
+ *   - gamma, beta, running_mean, running_var, dgamma and dbeta are C_valid floats; nothing at or past index C_valid is read or
+ *     written (a flat parameter store puts the next tensor right there);
+ *   - stats, sums, scale, shift, mean, invstd and aff stay C wide; the pad channels get scale = shift = mean = invstd = 0, so
+ *     the pad lanes of y are act(0) = 0 and those of dz are 0.
+ * dy_X(..., C, ...) is dy_X_valid(..., C, C, ...). */
+int dy_bn_finalize_valid(const double* stats, int64_t count, const float* gamma, const float* beta, float* running_mean,
+                         float* running_var, float momentum, float eps, float* scale, float* shift, float* mean, float* invstd,
+                         int C, int C_valid, void* stream);
+int dy_bn_fold_eval_valid(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                          float* scale, float* shift, int C, int C_valid, void* stream);
 /* y = act(z*scale + shift) (+ residual); views over `pixels` pixels x C channels */
 int dy_bn_act_fwd(const void* z, int64_t z_ld, const float* scale, const float* shift, int act, const void* residual,
                   int64_t res_ld, void* y, int64_t y_ld, int64_t pixels, int C, int dtype, void* stream);
@@ -129,6 +142,10 @@ int dy_bn_act_bwd_apply(const void* dy, int64_t dy_ld, const void* z, int64_t z_
                         const float* mean, const float* invstd, const float* gamma, int act, int has_bn,
                         const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C,
                         int dtype, void* stream);
+int dy_bn_act_bwd_apply_valid(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale, const float* shift,
+                              const float* mean, const float* invstd, const float* gamma, int act, int has_bn,
+                              const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C,
+                              int C_valid, int dtype, void* stream);
 
 /* ----------------------------------------------------------------------------- pooling / resampling / concat
  * SPPF's 3 chained MaxPool2d(5,1,2) (block.py:331-338), ASFF's MaxPool2d(2,2) and max_pool2d(3,2,1) (block.py:58,85-86),
@@ -367,6 +384,13 @@ int dy_conv2d_bn_act_fwd(const dy_conv_desc* d, int64_t count, const float* gamm
                          void* y, int64_t y_ld, void* stream);
 int dy_bn_act_bwd(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* aff, const float* gamma, int act,
                   double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C, int dtype, void* stream);
+/* ... with channel padding (see dy_bn_finalize_valid): C = Cd of the descriptor / of the views, C_valid real channels */
+int dy_conv2d_bn_act_fwd_valid(const dy_conv_desc* d, int64_t count, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float momentum, float eps, float* aff, int act, const void* residual,
+                               int64_t res_ld, void* y, int64_t y_ld, int C_valid, void* stream);
+int dy_bn_act_bwd_valid(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* aff, const float* gamma, int act,
+                        double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C, int C_valid,
+                        int dtype, void* stream);
 int dy_conv2d_wgrad_forked(void* wait_for, const void* x, int64_t x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz,
                            int64_t dz_ld, int Ho, int Wo, int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout,
                            int Cin, float* scratch, int64_t scratch_elems, float* g_oihw, int dtype, void* stream);

@@ -327,7 +327,7 @@ def test_fuse_caches_the_batchnorm_fold():
             y1 = m(x)[0]
     finally:
         ops.call = orig
-    assert "dy_bn_fold_eval" not in calls and torch.equal(y0, y1)
+    assert not any(c.startswith("dy_bn_fold_eval") for c in calls) and torch.equal(y0, y1)
     ops.bump_weights_epoch()                          # what an optimizer step does
     assert not m.is_fused()
     m.fuse()
