@@ -49,6 +49,17 @@ class AugSample(C.Structure):
                 ("lut", (C.c_uint8 * 256) * 3)]
 
 
+class SegDesc(C.Structure):
+    """dy_seg_desc (include/dedark_yolo.h)"""
+    _fields_ = [("mc", vp), ("mc_ld", i64), ("proto", vp), ("proto_ld", i64), ("B", i32), ("A", i32), ("nm", i32), ("mh", i32),
+                ("mw", i32), ("target_gt_idx", vp), ("fg_mask", vp), ("target_box", vp), ("masks", vp), ("mask_dtype", i32),
+                ("mask_h", i32), ("mask_w", i32), ("overlap", i32), ("gt_rows", vp), ("n_max", i32), ("img_h", f32), ("img_w", f32),
+                ("pos", vp), ("npos", vp), ("dtype", i32)]
+
+
+BIAS_GRAD_CHUNKS = 2048      # DY_BIAS_GRAD_CHUNKS
+
+
 _SIGS = {
     "dy_version": [],
     "dy_frontend_init": [],
@@ -128,6 +139,15 @@ _SIGS = {
     "dy_ema_lerp": [vp, vp, f32, i64, vp],
     "dy_grad_accumulate": [vp, vp, i64, vp],
     "dy_stream_fork": [vp, vp],
+    "dy_seg_positives": [vp, i32, i32, vp, vp, vp],
+    "dy_seg_gt_rows": [vp, i32, i32, i32, vp, vp],
+    "dy_seg_loss_fwd": [C.POINTER(SegDesc), f32, vp, vp, vp, vp],
+    "dy_seg_loss_bwd": [C.POINTER(SegDesc), vp, f32, vp, i64, vp, i64, vp],
+    "dy_bias_add": [vp, i64, vp, i64, i32, i32, vp],
+    "dy_bias_grad": [vp, i64, i64, i32, i32, vp, i64, vp, vp],
+    "dy_seg_mask_decode": [vp, i64, i32, i32, i32, vp, i64, vp, i32, f32, f32, i32, vp, vp],
+    "dy_seg_crop_mask": [vp, vp, i32, i32, i32, vp],
+    "dy_seg_mask_iou": [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp],
 }
 
 _lib = None

@@ -8,11 +8,16 @@ from ..nn.tasks import DetectionModel
 from .trainer import DetectionTrainer, get_cfg
 
 
+def _model_class(task):
+    from ..nn.tasks import SegmentationModel
+    return SegmentationModel if task == "segment" else DetectionModel
+
+
 class YOLO:
     def __init__(self, model="yolov8l.yaml", task=None):
-        if task not in (None, "detect"):
-            raise NotImplementedError("only the detect task is on the Dedark-YOLO hot path")
-        self.task = "detect"
+        if task not in (None, "detect", "segment"):
+            raise NotImplementedError("only the detect and segment tasks are on the Dedark-YOLO hot path")
+        self.task = task
         self.trainer = None
         self.overrides = {}
         suffix = Path(str(model)).suffix
@@ -24,9 +29,13 @@ class YOLO:
             raise FileNotFoundError(f"'{model}': expected a model .yaml or a state_dict checkpoint .pt")
 
     def _new(self, cfg):
+        from ..nn.tasks import guess_model_task, yaml_model_load
         self.cfg = cfg
-        self.model = DetectionModel(cfg)
+        d = yaml_model_load(cfg)
+        self.task = self.task or guess_model_task(d)
+        self.model = _model_class(self.task)(d)
         self.overrides["model"] = cfg
+        self.overrides["task"] = self.task
 
     def _load(self, weights):
         """reference nn/tasks.py:592-630,674-707 (attempt_load_one_weight): `ckpt.get('ema') or ckpt['model']`, cast to fp32.  Reads
@@ -36,7 +45,11 @@ class YOLO:
         cfg = ck.yaml
         if cfg is None:
             raise RuntimeError(f"{weights}: the checkpoint carries no model yaml")
-        self.model = DetectionModel(cfg, nc=ck.nc)
+        from ..nn.tasks import guess_model_task, yaml_model_load
+        d = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        self.task = self.task or guess_model_task(d)
+        self.model = _model_class(self.task)(d, nc=ck.nc)
+        self.overrides["task"] = self.task
         n = self.model.load(ck.state_dict)
         if n == 0:
             raise RuntimeError(f"{weights}: no tensor of the checkpoint matches the graph of its yaml")
@@ -69,10 +82,10 @@ class YOLO:
         return self.trainer.train(loader)
 
     def val(self, loader=None, **kwargs):
-        from .validator import DetectionValidator
+        from .validator import DetectionValidator, SegmentationValidator
         ov = dict(self.overrides)
         ov.update(kwargs)
-        v = DetectionValidator(get_cfg(ov))
+        v = (SegmentationValidator if self.task == "segment" else DetectionValidator)(get_cfg(ov))
         return v(self.model, loader)
 
     @torch.no_grad()
@@ -84,6 +97,8 @@ class YOLO:
         from ..utils import ops as uops
         from .results import Results
         from .validator import DetectionValidator
+        if self.task == "segment":
+            raise NotImplementedError("predict() of a segment model: mask outputs (process_mask_upsample) are not implemented")
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("predict() needs the model on a GPU (there is no CPU path)")

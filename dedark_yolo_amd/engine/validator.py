@@ -12,7 +12,7 @@ from .. import ops as kops
 from .._C import call
 from ..ops import ptr, stream
 from ..utils import ops
-from ..utils.metrics import DetMetrics, box_iou
+from ..utils.metrics import DetMetrics, SegmentMetrics, box_iou
 
 
 def match_predictions(detections, labels, iouv):
@@ -26,11 +26,17 @@ def match_predictions(detections, labels, iouv):
          rows that the first one has re-ordered by detection index, so it is not the best-overlapping one).
     The detections that survive both steps are correct at that threshold."""
     iou = box_iou(labels[:, 1:], detections[:, :4]).numpy()
+    return match_from_iou(iou, labels[:, 0], detections[:, 5], iouv)
+
+
+def match_from_iou(iou, label_cls, det_cls, iouv):
+    """match_predictions' rule on a precomputed IoU matrix [n_labels, n_detections] (numpy; the mask IoU of the segment validator,
+    reference segment/val.py:185-209): label_cls [M], det_cls [N] host tensors -> bool [N, len(iouv)]."""
     n_lab, n_det = iou.shape
     correct = np.zeros((n_det, len(iouv)), dtype=bool)
     if n_lab == 0 or n_det == 0:
         return torch.from_numpy(correct)
-    same_cls = (labels[:, 0:1] == detections[:, 5]).numpy()
+    same_cls = (label_cls.view(-1, 1) == det_cls.view(1, -1)).numpy()
     thr = np.asarray(iouv, dtype=iou.dtype)
     for k in range(len(thr)):
         cand = (iou >= thr[k]) & same_cls
@@ -144,3 +150,62 @@ class DetectionValidator:
         stats = self.get_stats()
         model.train(was_training)
         return {k: float(v) for k, v in stats.items()}
+
+
+class SegmentationValidator(DetectionValidator):
+    """Segment validator (reference models/yolo/segment/val.py): NMS with the mask-coefficient columns, masks decoded at the
+    proto resolution (process_mask, upsample=False; dy_seg_mask_decode), mask IoU against the gt masks with integer counts
+    (dy_seg_mask_iou), box and mask `correct` matrices by the same matching rule, SegmentMetrics.  The gt masks must be at the
+    proto resolution (the reference's bilinear resize of other sizes is not implemented)."""
+
+    def __init__(self, args=None, dataloader=None):
+        super().__init__(args, dataloader)
+        self.args.task = "segment"
+        self.metrics = SegmentMetrics()
+
+    def postprocess(self, preds):
+        a = self.args
+        p = ops.non_max_suppression(preds[0], self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
+                                    max_det=a.max_det, nc=self.nc)
+        proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]
+        return p, proto
+
+    def update_metrics(self, preds, batch):
+        dets, proto = preds
+        overlap = bool(getattr(self.args, "overlap_mask", True))
+        height, width = batch["img"].shape[2:]
+        pmasks = ops.process_masks_batched(proto, [d[:, :6 + proto.shape[1]] for d in dets], (height, width))
+        masks = batch["masks"]
+        if tuple(masks.shape[-2:]) != tuple(proto.shape[2:]):
+            raise NotImplementedError(f"segment validation: gt masks {tuple(masks.shape[-2:])} are not at the proto resolution "
+                                      f"{tuple(proto.shape[2:])} (the bilinear path is not implemented)")
+        masks = masks.to(self.device, non_blocking=True)
+        bi = batch["batch_idx"].cpu()
+        cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
+        for si, pred in enumerate(dets):
+            idx = bi == si
+            cls, bbox = cls_all[idx], box_all[idx]
+            nl, npr = cls.shape[0], pred.shape[0]
+            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
+            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
+            correct_b = torch.zeros(npr, self.niou, dtype=torch.bool)
+            correct_m = torch.zeros(npr, self.niou, dtype=torch.bool)
+            self.seen += 1
+            if npr == 0:
+                if nl:
+                    self.stats.append((correct_b, correct_m, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
+                continue
+            if nl:
+                gt = masks[si] if overlap else masks[idx.to(masks.device)]
+                iou_m = ops.mask_iou_binary(gt, pmasks[si], overlap, nl).cpu().numpy()
+            pred = pred.cpu()
+            if getattr(self.args, "single_cls", False):
+                pred[:, 5] = 0
+            predn = pred[:, :6].clone()
+            ops.scale_boxes((height, width), predn[:, :4], shape, ratio_pad=ratio_pad)
+            if nl:
+                tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
+                ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
+                correct_b = match_predictions(predn, torch.cat((cls, tbox), 1), self.iouv)
+                correct_m = match_from_iou(iou_m, cls[:, 0], predn[:, 5], self.iouv)
+            self.stats.append((correct_b, correct_m, pred[:, 4], pred[:, 5], cls.squeeze(-1)))

@@ -18,7 +18,7 @@ from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
 __all__ = ("Conv", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
-           "AsffDetect",
+           "AsffDetect", "Proto", "Segment",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
 
@@ -1016,6 +1016,112 @@ class AsffDetect(Detect):
             raise RuntimeError("AsffDetect: gradient map lacks channel padding")
         dx = conv_backward(tape, g[:, r:r + self.nc])                      # cv3[i][0]
         return conv_backward(tape, g[:, :r], dx_out=dx, accumulate=True)   # cv2[i][0]
+
+
+class Proto(DyModule):
+    """YOLOv8 mask prototypes (reference block.py:242-254): Conv3x3 -> ConvTranspose2d(c_, c_, 2, 2) -> Conv3x3 -> Conv1x1.  The
+    transposed conv runs on the conv kernels (ops.conv_transpose2x2_forward)."""
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def _fwd(self, tape, x):
+        t = self.cv1._fwd(tape, x)
+        t = ops.conv_transpose2x2_forward(tape, t, self.upsample.weight, self.upsample.bias)
+        return self.cv3._fwd(tape, self.cv2._fwd(tape, t))
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        g = self.cv2._bwd(tape, self.cv3._bwd(tape, dy))
+        g = ops.conv_transpose2x2_backward(tape, g)
+        return self.cv1._bwd(tape, g, needs=needs, dx_out=dx_out, accumulate=accumulate)
+
+
+class Segment(Detect):
+    """YOLOv8 segment head (reference head.py:177-200): Detect plus per-level mask-coefficient chains cv4[i] = Conv3x3, Conv3x3,
+    Conv2d(c4 -> nm, 1) and a Proto on the finest level.  Train: (maps, mc [B, nm, A], p [B, nm, mh, mw]); eval:
+    (cat([y, mc], 1) [B, 4+nc+nm, A] f32, (maps, mc, p)).
+
+    mc lives in one [B, A, nm] buffer (one NHWC row per anchor): each level's final 1x1 conv result is copied into its anchor
+    range, and the loss writes its gradient in the same layout.  The cv4 chains run inside the level chains that
+    Detect._run_levels forks onto the branch streams; the Proto runs on the compute stream."""
+
+    def __init__(self, nc=80, nm=32, npr=256, ch=()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        self.detect = Detect.forward
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+
+    @staticmethod
+    def _offsets(ts):
+        offs, o = [], 0
+        for t in ts:
+            offs.append(o)
+            o += t.shape[2] * t.shape[3]
+        return offs, o
+
+    def _seg_level_fwd(self, tape, i, x, mc, off):
+        a, b, c = self.cv4[i]
+        y = plain_conv_fwd(tape, c, b._fwd(tape, a._fwd(tape, x)))
+        B, _, H, W = y.shape
+        mc[:, off:off + H * W].view(B, H, W, self.nm).copy_(y.permute(0, 2, 3, 1))
+        return self._level_fwd(tape, i, x)            # Detect's branches: their contexts sit on top of the tape
+
+    def _seg_level_bwd(self, tape, i, g, dmc, off):
+        dx = self._level_bwd(tape, i, g)
+        B, _, H, W = g.shape
+        gl = empty_nhwc(B, self.nm, H, W, g.dtype, g.device)
+        gl.permute(0, 2, 3, 1).view(B, H * W, self.nm).copy_(dmc[:, off:off + H * W])   # .view: raises if gl were not dense
+        gt = self.cv4[i][1]._bwd(tape, conv_backward(tape, gl))
+        return self.cv4[i][0]._bwd(tape, gt, dx_out=dx, accumulate=True)
+
+    def _fwd(self, tape, *xs):
+        if self.nm % ops.vec_elems(xs[0].dtype):
+            raise NotImplementedError("Segment: nm must be a multiple of the vector width")
+        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        offs, A = self._offsets(xs)
+        mc = torch.empty((B, A, self.nm), dtype=dt, device=dev)
+        ptape = Tape() if tape is not None else None
+        p = self.proto._fwd(ptape, xs[0])
+        subs = [Tape() if tape is not None else None for _ in xs]
+        maps = self._run_levels(lambda t, i, x: self._seg_level_fwd(t, i, x, mc, offs[i]), subs, list(xs))
+        if tape is not None:
+            tape.push((subs, ptape))
+        mc4 = mc.permute(0, 2, 1).unsqueeze(2)         # [B, nm, 1, A]: a 4-d NHWC view (pixel stride nm) for the graph plumbing
+        if self.training:
+            return [*maps, mc4, p]
+        m = ops.det_maps(maps, self.strides_as_floats(), self.nc)
+        y = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev)
+        call("dy_detect_decode", C.byref(m), ptr(y), stream())
+        return (y, *maps, mc4, p)
+
+    def _wrap(self, out):
+        n = self.nl
+        if self.training:
+            return list(out[:n]), out[n].squeeze(2), out[n + 1]
+        mc = out[1 + n].squeeze(2)
+        return torch.cat([out[0], mc.float()], 1), (list(out[1:1 + n]), mc, out[2 + n])
+
+    def _bwd(self, tape, *gs, needs=None):
+        if not self.training:
+            raise RuntimeError("Segment: backward through the eval decode is not supported")
+        n = self.nl
+        subs, ptape = tape.pop()
+        dmc = gs[n].squeeze(2).permute(0, 2, 1)        # [B, A, nm]
+        offs, _ = self._offsets(gs[:n])
+        dxs = self._run_levels(lambda t, i, g: self._seg_level_bwd(t, i, g, dmc, offs[i]), subs, list(gs[:n]))
+        self.proto._bwd(ptape, gs[n + 1], dx_out=dxs[0], accumulate=True)
+        for t in subs + [ptape]:
+            assert not t.stack, "Segment: unbalanced tape"
+            for p, g in t.pgrads.items():
+                ops._add_pgrad(tape, p, g)
+        return dxs
 
 
 # ------------------------------------------------------------------------------------------------ low-light front-end

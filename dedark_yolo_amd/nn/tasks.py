@@ -16,7 +16,7 @@ import yaml
 
 from .. import ops
 from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
-                      PconvBottleneck, PconvBottleneck_n, RFBblock, SPPF, Tape, Upsample, lowlight_recovery)
+                      PconvBottleneck, PconvBottleneck_n, RFBblock, SPPF, Segment, Tape, Upsample, lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
 # reverse, adding the gradients of a multi-consumer output itself -- no autograd.Function per yaml node, no ATen `add` for the fan-outs.
@@ -27,7 +27,8 @@ CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 
 _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
-                 FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck)
+                 FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
+                 Segment=Segment)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -82,6 +83,12 @@ def _rule_c2f(row):                       # the row's repeat count becomes the n
     return [args[0], args[1], row.repeats, *args[2:]], c2, 1
 
 
+def _rule_segment(row):                   # tasks.py:897-900: append the input widths, scale the prototype count npr
+    args = [*row.args, list(row.ch_in)]
+    args[2] = _scaled_width(args[2], row)
+    return args, row.ch_in[0], row.repeats
+
+
 _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
@@ -93,6 +100,7 @@ _RULES = {
     MFRU: lambda r: (r.args, 256, r.repeats),                                                  # tasks.py:890-891
     Detect: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),
     AsffDetect: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),
+    Segment: _rule_segment,
 }
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
@@ -556,3 +564,39 @@ class DetectionModel(BaseModel):
     def init_criterion(self):
         from ..utils.loss import RcoveryDetectionLoss
         return RcoveryDetectionLoss(self)
+
+
+class SegmentationModel(DetectionModel):
+    """YOLOv8 segmentation model (reference tasks.py:348-356): a Segment head, criterion v8SegmentationLoss.  Training output
+    (maps, mc [B, nm, A], proto [B, nm, mh, mw]); eval output (cat([y, mc], 1), (maps, mc, proto))."""
+
+    def __init__(self, cfg="yolov8n-seg.yaml", ch=3, nc=None, verbose=False):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        if not isinstance(self.model[-1], Segment):
+            raise ValueError("SegmentationModel: the yaml's last layer is not a Segment head")
+
+    def _predict_once(self, x, profile=False, visualize=False):
+        out = super()._predict_once(x, profile, visualize)
+        if isinstance(out, list):              # the layer graph's own training output: maps..., mc [B, nm, 1, A], proto
+            return self.model[-1]._wrap(out)
+        return out
+
+    def init_criterion(self):
+        from ..utils.loss import v8SegmentationLoss
+        return v8SegmentationLoss(self)
+
+
+def guess_model_task(model):
+    """'segment' for a Segment head, 'detect' for Detect / AsffDetect (reference tasks.py:968-1030, from a yaml dict or a model).
+    The reference's yaml rule reads `m == 'detect' or "asffdetect"`, which is always true; the intended rule is used here."""
+    if isinstance(model, dict):
+        kind = str(model["head"][-1][-2]).lower()
+        if kind == "segment":
+            return "segment"
+        if kind in ("detect", "asffdetect"):
+            return "detect"
+        raise NotImplementedError(f"head '{model['head'][-1][-2]}' is outside the Dedark-YOLO hot path")
+    if isinstance(model, nn.Module):
+        last = model.model[-1] if hasattr(model, "model") else model
+        return "segment" if isinstance(last, Segment) else "detect"
+    raise TypeError(f"guess_model_task: expected a yaml dict or a model, got {type(model).__name__}")

@@ -880,3 +880,83 @@ def det_maps(maps, strides, nc):
         t = maps[3]
         m.map3, m.map_ld3, m.h3, m.w3, m.stride3 = t.data_ptr(), ld_of(t), t.shape[2], t.shape[3], float(strides[3])
     return m
+
+
+# ------------------------------------------------------------------------------------------------ ConvTranspose2d(k=2, s=2)
+class ConvTCtx:
+    __slots__ = ("x", "weight", "bias")
+
+
+def conv_transpose2x2_forward(tape, x, weight, bias=None):
+    """nn.ConvTranspose2d(c1, c2, 2, 2, 0) (the Proto's upsample, reference block.py:242-254) on the conv kernels.  The weight
+    [c1, c2, 2, 2] is the OIHW weight of a 2x2 / stride-2 / pad-0 conv that maps c2 -> c1, so the transposed conv's forward is that
+    conv's data gradient (dy_conv2d_dgrad: four one-tap parity classes writing strided destinations) and its bias is added by
+    dy_bias_add.  x: NHWC view [B, c1, H, W] -> NHWC [B, c2, 2H, 2W] with zero channel padding."""
+    dtype = x.dtype
+    B, c1, H, W = x.shape
+    if weight.shape[0] != c1 or tuple(weight.shape[2:]) != (2, 2):
+        raise RuntimeError(f"conv_transpose2x2: weight {tuple(weight.shape)} does not fit {c1} input channels")
+    c2 = weight.shape[1]
+    ve = vec_elems(dtype)
+    c1_pad, c2_pad = padded_channels(x), round_up(c2, ve)
+    wt = _pack(weight, c1_pad, c2_pad, True, dtype)
+    y = empty_nhwc(B, c2_pad, 2 * H, 2 * W, dtype, x.device)
+    d = _conv_desc(x, wt, y, B, H, W, c1_pad, 2 * H, 2 * W, c2_pad, 2, 2, 2, 0, 1, None, None, ACT_NONE, None, False, dtype)
+    d.dst_valid_channels = c2
+    _C._prof is not None and _C.set_meta(kind="convT_fwd", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
+                                         flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + 4 * B * H * W * c2) * x.element_size()))
+    call("dy_conv2d_dgrad", C.byref(d), stream())
+    if bias is not None:
+        call("dy_bias_add", ptr(y), ld_of(y), ptr(bias.detach()), B * 4 * H * W, c2, dt_id(dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        ctx = ConvTCtx()
+        ctx.x, ctx.weight, ctx.bias = x, weight, bias
+        tape.push(ctx)
+    return y if c2_pad == c2 else y[:, :c2]
+
+
+def conv_transpose2x2_backward(tape, dy, need_dx=True):
+    """Backward of conv_transpose2x2_forward (pops its context).  Weight gradient = the 2x2 / stride-2 conv's weight gradient with
+    x = dy and dz = the forward's input (dy_conv2d_wgrad writes [c1][c2][2][2], exactly ConvTranspose2d.weight.grad); bias gradient =
+    per-channel sum of dy (dy_bias_grad, fixed order); data gradient = that conv's forward of dy (dy_conv2d_fwd)."""
+    ctx = tape.pop()
+    x, weight, bias = ctx.x, ctx.weight, ctx.bias
+    dtype, dev, st = x.dtype, x.device, stream()
+    B, c1, H, W = x.shape
+    c2 = weight.shape[1]
+    c1_pad = padded_channels(x)
+    c2_pad = round_up(c2, vec_elems(dtype))
+    if tuple(dy.shape) != (B, c2, 2 * H, 2 * W) or dy.dtype != dtype:
+        raise RuntimeError("conv_transpose2x2_backward: gradient does not match the forward's output")
+    if padded_channels(dy) != c2_pad:
+        raise RuntimeError("conv_transpose2x2_backward: gradient view lacks zero padding")
+    did = dt_id(dtype)
+    pixels = B * 4 * H * W
+    if bias is not None and bias.requires_grad:
+        gd = _grad_dst(bias)
+        db = gd if gd is not None else torch.empty(c2, dtype=torch.float32, device=dev)
+        scratch = wgrad_scratch(dev, tag=st)
+        call("dy_bias_grad", ptr(dy), ld_of(dy), pixels, c2, did, ptr(scratch), scratch.numel(), ptr(db), st)
+        if gd is None:
+            _add_pgrad(tape, bias, db)
+    if weight.requires_grad:
+        gd = _grad_dst(weight)
+        gw = gd if gd is not None else torch.empty(weight.shape, dtype=torch.float32, device=dev)
+        scratch = wgrad_scratch(dev, tag=st)
+        _C._prof is not None and _C.set_meta(kind="convT_wgrad", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
+                                             flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
+        call("dy_conv2d_wgrad", ptr(dy), ld_of(dy), B, 2 * H, 2 * W, c2_pad, ptr(x), ld_of(x), H, W, c1_pad, 2, 2, 2, 0, 1, c1, c2,
+             ptr(scratch), scratch.numel(), ptr(gw), did, st)
+        if gd is None:
+            _add_pgrad(tape, weight, gw)
+    if not need_dx:
+        return None
+    wp = _pack(weight, c1_pad, c2_pad, False, dtype)
+    dx = empty_nhwc(B, c1_pad, H, W, dtype, dev)
+    d = _conv_desc(dy, wp, dx, B, 2 * H, 2 * W, c2_pad, H, W, c1_pad, 2, 2, 2, 0, 1, None, None, ACT_NONE, None, False, dtype)
+    _C._prof is not None and _C.set_meta(kind="convT_dgrad", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
+                                         flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
+    call("dy_conv2d_fwd", C.byref(d), st)
+    emu_round(dx)
+    return dx if c1_pad == c1 else dx[:, :c1]

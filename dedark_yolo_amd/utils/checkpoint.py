@@ -204,7 +204,8 @@ def intersect_dicts(da, db, exclude=()):
 # GLOBAL opcode.  torch.nn leaves (Conv2d, BatchNorm2d, SiLU, Sequential, ...) are real torch modules.  The layout is checked on the
 # CPU against tests/golden/g12_ref_skeleton.json (what the reference itself pickles) and, in the build container, by loading the
 # file with the reference (tests/golden/make_ckpt_interop.py).
-_REF_HOME = {"DetectionModel": "ultralytics.nn.tasks"}
+_REF_HOME = {"DetectionModel": "ultralytics.nn.tasks", "SegmentationModel": "ultralytics.nn.tasks", "Proto": "ultralytics.nn.modules.block",
+             "Segment": "ultralytics.nn.modules.head"}
 _REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
@@ -235,7 +236,7 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "Detect": ("nc", "nl", "reg_max", "no", "stride"), "AsffDetect": ("nc", "nl", "reg_max", "no", "stride"),
               "lowlight_recovery": (), "ExtractParameters2": ("output_dim", "channels"), "ConvBlock": (),
               "PConv": ("dim_conv3", "dim_untouched"), "FasterC2f_N": ("c",), "FasterC2f": ("c",), "PconvBottleneck_n": ("add",),
-              "PconvBottleneck": ("add",)}
+              "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr")}
 
 _STANDINS = {}
 
@@ -404,7 +405,9 @@ class _RefWriter:
             kids["advavg"] = self.torch_leaf(nn.AdaptiveAvgPool2d(1), "")
         elif name == "PConv":                             # the constructor binds the split_cat forward per instance (conv.py:169-172)
             state["forward"] = _RefMethod(obj, "forward_split_cat")
-        elif name in ("Detect", "AsffDetect"):
+        elif name in ("Detect", "AsffDetect", "Segment"):
+            if name == "Segment":                         # self.detect = Detect.forward (head.py:186): getattr(Detect, 'forward')
+                state["detect"] = _RefMethod(_standin_type("ultralytics.nn.modules.head", "Detect"), "forward")
             state["inplace"] = True
             state["anchors"] = torch.empty(0, dtype=torch.float16)       # BaseModel._apply moves stride / anchors / strides
             state["strides"] = torch.empty(0, dtype=torch.float16)       # (tasks.py:203-220); rebuilt at the first eval forward
@@ -429,7 +432,8 @@ class _RefWriter:
         return self.filters
 
     def model(self, model, args):
-        obj = _standin_type("ultralytics.nn.tasks", "DetectionModel")()
+        cls = "SegmentationModel" if type(model).__name__ == "SegmentationModel" else "DetectionModel"
+        obj = _standin_type("ultralytics.nn.tasks", cls)()
         state = _nn_base_state(self.training)
         layers = list(model.model)
         save = sorted(x % m.i for m in layers for x in ([m.f] if isinstance(m.f, int) else m.f) if x != -1)      # tasks.py:913

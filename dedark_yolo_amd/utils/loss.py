@@ -10,7 +10,7 @@ import weakref
 
 import torch
 
-from .. import ops
+from .. import _C, ops
 from .._C import call
 from ..ops import ld_of, ptr, stream
 
@@ -218,6 +218,119 @@ class RcoveryDetectionLoss(v8DetectionLoss):
     def __init__(self, model):
         super().__init__(model)
         self.recovery_weight = self.hyp.lrl
+
+
+def _gt_masks(batch, B, dev):
+    """batch['masks'] on the device as uint8 or int32 ([B, h, w] index maps or [N, h, w] planes, the reference's collate)."""
+    m = batch.get("masks")
+    if m is None:
+        raise ValueError("segment loss: the batch has no 'masks' (not a segment dataset?)")
+    if m.dtype not in (torch.uint8, torch.int32):
+        m = m.to(torch.int32) if (m.dtype != torch.bool and m.numel() and float(m.max()) > 255) else m.to(torch.uint8)
+    return m.to(dev, non_blocking=True).contiguous()
+
+
+class _SegLossFn(torch.autograd.Function):
+    """(loss, items[box, seg, cls, dfl]) = f(maps..., mc [B, nm, A], proto [B, nm, mh, mw]); backward: one dy_loss_bwd for the maps,
+    dy_seg_loss_bwd for mc and proto."""
+
+    @staticmethod
+    def forward(ctx, crit, batch, n_maps, *ts):
+        dt = ops.get_compute_dtype()
+        maps = [ops.as_nhwc(m) for m in ts[:n_maps]]
+        mc, proto = ts[n_maps], ops.as_nhwc(ts[n_maps + 1])
+        B, dev, st = maps[0].shape[0], maps[0].device, stream()
+        A = mc.shape[2]
+        mcr = mc.transpose(1, 2)                                         # [B, A, nm] rows
+        if (mcr.dtype != dt or mcr.stride(2) != 1 or mcr.stride(1) != mcr.shape[2] or mcr.stride(0) != A * mcr.shape[2]
+                or mcr.data_ptr() % 16):
+            mcr = mcr.to(dt).contiguous()
+        strides = crit.strides_as_floats()[:n_maps]
+        bi = batch["batch_idx"]
+        a = assign(maps, strides, crit.nc, bi, batch["cls"], batch["bboxes"], batch.get("n_max"), frozen=crit.frozen_assignment)
+        dm = ops.det_maps(maps, strides, crit.nc)
+        acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
+             ptr(acc), st)
+        det = torch.empty(4, dtype=torch.float32, device=dev)
+        call("dy_loss_finish", ptr(acc), None, float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), 0.0, B, ptr(det[0:1]),
+             ptr(det[1:4]), st)
+        masks = _gt_masks(batch, B, dev)
+        n_max = max(a.n_max, 1)
+        rows = None
+        if not crit.overlap:
+            n_t = int(bi.numel())
+            bif = bi.to(dev, torch.float32).contiguous().view(-1)
+            rows = torch.empty((B, n_max), dtype=torch.int32, device=dev)
+            call("dy_seg_gt_rows", ptr(bif) if n_t else None, n_t, B, n_max, ptr(rows), st)
+            if masks.dim() != 3 or masks.shape[0] != n_t:
+                raise ValueError(f"segment loss: overlap_mask=False needs masks [N={n_t}, h, w], got {tuple(masks.shape)}")
+        elif masks.dim() != 3 or masks.shape[0] != B:
+            raise ValueError(f"segment loss: overlap_mask=True needs masks [B={B}, h, w], got {tuple(masks.shape)}")
+        pos = torch.empty((B, A), dtype=torch.int32, device=dev)
+        npos = torch.empty(B, dtype=torch.int32, device=dev)
+        call("dy_seg_positives", ptr(a.fg_mask), B, A, ptr(pos), ptr(npos), st)
+        d = _C.SegDesc()
+        d.mc, d.mc_ld, d.proto, d.proto_ld = mcr.data_ptr(), mcr.stride(1), proto.data_ptr(), ld_of(proto)
+        d.B, d.A, d.nm, d.mh, d.mw = B, A, mc.shape[1], proto.shape[2], proto.shape[3]
+        d.target_gt_idx, d.fg_mask, d.target_box = ptr(a.target_gt_idx), ptr(a.fg_mask), ptr(a.target_box)
+        if masks.numel() == 0:          # no labels at all ([0, h, w] per-instance stack): no positive reads a mask, the kernels need a pointer
+            masks = torch.zeros((1, max(masks.shape[1], 1), max(masks.shape[2], 1)), dtype=masks.dtype, device=dev)
+        d.masks, d.mask_dtype, d.mask_h, d.mask_w = masks.data_ptr(), int(masks.dtype == torch.int32), masks.shape[1], masks.shape[2]
+        d.overlap, d.gt_rows, d.n_max = int(bool(crit.overlap)), ptr(rows), n_max
+        d.img_h, d.img_w = maps[0].shape[2] * strides[0], maps[0].shape[3] * strides[0]
+        d.pos, d.npos, d.dtype = pos.data_ptr(), npos.data_ptr(), ops.dt_id(mcr.dtype)
+        lossp = torch.empty(B * A + B, dtype=torch.float32, device=dev)
+        out = torch.empty(5, dtype=torch.float32, device=dev)
+        call("dy_seg_loss_fwd", C.byref(d), float(crit.hyp.box), ptr(lossp), ptr(det), ptr(out), st)
+        ctx.crit, ctx.maps, ctx.assign, ctx.acc, ctx.strides = crit, maps, a, acc, strides
+        ctx.desc, ctx.keep = d, (mcr, proto, masks, rows, pos, npos)
+        ctx.mc_meta = (mc.shape, mc.dtype)
+        crit.last_assignment = a
+        loss, items = out[0], out[1:5]
+        ctx.mark_non_differentiable(items)
+        return loss, items
+
+    @staticmethod
+    def backward(ctx, gloss, _gitems):
+        crit, maps, a = ctx.crit, ctx.maps, ctx.assign
+        dev, dt, st = maps[0].device, maps[0].dtype, stream()
+        ve = ops.vec_elems(dt)
+        dm = ops.det_maps(maps, ctx.strides, crit.nc)
+        width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
+        dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
+        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
+        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
+        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
+             ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), st)
+        mcr, proto = ctx.keep[0], ctx.keep[1]
+        B, A, nm = mcr.shape
+        dmc = torch.zeros((B, A, nm), dtype=mcr.dtype, device=dev)      # rows of anchors without a positive stay zero
+        dp = ops.empty_nhwc(B, nm, proto.shape[2], proto.shape[3], proto.dtype, dev)
+        call("dy_seg_loss_bwd", C.byref(ctx.desc), ptr(g), float(crit.hyp.box), ptr(dmc), nm, ptr(dp), ld_of(dp), st)
+        ops.emu_round(*dbufs, dmc, dp)
+        no = 4 * REG_MAX + crit.nc
+        shape, mdt = ctx.mc_meta
+        dmc_out = dmc.transpose(1, 2) if mdt == dmc.dtype else dmc.transpose(1, 2).to(mdt)
+        ctx.keep = None
+        return (None, None, None, *[d[:, :no] for d in dbufs], dmc_out, dp)
+
+
+class v8SegmentationLoss(v8DetectionLoss):
+    """reference loss.py:196-288: the detection terms (dy_loss_fwd / dy_loss_bwd on the HIP assignment) plus the mask term on
+    csrc/seg.hip.  Returns (loss.sum() * B, items [box, seg, cls, dfl]); `model.args` carries .box/.cls/.dfl and .overlap_mask
+    (True by default, cfg/default.yaml)."""
+
+    def __init__(self, model):
+        super().__init__(model)
+        self.nm = model.model[-1].nm
+        self.overlap = bool(getattr(model.args, "overlap_mask", True))
+
+    def __call__(self, preds, batch):
+        feats, mc, proto = preds if len(preds) == 3 else preds[1]
+        loss, items = _SegLossFn.apply(self, batch, len(feats), *feats, mc, proto)
+        return loss, items
 
 
 class TaskAlignedAssigner:

@@ -211,3 +211,43 @@ class DetMetrics:
     @property
     def results_dict(self):
         return dict(zip(self.keys + ["fitness"], self.box.mean_results() + [self.fitness]))
+
+
+class SegmentMetrics:
+    """Box and mask tables of the segment validator (reference SegmentMetrics, metrics.py:804-900): `.process(tp_b, tp_m, conf,
+    pred_cls, target_cls)`, keys `metrics/...(B)` then `metrics/...(M)`, fitness = box fitness + mask fitness."""
+    keys = DetMetrics.keys + ["metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP50-95(M)"]
+
+    def __init__(self, save_dir=None, plot=False, on_plot=None, names=()):
+        self.save_dir, self.plot, self.on_plot, self.names = save_dir, plot, on_plot, names
+        self.box = BoxSummary()
+        self.seg = BoxSummary()
+        self.speed = dict(preprocess=0.0, inference=0.0, loss=0.0, postprocess=0.0)
+
+    def process(self, tp_b, tp_m, conf, pred_cls, target_cls):
+        self.seg.nc = len(self.names)
+        self.seg.update(ap_per_class(tp_m, conf, pred_cls, target_cls, names=self.names)[2:])
+        self.box.nc = len(self.names)
+        self.box.update(ap_per_class(tp_b, conf, pred_cls, target_cls, names=self.names)[2:])
+
+    def mean_results(self):
+        return self.box.mean_results() + self.seg.mean_results()
+
+    def class_result(self, i):
+        return self.box.class_result(i) + self.seg.class_result(i)
+
+    @property
+    def maps(self):
+        return self.box.maps + self.seg.maps
+
+    @property
+    def fitness(self):
+        return self.seg.fitness() + self.box.fitness()
+
+    @property
+    def ap_class_index(self):
+        return self.box.ap_class_index
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))

@@ -106,8 +106,97 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
         prediction = prediction[0]
     if classes is not None or (labels is not None and len(labels)):
         raise NotImplementedError("class filtering / hybrid autolabelling are outside the Dedark-YOLO hot path")
-    if nc not in (0, prediction.shape[1] - 4):
-        raise NotImplementedError("mask coefficients (segment task) are outside the Dedark-YOLO hot path")
-    out, cnt = nms_batched(prediction, conf_thres, iou_thres, multi_label, agnostic, max_det, max_nms, max_wh)
+    nc = nc or (prediction.shape[1] - 4)
+    nm = prediction.shape[1] - nc - 4
+    if nm < 0:
+        raise ValueError(f"non_max_suppression: nc={nc} does not fit {prediction.shape[1]} rows")
+    if nm == 0:
+        out, cnt = nms_batched(prediction, conf_thres, iou_thres, multi_label, agnostic, max_det, max_nms, max_wh)
+        cnt = cnt.tolist()
+        return [out[i, :cnt[i]] for i in range(len(cnt))]
+    # mask coefficients (ops.py:200,234-241): the kernels run on the box / class rows; each kept row's coefficients are gathered by
+    # its anchor (keep // nc) and appended -> [n, 6 + nm]
+    out, cnt, keep = nms_batched(prediction[:, :4 + nc], conf_thres, iou_thres, multi_label, agnostic, max_det, max_nms, max_wh,
+                                 return_indices=True)
+    B = prediction.shape[0]
+    anchor = (keep.clamp(min=0) // nc)                                          # [B, max_det]
+    coef = torch.gather(prediction[:, 4 + nc:], 2, anchor.unsqueeze(1).expand(B, nm, anchor.shape[1]))     # [B, nm, max_det]
+    full = torch.cat((out, coef.transpose(1, 2).to(out.dtype)), 2)
     cnt = cnt.tolist()
-    return [out[i, :cnt[i]] for i in range(len(cnt))]
+    return [full[i, :cnt[i]] for i in range(len(cnt))]
+
+
+def crop_mask(masks, boxes):
+    """Zero masks [n, h, w] outside their xyxy boxes [n, 4] (reference ops.py:553-569: columns x1 <= r < x2, rows y1 <= c < y2); f32
+    device tensors, returns a new tensor (dy_seg_crop_mask)."""
+    if not masks.is_cuda:
+        raise RuntimeError("crop_mask needs device tensors (there is no CPU path)")
+    n, h, w = masks.shape
+    out = masks.float().contiguous().clone()
+    bx = boxes.float().contiguous()
+    call("dy_seg_crop_mask", ptr(out), ptr(bx), n, h, w, stream())
+    return out
+
+
+def process_masks_batched(protos, dets, shape):
+    """process_mask for every image of a batch in one launch.  protos [B, nm, mh, mw] NHWC (any compute dtype), dets: one
+    [n_i, 6+nm] tensor per image (non_max_suppression) -> one uint8 [n_i, mh, mw] tensor per image."""
+    from .. import ops as kops
+    B, nm, mh, mw = protos.shape
+    ih, iw = shape
+    p = kops.as_nhwc(protos, protos.dtype)
+    dev = p.device
+    ns = [int(d.shape[0]) for d in dets]
+    n = sum(ns)
+    out = torch.empty((n, mh, mw), dtype=torch.uint8, device=dev)
+    if n:
+        det = torch.cat([d.float() for d in dets], 0).contiguous()
+        img = torch.cat([torch.full((k,), i, dtype=torch.int32, device=dev) for i, k in enumerate(ns)])
+        call("dy_seg_mask_decode", ptr(p), kops.ld_of(p), nm, mh, mw, ptr(det), det.shape[1], ptr(img), n, float(mw / iw), float(mh / ih),
+             kops.dt_id(p.dtype), ptr(out), stream())
+    return list(out.split(ns, 0))
+
+
+def process_mask(protos, masks_in, bboxes, shape, upsample=False):
+    """Reference signature (ops.py:593-623): protos [nm, mh, mw], masks_in [n, nm], bboxes [n, 4] xyxy at the input size `shape`
+    -> [n, mh, mw] f32 of 0 / 1 (sigmoid(c . P) > 0.5 inside the box scaled to the proto grid).  upsample=True (the bilinear
+    resize to the input size) is not implemented."""
+    if upsample:
+        raise NotImplementedError("process_mask(upsample=True): the bilinear upsampling path is not implemented")
+    if not protos.is_cuda:
+        raise RuntimeError("process_mask needs device tensors (there is no CPU path)")
+    n = masks_in.shape[0]
+    det = torch.zeros((n, 6 + masks_in.shape[1]), dtype=torch.float32, device=protos.device)
+    det[:, :4] = bboxes.float()
+    det[:, 6:] = masks_in.float()
+    p = protos.float().unsqueeze(0).contiguous(memory_format=torch.channels_last)
+    return process_masks_batched(p, [det], shape)[0].float()
+
+
+def mask_iou_binary(gt, pred, overlap, m):
+    """IoU [m, n] of uint8 pred masks [n, h, w] against the gt: overlap -> index map [h, w] (label k == k + 1, uint8 / int32),
+    else uint8 planes [m, h, w] (dy_seg_mask_iou: integer intersection counts, f32 ratio)."""
+    n = pred.shape[0]
+    dev = pred.device
+    iou = torch.zeros((m, n), dtype=torch.float32, device=dev)
+    if n == 0 or m == 0:
+        return iou
+    hw = pred.shape[1] * pred.shape[2]
+    g = gt.contiguous()
+    if g.dtype not in (torch.uint8, torch.int32):
+        g = g.to(torch.int32 if overlap else torch.uint8)
+    work = torch.empty(m * n + n, dtype=torch.int32, device=dev)
+    call("dy_seg_mask_iou", ptr(pred.contiguous()), n, ptr(g), int(g.dtype == torch.int32), int(bool(overlap)), m, hw, ptr(work),
+         ptr(iou), stream())
+    return iou
+
+
+def mask_iou(mask1, mask2, eps=1e-7):
+    """Reference signature (metrics.py:131-147) for BINARY masks: mask1 [N, n] (gt), mask2 [M, n] (predictions) -> IoU [N, M].
+    Integer counts on the device; eps is fixed at the reference's 1e-7."""
+    if eps != 1e-7:
+        raise NotImplementedError("mask_iou: eps is fixed at 1e-7")
+    if not mask2.is_cuda:
+        raise RuntimeError("mask_iou needs device tensors (there is no CPU path)")
+    N, M = mask1.shape[0], mask2.shape[0]
+    return mask_iou_binary(mask1.to(torch.uint8).view(N, 1, -1), mask2.to(torch.uint8).view(M, 1, -1), False, N)

@@ -427,6 +427,60 @@ int dy_aug_mosaic_warp(const dy_aug_sample* samples, int B, int out_h, int out_w
  * reference's unstable argsort go by pixel index, the rows DarkIcA leaves uninitialised use the per-channel formula. */
 int dy_dark_channel_prior(const float* img, int B, int H, int W, float* A, float* ica, void* stream);
 
+
+/* ---- segment task (csrc/seg.hip) ---------------------------------------------------------------------------------------------------
+ * Mask loss of v8SegmentationLoss (U/utils/loss.py:252-288, single_mask_loss; crop_mask U/utils/ops.py:553-569) on the assignment of
+ * dy_tal_assign, and the bias of the Proto's ConvTranspose2d(k=2, s=2) (U/nn/modules/block.py:242-254; its weight runs on
+ * dy_conv2d_dgrad / dy_conv2d_fwd / dy_conv2d_wgrad as a 2x2 stride-2 conv mapping c2 -> c1).  Fixed-order sums, no float atomics,
+ * no host synchronisation. */
+typedef struct dy_seg_desc {
+  const void* mc; int64_t mc_ld;          /* mask coefficients [B][A][mc_ld] (compute dtype, nm used) */
+  const void* proto; int64_t proto_ld;    /* proto map NHWC [B][mh][mw][proto_ld] (compute dtype) */
+  int32_t B, A, nm, mh, mw;               /* nm must be 32 */
+  const int32_t* target_gt_idx;           /* [B][A] from dy_tal_assign */
+  const uint8_t* fg_mask;                 /* [B][A] */
+  const float* target_box;                /* [B][A][4] xyxy pixels */
+  const void* masks;                      /* overlap: [B][mask_h][mask_w] index map, gt k of image b == k + 1 (batch-label order);
+                                           * else [N][mask_h][mask_w] per-instance planes, gt j of image b = j-th row with batch_idx == b */
+  int32_t mask_dtype;                     /* 0: uint8, 1: int32 */
+  int32_t mask_h, mask_w;                 /* != (mh, mw): sampled as F.interpolate(mode='nearest') (loss.py:254-255) */
+  int32_t overlap;
+  const int32_t* gt_rows; int32_t n_max;  /* overlap == 0: dy_seg_gt_rows table [B][n_max] */
+  float img_h, img_w;                     /* network input size (pixels of target_box) */
+  const int32_t* pos; const int32_t* npos;/* dy_seg_positives: pos [B][A] anchor indices in anchor order, npos [B] */
+  int32_t dtype;                          /* DY_F32 / DY_BF16 / DY_F16 of mc and proto */
+} dy_seg_desc;
+/* positives of every image in anchor order: pos[b][0..npos[b]) = anchors a with fg_mask[b][a] != 0 */
+int dy_seg_positives(const uint8_t* fg_mask, int B, int A, int32_t* pos, int32_t* npos, void* stream);
+/* rows[b][j] = index of the j-th target row with batch_idx == b (-1 past the image's count); batch_idx f32 [n_targets] */
+int dy_seg_gt_rows(const float* batch_idx, int n_targets, int B, int n_max, int32_t* rows, void* stream);
+/* Mask loss.  lossp: f32 workspace [B*A + B].  det_out = dy_loss_finish's (total, box, cls, dfl) -> out[5] = (total + seg * B, box,
+ * seg, cls, dfl) with seg = hyp_box / B * sum_b mean over b's positives of the cropped BCE / (mh*mw) / normalised box area. */
+int dy_seg_loss_fwd(const dy_seg_desc* d, float hyp_box, float* lossp, const float* det_out, float* out, void* stream);
+/* d total / d mc for every positive anchor (rows [B][A][dmc_ld]; rows of other anchors are not written) and d total / d proto
+ * (NHWC [B][mh][mw][dproto_ld], every pixel written), both in the compute dtype; grad_out = d loss / d total (f32, device). */
+int dy_seg_loss_bwd(const dy_seg_desc* d, const float* grad_out, float hyp_box, void* dmc, int64_t dmc_ld, void* dproto,
+                    int64_t dproto_ld, void* stream);
+/* x[p][c] += bias[c] for p < pixels, c < C (NHWC view, pixel stride ld): ConvTranspose2d's bias after the dgrad-route forward */
+int dy_bias_add(void* x, int64_t ld, const float* bias, int64_t pixels, int C, int dtype, void* stream);
+/* db[c] = sum over pixels of dy[p][c], c < C, in a fixed order.  scratch: DY_BIAS_GRAD_CHUNKS * C floats. */
+#define DY_BIAS_GRAD_CHUNKS 2048
+int dy_bias_grad(const void* dy, int64_t ld, int64_t pixels, int C, int dtype, float* scratch, int64_t scratch_elems, float* db,
+                 void* stream);
+
+/* Validation (process_mask with upsample=False, U/utils/ops.py:593-623): out[j][mh][mw] = sigmoid(c_j . P_b) > 0.5 inside box_j * (sx, sy)
+ * (crop_mask's x1 <= col < x2), in f32.  det rows (x1, y1, x2, y2, conf, cls, c_0 .. c_31) at stride det_ld, det_img[j] = image b;
+ * proto NHWC [B][mh][mw][proto_ld] in `dtype`. */
+int dy_seg_mask_decode(const void* proto, int64_t proto_ld, int nm, int mh, int mw, const float* det, int64_t det_ld,
+                       const int32_t* det_img, int n, float sx, float sy, int dtype, uint8_t* out, void* stream);
+/* crop_mask (U/utils/ops.py:553-569) in place: masks f32 [n][h][w] zeroed outside box_j = (x1, y1, x2, y2). */
+int dy_seg_crop_mask(float* masks, const float* boxes, int n, int h, int w, void* stream);
+/* mask_iou (U/utils/metrics.py:131-147) with integer counts: pred uint8 [n][hw]; gt = overlap ? one index map [hw] (uint8 / int32
+ * by gt_dtype 0 / 1, label k == k + 1) : uint8 planes [m][hw].  iou f32 [m][n] = inter / ((area_g + area_p) - inter + 1e-7);
+ * work: int32 [m*n + n]. */
+int dy_seg_mask_iou(const uint8_t* pred, int n, const void* gt, int gt_dtype, int overlap, int m, int64_t hw, int32_t* work,
+                    float* iou, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
