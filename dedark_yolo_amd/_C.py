@@ -59,6 +59,16 @@ class SegDesc(C.Structure):
 
 BIAS_GRAD_CHUNKS = 2048      # DY_BIAS_GRAD_CHUNKS
 
+POSE_MAX_LEVELS = 4          # DY_POSE_MAX_LEVELS
+
+
+class PoseDesc(C.Structure):
+    """dy_pose_desc (include/dedark_yolo.h)"""
+    _fields_ = [("kpt", vp * POSE_MAX_LEVELS), ("kpt_ld", i64 * POSE_MAX_LEVELS), ("h", i32 * POSE_MAX_LEVELS), ("w", i32 * POSE_MAX_LEVELS),
+                ("stride", f32 * POSE_MAX_LEVELS), ("n_levels", i32), ("B", i32), ("A", i32), ("K", i32), ("ndim", i32), ("dtype", i32),
+                ("target_gt_idx", vp), ("fg_mask", vp), ("target_box", vp), ("keypoints", vp), ("n_targets", i32), ("gt_rows", vp),
+                ("n_max", i32), ("img_h", f32), ("img_w", f32), ("sigma", vp), ("pos", vp), ("npos", vp)]
+
 
 _SIGS = {
     "dy_version": [],
@@ -126,6 +136,7 @@ _SIGS = {
     "dy_loss_finish": [vp, vp, f32, f32, f32, f32, i32, vp, vp, vp],
     "dy_loss_bwd": [C.POINTER(DetMaps), C.POINTER(vp), C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp],
     "dy_detect_decode": [C.POINTER(DetMaps), vp, vp],
+    "dy_detect_decode_rows": [C.POINTER(DetMaps), vp, i32, vp],
     "dy_nms_candidates": [vp, i32, i32, i32, f32, i32, vp, vp, i64, vp],
     "dy_nms_sort": [vp, vp, vp, i32, i64, vp, vp, vp],
     "dy_nms_greedy": [vp, vp, vp, i32, i32, i32, i64, C.c_double, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp],
@@ -148,6 +159,10 @@ _SIGS = {
     "dy_seg_mask_decode": [vp, i64, i32, i32, i32, vp, i64, vp, i32, f32, f32, i32, vp, vp],
     "dy_seg_crop_mask": [vp, vp, i32, i32, i32, vp],
     "dy_seg_mask_iou": [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp],
+    "dy_pose_loss_fwd": [C.POINTER(PoseDesc), f32, f32, vp, vp, vp, vp],
+    "dy_pose_loss_bwd": [C.POINTER(PoseDesc), vp, vp, f32, f32, C.POINTER(vp), i64, vp],
+    "dy_pose_kpt_decode": [C.POINTER(PoseDesc), i32, vp, vp],
+    "dy_kpt_oks": [vp, i32, vp, i32, i32, vp, vp, i32, f32, vp, vp],
 }
 
 _lib = None

@@ -582,8 +582,9 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Maps m, char* d0, char* d
 }
 
 // ---- Detect eval decode ----------------------------------------------------------------------------------------------------------
+// y [B][rows][A] f32 with rows >= 4 + nc (the Pose head's buffer also holds its keypoint rows after the class rows)
 template <typename T>
-__global__ void detect_decode_kernel(Maps m, float* __restrict__ y) {
+__global__ void detect_decode_kernel(Maps m, float* __restrict__ y, int rows) {
   long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (i >= (long)m.B * m.A) return;
   int b = (int)(i / m.A), a = (int)(i - (long)b * m.A);
@@ -600,7 +601,7 @@ __global__ void detect_decode_kernel(Maps m, float* __restrict__ y) {
   }
   const float st = m.stride[lvl];
   float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
-  float* o = y + (long)b * (4 + m.nc) * m.A + a;
+  float* o = y + (long)b * rows * m.A + a;
   o[0] = (x1 + x2) / 2 * st;
   o[(long)m.A] = (y1 + y2) / 2 * st;
   o[2L * m.A] = (x2 - x1) * st;
@@ -902,16 +903,20 @@ extern "C" int dy_dfl_loss(const float* pred_dist, const float* target, int64_t 
   return 0;
 }
 
-extern "C" int dy_detect_decode(const dy_det_maps* d, float* y, void* stream) {
+extern "C" int dy_detect_decode_rows(const dy_det_maps* d, float* y, int rows, void* stream) {
   Maps m;
   if (int e = make_maps(d, m, "dy_detect_decode")) return e;
-  DY_CHECK(y, "dy_detect_decode: null");
+  DY_CHECK(y && rows >= 4 + m.nc, "dy_detect_decode: null output or rows < 4 + nc");
   int blocks = dy_cdiv((long)m.B * m.A, 256);
-  if (d->dtype == DY_F32) detect_decode_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y);
-  else if ((d->dtype) == DY_F16) detect_decode_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y);
-  else detect_decode_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y);
+  if (d->dtype == DY_F32) detect_decode_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
+  else if ((d->dtype) == DY_F16) detect_decode_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
+  else detect_decode_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
   DY_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int dy_detect_decode(const dy_det_maps* d, float* y, void* stream) {
+  return dy_detect_decode_rows(d, y, d ? 4 + d->nc : 0, stream);
 }
 
 extern "C" int dy_preprocess_batch(const uint8_t* img, float* img_out, float* clean_out, float dark_param, int lowlight,

@@ -1,5 +1,5 @@
 """`YOLO` facade with the reference call surface (ultralytics/engine/model.py:29-416): YOLO(model), .train(**kw), .val(**kw),
-.load(), .fuse(); detect task only (the other tasks are outside the hot path)."""
+.load(), .fuse(); the detect, segment and pose tasks (the others are outside the hot path)."""
 from pathlib import Path
 
 import torch
@@ -9,14 +9,24 @@ from .trainer import DetectionTrainer, get_cfg
 
 
 def _model_class(task):
-    from ..nn.tasks import SegmentationModel
-    return SegmentationModel if task == "segment" else DetectionModel
+    from ..nn.tasks import PoseModel, SegmentationModel
+    return SegmentationModel if task == "segment" else PoseModel if task == "pose" else DetectionModel
+
+
+def _resolve_task(task, d):
+    """The yaml's own task unless one is given; 'pose' and a Pose head go together only (an explicit task that contradicts
+    them raises, as one outside the hot path does)."""
+    from ..nn.tasks import guess_model_task
+    head = guess_model_task(d)
+    if task is not None and (task == "pose") != (head == "pose"):
+        raise NotImplementedError(f"task '{task}' does not match the model's {head} head")
+    return task or head
 
 
 class YOLO:
     def __init__(self, model="yolov8l.yaml", task=None):
-        if task not in (None, "detect", "segment"):
-            raise NotImplementedError("only the detect and segment tasks are on the Dedark-YOLO hot path")
+        if task not in (None, "detect", "segment", "pose"):
+            raise NotImplementedError("only the detect, segment and pose tasks are on the Dedark-YOLO hot path")
         self.task = task
         self.trainer = None
         self.overrides = {}
@@ -29,10 +39,10 @@ class YOLO:
             raise FileNotFoundError(f"'{model}': expected a model .yaml or a state_dict checkpoint .pt")
 
     def _new(self, cfg):
-        from ..nn.tasks import guess_model_task, yaml_model_load
+        from ..nn.tasks import yaml_model_load
         self.cfg = cfg
         d = yaml_model_load(cfg)
-        self.task = self.task or guess_model_task(d)
+        self.task = _resolve_task(self.task, d)
         self.model = _model_class(self.task)(d)
         self.overrides["model"] = cfg
         self.overrides["task"] = self.task
@@ -45,9 +55,9 @@ class YOLO:
         cfg = ck.yaml
         if cfg is None:
             raise RuntimeError(f"{weights}: the checkpoint carries no model yaml")
-        from ..nn.tasks import guess_model_task, yaml_model_load
+        from ..nn.tasks import yaml_model_load
         d = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
-        self.task = self.task or guess_model_task(d)
+        self.task = _resolve_task(self.task, d)
         self.model = _model_class(self.task)(d, nc=ck.nc)
         self.overrides["task"] = self.task
         n = self.model.load(ck.state_dict)
@@ -82,10 +92,10 @@ class YOLO:
         return self.trainer.train(loader)
 
     def val(self, loader=None, **kwargs):
-        from .validator import DetectionValidator, SegmentationValidator
+        from .validator import DetectionValidator, PoseValidator, SegmentationValidator
         ov = dict(self.overrides)
         ov.update(kwargs)
-        v = (SegmentationValidator if self.task == "segment" else DetectionValidator)(get_cfg(ov))
+        v = {"segment": SegmentationValidator, "pose": PoseValidator}.get(self.task, DetectionValidator)(get_cfg(ov))
         return v(self.model, loader)
 
     @torch.no_grad()
@@ -111,14 +121,19 @@ class YOLO:
         else:
             img = source.to(dev).float()
         preds = self.model(img)
-        dets = uops.non_max_suppression(preds, conf, iou, agnostic=agnostic_nms, max_det=max_det)
+        pose = self.task == "pose"
+        nc = self.model.model[-1].nc if pose else 0
+        dets = uops.non_max_suppression(preds, conf, iou, agnostic=agnostic_nms, max_det=max_det, nc=nc)
         H, W = img.shape[2:]
         out = []
         for i, d in enumerate(dets):
             shape = tuple(orig_shapes[i]) if orig_shapes is not None else (H, W)
             d = d.clone()
             uops.scale_boxes((H, W), d[:, :4], shape)          # also clips to the image, like predict.py:27
-            out.append(Results(shape, d, names=self.model.names))
+            kpts = None
+            if pose:                                          # models/yolo/pose/predict.py:29-30
+                kpts = uops.scale_coords((H, W), d[:, 6:].reshape(len(d), *self.model.model[-1].kpt_shape), shape)
+            out.append(Results(shape, d[:, :6], names=self.model.names, keypoints=kpts))
         self.model.train(was_training)
         return out
 

@@ -560,9 +560,10 @@ class DetectionTrainer:
     def validate(self, val_loader):
         """trainer.validate() (engine/trainer.py:471-480): the validator on the EMA weights, forced to fp32 as the fork does
         (engine/validator.py:105-107 `self.args.half = False`).  Returns (metrics dict, fitness)."""
-        from .validator import DetectionValidator, SegmentationValidator
-        from ..nn.modules import Segment
-        V = SegmentationValidator if isinstance(self.model.model[-1], Segment) else DetectionValidator
+        from .validator import DetectionValidator, PoseValidator, SegmentationValidator
+        from ..nn.modules import Pose, Segment
+        head = self.model.model[-1]
+        V = SegmentationValidator if isinstance(head, Segment) else PoseValidator if isinstance(head, Pose) else DetectionValidator
         dt = ops.get_compute_dtype()
         try:
             with self.ema_weights() as model:

@@ -12,7 +12,7 @@ from .. import ops as kops
 from .._C import call
 from ..ops import ptr, stream
 from ..utils import ops
-from ..utils.metrics import DetMetrics, SegmentMetrics, box_iou
+from ..utils.metrics import OKS_SIGMA, DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou
 
 
 def match_predictions(detections, labels, iouv):
@@ -209,3 +209,69 @@ class SegmentationValidator(DetectionValidator):
                 correct_b = match_predictions(predn, torch.cat((cls, tbox), 1), self.iouv)
                 correct_m = match_from_iou(iou_m, cls[:, 0], predn[:, 5], self.iouv)
             self.stats.append((correct_b, correct_m, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+
+
+class PoseValidator(DetectionValidator):
+    """Pose validator (reference models/yolo/pose/val.py): NMS with multi_label and the K * ndim keypoint columns appended,
+    boxes (scale_boxes) and keypoints (scale_coords) to ori_shape / ratio_pad, OKS against the gt keypoints in native space with
+    area = gt box w * h * 0.53 (kpt_iou on dy_kpt_oks), box and pose `correct` matrices by the same matching rule, PoseMetrics.
+    sigma = OKS_SIGMA for kpt_shape [17, 3], else ones(K) / K."""
+
+    def __init__(self, args=None, dataloader=None):
+        super().__init__(args, dataloader)
+        self.args.task = "pose"
+        self.metrics = PoseMetrics()
+
+    def init_metrics(self, model):
+        super().init_metrics(model)
+        self.kpt_shape = list(model.model[-1].kpt_shape)
+        nkpt = int(self.kpt_shape[0])
+        self.sigma = OKS_SIGMA if [int(v) for v in self.kpt_shape] == [17, 3] else np.ones(nkpt) / nkpt
+
+    def postprocess(self, preds):
+        a = self.args
+        return ops.non_max_suppression(preds, self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
+                                       max_det=a.max_det, nc=self.nc)
+
+    def update_metrics(self, preds, batch):
+        """val.py:62-109 on host copies (the OKS matrix on the device)."""
+        bi = batch["batch_idx"].cpu()
+        cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
+        if "keypoints" not in batch:
+            raise ValueError("pose validation: the batch has no 'keypoints'")
+        kpt_all = batch["keypoints"].cpu().float()
+        height, width = batch["img"].shape[2:]
+        for si, pred in enumerate(preds):
+            pred = pred.cpu()
+            idx = bi == si
+            cls, bbox, kpts = cls_all[idx], box_all[idx], kpt_all[idx]
+            nl, npr = cls.shape[0], pred.shape[0]
+            nk = kpts.shape[1] if kpts.dim() == 3 else int(self.kpt_shape[0])
+            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
+            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
+            correct_b = torch.zeros(npr, self.niou, dtype=torch.bool)
+            correct_p = torch.zeros(npr, self.niou, dtype=torch.bool)
+            self.seen += 1
+            if npr == 0:
+                if nl:
+                    self.stats.append((correct_b, correct_p, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
+                continue
+            if getattr(self.args, "single_cls", False):
+                pred[:, 5] = 0
+            predn = pred.clone()
+            ops.scale_boxes((height, width), predn[:, :4], shape, ratio_pad=ratio_pad)
+            pred_kpts = predn[:, 6:].view(npr, nk, -1)
+            ops.scale_coords((height, width), pred_kpts, shape, ratio_pad=ratio_pad)
+            if nl:
+                tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
+                ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
+                tkpts = kpts.clone()
+                tkpts[..., 0] *= width
+                tkpts[..., 1] *= height
+                tkpts = ops.scale_coords((height, width), tkpts, shape, ratio_pad=ratio_pad)
+                labelsn = torch.cat((cls, tbox), 1)
+                correct_b = match_predictions(predn, labelsn, self.iouv)
+                area = ops.xyxy2xywh(labelsn[:, 1:])[:, 2:].prod(1) * 0.53
+                oks = kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma).cpu().numpy()
+                correct_p = match_from_iou(oks, cls[:, 0], predn[:, 5], self.iouv)
+            self.stats.append((correct_b, correct_p, pred[:, 4], pred[:, 5], cls.squeeze(-1)))

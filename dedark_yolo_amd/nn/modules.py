@@ -18,7 +18,7 @@ from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
 __all__ = ("Conv", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
-           "AsffDetect", "Proto", "Segment",
+           "AsffDetect", "Proto", "Segment", "Pose",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
 
@@ -1123,6 +1123,74 @@ class Segment(Detect):
                 ops._add_pgrad(tape, p, g)
         return dxs
 
+
+
+class Pose(Detect):
+    """YOLOv8 pose head (reference head.py:203-241): Detect plus per-level keypoint chains cv4[i] = Conv3x3, Conv3x3,
+    Conv2d(c4 -> nk, 1) with nk = K * ndim and c4 = max(ch[0] // 4, nk).  Train: (maps, kpt); eval: (y [B, 4+nc+nk, A] f32 with
+    the keypoint rows decoded, (maps, kpt)).
+
+    kpt is the list of the per-level cv4 outputs, NHWC [B, nk, h, w] with the pixel stride rounded up to the vector width
+    (pad lanes zero): the loss and decode kernels (csrc/pose.hip) read them in place, anchors numbered level by level, and the
+    loss writes each level's gradient map in the same layout -- no [B, nk, A] concatenation either way.  The cv4 chains run
+    inside the level chains that Detect._run_levels forks onto the branch streams."""
+
+    def __init__(self, nc=80, kpt_shape=(17, 3), ch=()):
+        super().__init__(nc, ch)
+        self.kpt_shape = kpt_shape
+        self.nk = kpt_shape[0] * kpt_shape[1]
+        self.detect = Detect.forward
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+
+    def _pose_level_fwd(self, tape, i, x):
+        a, b, c = self.cv4[i]
+        k = plain_conv_fwd(tape, c, b._fwd(tape, a._fwd(tape, x)))
+        return self._level_fwd(tape, i, x), k          # Detect's branches: their contexts sit on top of the tape
+
+    def _pose_level_bwd(self, tape, i, g, gk):
+        gk.record_stream(torch.cuda.current_stream(gk.device))   # may be a branch stream: as Detect._run_levels does for g
+        dx = self._level_bwd(tape, i, g)
+        gt = self.cv4[i][1]._bwd(tape, conv_backward(tape, gk))
+        return self.cv4[i][0]._bwd(tape, gt, dx_out=dx, accumulate=True)
+
+    def _fwd(self, tape, *xs):
+        subs = [Tape() if tape is not None else None for _ in xs]
+        outs = self._run_levels(self._pose_level_fwd, subs, list(xs))
+        if tape is not None:
+            tape.push(subs)
+        maps, kpts = [o[0] for o in outs], [o[1] for o in outs]
+        if self.training:
+            return [*maps, *kpts]
+        B, dev = maps[0].shape[0], maps[0].device
+        strides = self.strides_as_floats()
+        A = sum(t.shape[2] * t.shape[3] for t in maps)
+        rows = 4 + self.nc + self.nk
+        y = torch.empty((B, rows, A), dtype=torch.float32, device=dev)
+        m = ops.det_maps(maps, strides, self.nc)
+        call("dy_detect_decode_rows", C.byref(m), ptr(y), rows, stream())
+        d = ops.pose_desc(kpts, strides, self.kpt_shape)
+        call("dy_pose_kpt_decode", C.byref(d), self.nc, ptr(y), stream())
+        return (y, *maps, *kpts)
+
+    def _wrap(self, out):
+        n = self.nl
+        if self.training:
+            return list(out[:n]), list(out[n:2 * n])
+        return out[0], (list(out[1:1 + n]), list(out[1 + n:1 + 2 * n]))
+
+    def _bwd(self, tape, *gs, needs=None):
+        if not self.training:
+            raise RuntimeError("Pose: backward through the eval decode is not supported")
+        n = self.nl
+        subs = tape.pop()
+        gk = gs[n:2 * n]
+        dxs = self._run_levels(lambda t, i, g: self._pose_level_bwd(t, i, g, gk[i]), subs, list(gs[:n]))
+        for t in subs:
+            assert not t.stack, "Pose: unbalanced level tape"
+            for p, g in t.pgrads.items():
+                ops._add_pgrad(tape, p, g)
+        return dxs
 
 # ------------------------------------------------------------------------------------------------ low-light front-end
 class ConvBlock(nn.Module):

@@ -16,7 +16,8 @@ import yaml
 
 from .. import ops
 from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
-                      PconvBottleneck, PconvBottleneck_n, RFBblock, SPPF, Segment, Tape, Upsample, lowlight_recovery)
+                      PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SPPF, Segment, Tape, Upsample,
+                      lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
 # reverse, adding the gradients of a multi-consumer output itself -- no autograd.Function per yaml node, no ATen `add` for the fan-outs.
@@ -28,7 +29,7 @@ CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
-                 Segment=Segment)
+                 Segment=Segment, Pose=Pose)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -101,6 +102,7 @@ _RULES = {
     Detect: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),
     AsffDetect: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),
     Segment: _rule_segment,
+    Pose: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),                        # tasks.py:897-898
 }
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
@@ -320,7 +322,7 @@ def parse_model(d, ch, verbose=False):
             raise NotImplementedError(f"module '{kind}' is outside the Dedark-YOLO hot path (SURVEY.md 8)")
         row = _Row()
         row.index, row.src, row.kind, row.nc, row.width, row.max_ch = index, src, kind, nc, width, max_ch
-        row.args = [nc if a == "nc" else _literal(a, ast) for a in args]
+        row.args = [nc if a == "nc" else d.get("kpt_shape") if a == "kpt_shape" else _literal(a, ast) for a in args]
         row.repeats = max(round(repeats * depth), 1) if repeats > 1 else repeats
         rel = [src] if isinstance(src, int) else list(src)
         row.ch_in = [(widths[j] if widths else ch) if j == -1 else widths[j] for j in rel]
@@ -586,17 +588,43 @@ class SegmentationModel(DetectionModel):
         return v8SegmentationLoss(self)
 
 
+class PoseModel(DetectionModel):
+    """YOLOv8 pose model (reference tasks.py:366-386): a Pose head, criterion v8PoseLoss.  `data_kpt_shape` (the dataset's
+    kpt_shape) overrides the yaml's.  Training output (maps, kpt); eval output (y [B, 4+nc+nk, A], (maps, kpt)), kpt = the
+    per-level keypoint maps (Pose)."""
+
+    def __init__(self, cfg="yolov8n-pose.yaml", ch=3, nc=None, data_kpt_shape=(None, None), verbose=False):
+        if not isinstance(cfg, dict):
+            cfg = yaml_model_load(cfg)
+        if any(data_kpt_shape) and list(data_kpt_shape) != list(cfg["kpt_shape"]):
+            cfg["kpt_shape"] = data_kpt_shape
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        if not isinstance(self.model[-1], Pose):
+            raise ValueError("PoseModel: the yaml's last layer is not a Pose head")
+
+    def _predict_once(self, x, profile=False, visualize=False):
+        out = super()._predict_once(x, profile, visualize)
+        if isinstance(out, list):              # the layer graph's own training output: maps..., kpt maps...
+            return self.model[-1]._wrap(out)
+        return out
+
+    def init_criterion(self):
+        from ..utils.loss import v8PoseLoss
+        return v8PoseLoss(self)
+
+
 def guess_model_task(model):
-    """'segment' for a Segment head, 'detect' for Detect / AsffDetect (reference tasks.py:968-1030, from a yaml dict or a model).
-    The reference's yaml rule reads `m == 'detect' or "asffdetect"`, which is always true; the intended rule is used here."""
+    """'segment' for a Segment head, 'pose' for a Pose head, 'detect' for Detect / AsffDetect (reference tasks.py:968-1030, from a
+    yaml dict or a model).  Pose subclasses Detect, so it is checked first.  The reference's yaml rule reads
+    `m == 'detect' or "asffdetect"`, which is always true; the intended rule is used here."""
     if isinstance(model, dict):
         kind = str(model["head"][-1][-2]).lower()
-        if kind == "segment":
-            return "segment"
+        if kind in ("segment", "pose"):
+            return kind
         if kind in ("detect", "asffdetect"):
             return "detect"
         raise NotImplementedError(f"head '{model['head'][-1][-2]}' is outside the Dedark-YOLO hot path")
     if isinstance(model, nn.Module):
         last = model.model[-1] if hasattr(model, "model") else model
-        return "segment" if isinstance(last, Segment) else "detect"
+        return "segment" if isinstance(last, Segment) else "pose" if isinstance(last, Pose) else "detect"
     raise TypeError(f"guess_model_task: expected a yaml dict or a model, got {type(model).__name__}")

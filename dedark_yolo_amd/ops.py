@@ -882,6 +882,23 @@ def det_maps(maps, strides, nc):
     return m
 
 
+def pose_desc(kpts, strides, kpt_shape):
+    """dy_pose_desc of the Pose head's per-level keypoint maps (NHWC [B, K*ndim, h, w], anchors level by level); the loss fields
+    are left null for the caller to fill."""
+    if not 1 <= len(kpts) <= _C.POSE_MAX_LEVELS:
+        raise ValueError(f"pose_desc: {len(kpts)} levels; the pose kernels take 1-{_C.POSE_MAX_LEVELS}")
+    d = _C.PoseDesc()
+    d.n_levels, d.B, d.K, d.ndim = len(kpts), kpts[0].shape[0], int(kpt_shape[0]), int(kpt_shape[1])
+    d.dtype = dt_id(kpts[0].dtype)
+    A = 0
+    for i, t in enumerate(kpts):
+        if t.dtype != kpts[0].dtype or t.shape[1] != d.K * d.ndim:
+            raise ValueError(f"pose_desc: level {i} is {tuple(t.shape)} {t.dtype}, expected {d.K * d.ndim} channels")
+        d.kpt[i], d.kpt_ld[i], d.h[i], d.w[i], d.stride[i] = t.data_ptr(), ld_of(t), t.shape[2], t.shape[3], float(strides[i])
+        A += t.shape[2] * t.shape[3]
+    d.A = A
+    return d
+
 # ------------------------------------------------------------------------------------------------ ConvTranspose2d(k=2, s=2)
 class ConvTCtx:
     __slots__ = ("x", "weight", "bias")

@@ -205,7 +205,7 @@ def intersect_dicts(da, db, exclude=()):
 # CPU against tests/golden/g12_ref_skeleton.json (what the reference itself pickles) and, in the build container, by loading the
 # file with the reference (tests/golden/make_ckpt_interop.py).
 _REF_HOME = {"DetectionModel": "ultralytics.nn.tasks", "SegmentationModel": "ultralytics.nn.tasks", "Proto": "ultralytics.nn.modules.block",
-             "Segment": "ultralytics.nn.modules.head"}
+             "Segment": "ultralytics.nn.modules.head", "PoseModel": "ultralytics.nn.tasks", "Pose": "ultralytics.nn.modules.head"}
 _REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
@@ -236,7 +236,8 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "Detect": ("nc", "nl", "reg_max", "no", "stride"), "AsffDetect": ("nc", "nl", "reg_max", "no", "stride"),
               "lowlight_recovery": (), "ExtractParameters2": ("output_dim", "channels"), "ConvBlock": (),
               "PConv": ("dim_conv3", "dim_untouched"), "FasterC2f_N": ("c",), "FasterC2f": ("c",), "PconvBottleneck_n": ("add",),
-              "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr")}
+              "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr"),
+              "Pose": ("nc", "nl", "reg_max", "no", "stride", "kpt_shape", "nk")}
 
 _STANDINS = {}
 
@@ -405,8 +406,8 @@ class _RefWriter:
             kids["advavg"] = self.torch_leaf(nn.AdaptiveAvgPool2d(1), "")
         elif name == "PConv":                             # the constructor binds the split_cat forward per instance (conv.py:169-172)
             state["forward"] = _RefMethod(obj, "forward_split_cat")
-        elif name in ("Detect", "AsffDetect", "Segment"):
-            if name == "Segment":                         # self.detect = Detect.forward (head.py:186): getattr(Detect, 'forward')
+        elif name in ("Detect", "AsffDetect", "Segment", "Pose"):
+            if name in ("Segment", "Pose"):               # self.detect = Detect.forward (head.py:186, 211): getattr(Detect, 'forward')
                 state["detect"] = _RefMethod(_standin_type("ultralytics.nn.modules.head", "Detect"), "forward")
             state["inplace"] = True
             state["anchors"] = torch.empty(0, dtype=torch.float16)       # BaseModel._apply moves stride / anchors / strides
@@ -432,7 +433,7 @@ class _RefWriter:
         return self.filters
 
     def model(self, model, args):
-        cls = "SegmentationModel" if type(model).__name__ == "SegmentationModel" else "DetectionModel"
+        cls = type(model).__name__ if type(model).__name__ in ("SegmentationModel", "PoseModel") else "DetectionModel"
         obj = _standin_type("ultralytics.nn.tasks", cls)()
         state = _nn_base_state(self.training)
         layers = list(model.model)

@@ -333,6 +333,116 @@ class v8SegmentationLoss(v8DetectionLoss):
         return loss, items
 
 
+def _gt_keypoints(batch, K, dev):
+    """batch['keypoints'] [N, K, 3] (normalised x, y and visibility; the label reader appends the visibility column for ndim 2
+    as well, data/utils.py:122-128) as f32 on the device."""
+    kp = batch.get("keypoints")
+    if kp is None:
+        raise ValueError("pose loss: the batch has no 'keypoints' (not a pose dataset?)")
+    n = int(batch["batch_idx"].numel())
+    if kp.dim() != 3 or kp.shape[0] != n or kp.shape[1] != K or kp.shape[2] != 3:
+        raise ValueError(f"pose loss: batch['keypoints'] must be [N={n}, K={K}, 3] (normalised x, y, visibility) for the model's "
+                         f"kpt_shape, got {tuple(kp.shape)}")
+    return kp.to(dev, torch.float32, non_blocking=True).contiguous()
+
+
+class _PoseLossFn(torch.autograd.Function):
+    """(loss, items[box, pose, kobj, cls, dfl]) = f(maps..., kpt maps...); backward: one dy_loss_bwd for the Detect maps,
+    dy_pose_loss_bwd for the keypoint maps (every element of each level's gradient map written)."""
+
+    @staticmethod
+    def forward(ctx, crit, batch, n_maps, *ts):
+        maps = [ops.as_nhwc(m) for m in ts[:n_maps]]
+        kpts = [ops.as_nhwc(k, maps[0].dtype) for k in ts[n_maps:2 * n_maps]]
+        B, dev, st = maps[0].shape[0], maps[0].device, stream()
+        strides = crit.strides_as_floats()[:n_maps]
+        bi = batch["batch_idx"]
+        K = int(crit.kpt_shape[0])
+        kp = _gt_keypoints(batch, K, dev)
+        a = assign(maps, strides, crit.nc, bi, batch["cls"], batch["bboxes"], batch.get("n_max"), frozen=crit.frozen_assignment)
+        dm = ops.det_maps(maps, strides, crit.nc)
+        acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
+             ptr(acc), st)
+        det = torch.empty(4, dtype=torch.float32, device=dev)
+        call("dy_loss_finish", ptr(acc), None, float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), 0.0, B, ptr(det[0:1]),
+             ptr(det[1:4]), st)
+        n_t, n_max = int(bi.numel()), max(a.n_max, 1)
+        bif = bi.to(dev, torch.float32).contiguous().view(-1)
+        rows = torch.empty((B, n_max), dtype=torch.int32, device=dev)
+        call("dy_seg_gt_rows", ptr(bif) if n_t else None, n_t, B, n_max, ptr(rows), st)
+        A = a.fg_mask.shape[1]
+        pos = torch.empty((B, A), dtype=torch.int32, device=dev)
+        npos = torch.empty(B, dtype=torch.int32, device=dev)
+        call("dy_seg_positives", ptr(a.fg_mask), B, A, ptr(pos), ptr(npos), st)
+        d = ops.pose_desc(kpts, strides, crit.kpt_shape)
+        d.target_gt_idx, d.fg_mask, d.target_box = ptr(a.target_gt_idx), ptr(a.fg_mask), ptr(a.target_box)
+        d.keypoints, d.n_targets = (kp.data_ptr() if n_t else None), n_t
+        d.gt_rows, d.n_max = rows.data_ptr(), n_max
+        d.img_h, d.img_w = maps[0].shape[2] * strides[0], maps[0].shape[3] * strides[0]
+        sigma = crit.sigmas_on(dev)
+        d.sigma, d.pos, d.npos = sigma.data_ptr(), pos.data_ptr(), npos.data_ptr()
+        work = torch.empty(3 * B * A + 3 * B, dtype=torch.float32, device=dev)
+        out = torch.empty(6, dtype=torch.float32, device=dev)
+        call("dy_pose_loss_fwd", C.byref(d), float(crit.hyp.pose), float(crit.hyp.kobj), ptr(work), ptr(det), ptr(out), st)
+        ctx.crit, ctx.maps, ctx.assign, ctx.acc, ctx.strides = crit, maps, a, acc, strides
+        ctx.desc, ctx.keep = d, (kpts, kp, rows, pos, npos, sigma, work)
+        crit.last_assignment = a
+        loss, items = out[0], out[1:6]
+        ctx.mark_non_differentiable(items)
+        return loss, items
+
+    @staticmethod
+    def backward(ctx, gloss, _gitems):
+        crit, maps, a = ctx.crit, ctx.maps, ctx.assign
+        dev, dt, st = maps[0].device, maps[0].dtype, stream()
+        ve = ops.vec_elems(dt)
+        dm = ops.det_maps(maps, ctx.strides, crit.nc)
+        width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
+        dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
+        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
+        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
+        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
+             ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), st)
+        kpts, work = ctx.keep[0], ctx.keep[-1]
+        nk = kpts[0].shape[1]
+        nk_pad = ops.round_up(nk, ve)
+        dks = [ops.empty_nhwc(k.shape[0], nk_pad, k.shape[2], k.shape[3], dt, dev) for k in kpts]
+        arr_k = (C.c_void_p * len(dks))(*[k.data_ptr() for k in dks])
+        call("dy_pose_loss_bwd", C.byref(ctx.desc), ptr(work), ptr(g), float(crit.hyp.pose), float(crit.hyp.kobj), arr_k, nk_pad, st)
+        ops.emu_round(*dbufs, *dks)
+        no = 4 * REG_MAX + crit.nc
+        ctx.keep = None
+        return (None, None, None, *[d[:, :no] for d in dbufs], *[k[:, :nk] for k in dks])
+
+
+class v8PoseLoss(v8DetectionLoss):
+    """reference loss.py:292-377 (KeypointLoss :87-99): the detection terms (dy_loss_fwd / dy_loss_bwd on the HIP assignment) plus
+    the keypoint location and visibility terms on csrc/pose.hip.  Returns (loss.sum() * B, items [box, pose, kobj, cls, dfl]);
+    `model.args` carries .box/.cls/.dfl/.pose/.kobj (cfg/default.yaml).  The OKS sigmas are OKS_SIGMA for kpt_shape [17, 3]
+    (compared as a list, as the yaml gives it), else ones(K) / K."""
+
+    def __init__(self, model):
+        super().__init__(model)
+        from .metrics import OKS_SIGMA
+        self.kpt_shape = model.model[-1].kpt_shape
+        K = int(self.kpt_shape[0])
+        is_pose = [int(v) for v in self.kpt_shape] == [17, 3]
+        self.sigmas = torch.from_numpy(OKS_SIGMA).float() if is_pose else torch.ones(K) / K
+        self._sigmas_dev = None
+
+    def sigmas_on(self, dev):
+        if self._sigmas_dev is None or self._sigmas_dev.device != dev:
+            self._sigmas_dev = self.sigmas.to(dev, torch.float32).contiguous()
+        return self._sigmas_dev
+
+    def __call__(self, preds, batch):
+        feats, pred_kpts = preds if isinstance(preds[0], list) else preds[1]
+        if len(pred_kpts) != len(feats):
+            raise ValueError(f"pose loss: {len(pred_kpts)} keypoint maps for {len(feats)} Detect levels")
+        return _PoseLossFn.apply(self, batch, len(feats), *feats, *pred_kpts)
+
 class TaskAlignedAssigner:
     """reference tal.py:59-243 (topk must be 10, alpha 0.5, beta 6.0: the constants compiled into the kernel).
 

@@ -251,3 +251,66 @@ class SegmentMetrics:
     @property
     def results_dict(self):
         return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))
+
+
+OKS_SIGMA = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0   # metrics.py:15
+
+
+def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
+    """OKS (reference metrics.py:150-169): gt kpt1 [N, K, 3], predictions kpt2 [M, K, 2 or 3], gt areas [N], sigma [K] -> [N, M],
+    on the device (dy_kpt_oks, f32, the reference's arithmetic order per keypoint)."""
+    from .. import _C
+    from ..ops import ptr, stream
+    if not kpt2.is_cuda:
+        raise RuntimeError("kpt_iou needs device tensors (there is no CPU path)")
+    dev = kpt2.device
+    N, M, K = kpt1.shape[0], kpt2.shape[0], kpt2.shape[1] if kpt2.dim() == 3 else kpt1.shape[1]
+    out = torch.zeros((N, M), dtype=torch.float32, device=dev)
+    if N == 0 or M == 0:
+        return out
+    g = kpt1.to(dev, torch.float32).reshape(N, K, 3).contiguous()
+    q = kpt2.to(dev, torch.float32).reshape(M, K, -1).contiguous()
+    a = torch.as_tensor(area).to(dev, torch.float32).reshape(N).contiguous()
+    sg = torch.as_tensor(np.asarray(sigma), dtype=torch.float32).to(dev).reshape(K).contiguous()
+    _C.call("dy_kpt_oks", ptr(g), N, ptr(q), M, q.shape[2], ptr(a), ptr(sg), K, float(eps), ptr(out), stream())
+    return out
+
+
+class PoseMetrics:
+    """Box and pose tables of the pose validator (reference PoseMetrics, metrics.py:913-1015): `.process(tp_b, tp_p, conf,
+    pred_cls, target_cls)`, keys `metrics/...(B)` then `metrics/...(P)`, fitness = pose fitness + box fitness."""
+    keys = DetMetrics.keys + ["metrics/precision(P)", "metrics/recall(P)", "metrics/mAP50(P)", "metrics/mAP50-95(P)"]
+
+    def __init__(self, save_dir=None, plot=False, on_plot=None, names=()):
+        self.save_dir, self.plot, self.on_plot, self.names = save_dir, plot, on_plot, names
+        self.box = BoxSummary()
+        self.pose = BoxSummary()
+        self.speed = dict(preprocess=0.0, inference=0.0, loss=0.0, postprocess=0.0)
+
+    def process(self, tp_b, tp_p, conf, pred_cls, target_cls):
+        self.pose.nc = len(self.names)
+        self.pose.update(ap_per_class(tp_p, conf, pred_cls, target_cls, names=self.names)[2:])
+        self.box.nc = len(self.names)
+        self.box.update(ap_per_class(tp_b, conf, pred_cls, target_cls, names=self.names)[2:])
+
+    def mean_results(self):
+        return self.box.mean_results() + self.pose.mean_results()
+
+    def class_result(self, i):
+        return self.box.class_result(i) + self.pose.class_result(i)
+
+    @property
+    def maps(self):
+        return self.box.maps + self.pose.maps
+
+    @property
+    def fitness(self):
+        return self.pose.fitness() + self.box.fitness()
+
+    @property
+    def ap_class_index(self):
+        return self.box.ap_class_index
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))

@@ -54,6 +54,33 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True):
     return clip_boxes(boxes, img0_shape)
 
 
+def clip_coords(coords, shape):
+    """in place (reference ops.py:300-316): x to [0, w], y to [0, h]"""
+    coords[..., 0].clamp_(0, shape[1])
+    coords[..., 1].clamp_(0, shape[0])
+
+
+def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None, normalize=False, padding=True):
+    """Rescale keypoint coordinates [..., >= 2] from the network input shape to the original image shape, in place (reference
+    ops.py:669-701: the letterbox pad is not rounded here, unlike scale_boxes), clipped to the image."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    else:
+        gain = ratio_pad[0][0]
+        pad = ratio_pad[1]
+    if padding:
+        coords[..., 0] -= pad[0]
+        coords[..., 1] -= pad[1]
+    coords[..., 0] /= gain
+    coords[..., 1] /= gain
+    clip_coords(coords, img0_shape)
+    if normalize:
+        coords[..., 0] /= img0_shape[1]
+        coords[..., 1] /= img0_shape[0]
+    return coords
+
+
 _ws = {}
 
 

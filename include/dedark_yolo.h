@@ -316,6 +316,8 @@ int dy_loss_bwd(const dy_det_maps* m, void* const* dmap, const int64_t* dmap_ld,
                 const double* acc, const float* grad_out, float hyp_box, float hyp_cls, float hyp_dfl, void* stream);
 /* Detect eval decode (head.py:66-93): y[B, 4+nc, A] f32 = cat(xywh*stride, sigmoid(cls)) */
 int dy_detect_decode(const dy_det_maps* m, float* y, void* stream);
+/* the same into y[B, rows, A] f32, rows >= 4+nc (rows past 4+nc are not written: the Pose head's keypoint rows, dy_pose_kpt_decode) */
+int dy_detect_decode_rows(const dy_det_maps* m, float* y, int rows, void* stream);
 /* ------------------------------------------------------------------------------------------------ NMS
  * non_max_suppression (U/utils/ops.py:144-278; called from U/models/yolo/detect/val.py:62-70) for the whole batch.
  * pred [B, 4+nc, A] f32 = Detect's eval output (xywh px + class scores).  Three stages:
@@ -480,6 +482,47 @@ int dy_seg_crop_mask(float* masks, const float* boxes, int n, int h, int w, void
  * work: int32 [m*n + n]. */
 int dy_seg_mask_iou(const uint8_t* pred, int n, const void* gt, int gt_dtype, int overlap, int m, int64_t hw, int32_t* work,
                     float* iou, void* stream);
+
+/* ---- pose task (csrc/pose.hip) ------------------------------------------------------------------------------------------------------
+ * Keypoint terms of v8PoseLoss / KeypointLoss (U/utils/loss.py:87-99, 292-377) on the assignment of dy_tal_assign, Pose.kpts_decode
+ * (U/nn/modules/head.py:221-241) and kpt_iou (U/utils/metrics.py:150-169).  Fixed-order sums, no float atomics, no host
+ * synchronisation.  The keypoint maps are the per-level outputs of Pose.cv4[l][2], read in place: NHWC [B][h_l][w_l][kpt_ld_l] in the
+ * compute dtype, channel k * ndim + j = coordinate j (x, y, visibility logit) of keypoint k; anchors are numbered level by level as in
+ * dy_det_maps / dy_det_maps4. */
+#define DY_POSE_MAX_LEVELS 4
+typedef struct dy_pose_desc {
+  const void* kpt[DY_POSE_MAX_LEVELS];    /* level maps (n_levels used) */
+  int64_t kpt_ld[DY_POSE_MAX_LEVELS];     /* pixel stride of each map, >= K * ndim */
+  int32_t h[DY_POSE_MAX_LEVELS], w[DY_POSE_MAX_LEVELS];
+  float stride[DY_POSE_MAX_LEVELS];
+  int32_t n_levels, B, A, K, ndim, dtype; /* A = sum of h_l * w_l; ndim 2 or 3; DY_F32 / DY_BF16 / DY_F16 */
+  /* loss only (dy_pose_kpt_decode reads none of these): */
+  const int32_t* target_gt_idx;           /* [B][A] from dy_tal_assign */
+  const uint8_t* fg_mask;                 /* [B][A] */
+  const float* target_box;                /* [B][A][4] xyxy pixels */
+  const float* keypoints;                 /* [n_targets][K][3] f32: normalised x, y and visibility (3 columns for ndim 2 as well) */
+  int32_t n_targets;
+  const int32_t* gt_rows; int32_t n_max;  /* dy_seg_gt_rows table [B][n_max]: gt g of image b = keypoints row gt_rows[b][g] */
+  float img_h, img_w;                     /* network input size */
+  const float* sigma;                     /* [K] f32: OKS_SIGMA for kpt_shape [17, 3], else 1 / K */
+  const int32_t* pos; const int32_t* npos;/* dy_seg_positives of fg_mask */
+} dy_pose_desc;
+/* Keypoint loss.  work: f32 [3*B*A + 3*B] (per-positive sums, then per image pose_b, kobj_b, visible count; dy_pose_loss_bwd reads it).
+ * det_out = dy_loss_finish's (total, box, cls, dfl) -> out[6] = (total + (pose + kobj) * B, box, pose, kobj, cls, dfl) with
+ * pose = hyp_pose / B * sum_b (n_b K) / (nnz_b + 1e-9) * mean((1 - exp(-e)) * vis), kobj = hyp_kobj / B * sum_b mean BCE(logit, vis)
+ * (0 for ndim 2), n_b = positives of image b; images without positives add 0. */
+int dy_pose_loss_fwd(const dy_pose_desc* d, float hyp_pose, float hyp_kobj, float* work, const float* det_out, float* out, void* stream);
+/* d total / d keypoint maps, scaled by *grad_out (f32, device): dkpt[l] = NHWC [B][h_l][w_l][dk_ld] in the compute dtype, every element
+ * written (non-positive anchors, channels >= K * ndim and pad lanes get 0); dk_ld >= K * ndim rounded up to the vector width. */
+int dy_pose_loss_bwd(const dy_pose_desc* d, const float* work, const float* grad_out, float hyp_pose, float hyp_kobj,
+                     void* const* dkpt, int64_t dk_ld, void* stream);
+/* Eval decode into rows [4+nc, 4+nc+K*ndim) of y [B][4+nc+K*ndim][A] f32 (dy_detect_decode fills rows [0, 4+nc)):
+ * x = (raw * 2 + (anchor_x - 0.5)) * stride, likewise y, sigmoid(raw) for the visibility of ndim 3. */
+int dy_pose_kpt_decode(const dy_pose_desc* d, int nc, float* y, void* stream);
+/* OKS (kpt_iou): gt f32 [N][K][3], pred f32 [M][K][pred_dim], area f32 [N], sigma f32 [K] -> out f32 [N][M] =
+ * sum_k exp(-e) [vis != 0] / (sum_k [vis != 0] + eps), e = d / (2 sigma)^2 / (area + eps) / 2. */
+int dy_kpt_oks(const float* gt, int N, const float* pred, int M, int pred_dim, const float* area, const float* sigma, int K, float eps,
+               float* out, void* stream);
 
 #ifdef __cplusplus
 }
