@@ -4,13 +4,12 @@ from pathlib import Path
 
 import torch
 
-from ..nn.tasks import DetectionModel
+from ..nn.tasks import task_table
 from .trainer import DetectionTrainer, get_cfg
 
 
 def _model_class(task):
-    from ..nn.tasks import PoseModel, SegmentationModel
-    return SegmentationModel if task == "segment" else PoseModel if task == "pose" else DetectionModel
+    return task_table()[task][0]
 
 
 def _resolve_task(task, d):
@@ -92,11 +91,9 @@ class YOLO:
         return self.trainer.train(loader)
 
     def val(self, loader=None, **kwargs):
-        from .validator import DetectionValidator, PoseValidator, SegmentationValidator
         ov = dict(self.overrides)
         ov.update(kwargs)
-        v = {"segment": SegmentationValidator, "pose": PoseValidator}.get(self.task, DetectionValidator)(get_cfg(ov))
-        return v(self.model, loader)
+        return task_table()[self.task][2](get_cfg(ov))(self.model, loader)
 
     @torch.no_grad()
     def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, **kw):

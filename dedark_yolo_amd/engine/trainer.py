@@ -23,7 +23,7 @@ import yaml
 from .. import ops
 from .._C import call
 from ..nn.modules import DyModule
-from ..nn.tasks import DetectionModel
+from ..nn.tasks import DetectionModel, guess_model_task, task_table
 from ..ops import ptr, stream
 
 DEFAULT_CFG_PATH = Path(__file__).resolve().parent.parent / "cfg" / "default.yaml"
@@ -560,10 +560,7 @@ class DetectionTrainer:
     def validate(self, val_loader):
         """trainer.validate() (engine/trainer.py:471-480): the validator on the EMA weights, forced to fp32 as the fork does
         (engine/validator.py:105-107 `self.args.half = False`).  Returns (metrics dict, fitness)."""
-        from .validator import DetectionValidator, PoseValidator, SegmentationValidator
-        from ..nn.modules import Pose, Segment
-        head = self.model.model[-1]
-        V = SegmentationValidator if isinstance(head, Segment) else PoseValidator if isinstance(head, Pose) else DetectionValidator
+        V = task_table()[guess_model_task(self.model)][2]
         dt = ops.get_compute_dtype()
         try:
             with self.ema_weights() as model:

@@ -12,7 +12,7 @@ from .. import ops as kops
 from .._C import call
 from ..ops import ptr, stream
 from ..utils import ops
-from ..utils.metrics import OKS_SIGMA, DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou
+from ..utils.metrics import DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou, oks_sigmas
 
 
 def match_predictions(detections, labels, iouv):
@@ -51,6 +51,8 @@ def match_from_iou(iou, label_cls, det_cls, iouv):
 
 
 class DetectionValidator:
+    n_task = 0          # `correct` matrices per image besides the box one (_task_correct)
+
     def __init__(self, args=None, dataloader=None):
         from .trainer import get_cfg
         self.args = args if args is not None else get_cfg()
@@ -76,10 +78,11 @@ class DetectionValidator:
         batch["img"] = out
         return batch
 
-    def postprocess(self, preds):
+    def postprocess(self, preds, nc=0):
+        """NMS on the eval output; `nc` = the class count when task columns follow the class scores (segment, pose)."""
         a = self.args
         return ops.non_max_suppression(preds, self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
-                                       max_det=a.max_det)
+                                       max_det=a.max_det, nc=nc)
 
     def init_metrics(self, model):
         self.nc = model.model[-1].nc
@@ -89,7 +92,8 @@ class DetectionValidator:
         self.stats = []
 
     def update_metrics(self, preds, batch):
-        """val.py:72-116 on host copies."""
+        """val.py:72-116 on host copies.  Per image one row of `self.stats`: the box `correct` matrix, the task's own ones
+        (`_task_correct`; `n_task` of them), confidences, predicted classes, label classes."""
         bi = batch["batch_idx"].cpu()
         cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
         height, width = batch["img"].shape[2:]
@@ -100,11 +104,11 @@ class DetectionValidator:
             nl, npr = cls.shape[0], pred.shape[0]
             shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
             ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
-            correct = torch.zeros(npr, self.niou, dtype=torch.bool)
+            correct = [torch.zeros(npr, self.niou, dtype=torch.bool) for _ in range(1 + self.n_task)]
             self.seen += 1
             if npr == 0:
                 if nl:
-                    self.stats.append((correct, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
+                    self.stats.append((*correct, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
                 continue
             if getattr(self.args, "single_cls", False):
                 pred[:, 5] = 0
@@ -113,8 +117,14 @@ class DetectionValidator:
             if nl:
                 tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
                 ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
-                correct = match_predictions(predn, torch.cat((cls, tbox), 1), self.iouv)
-            self.stats.append((correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+                labelsn = torch.cat((cls, tbox), 1)
+                correct = [match_predictions(predn, labelsn, self.iouv),
+                           *self._task_correct(batch, si, idx, predn, labelsn, shape, ratio_pad)]
+            self.stats.append((*correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+
+    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
+        """The task's own `correct` matrices of image `si` (labels `idx` of the batch; predn / labelsn scaled to `shape`)."""
+        return ()
 
     def get_stats(self):
         """val.py:123-129"""
@@ -158,64 +168,41 @@ class SegmentationValidator(DetectionValidator):
     (dy_seg_mask_iou), box and mask `correct` matrices by the same matching rule, SegmentMetrics.  The gt masks must be at the
     proto resolution (the reference's bilinear resize of other sizes is not implemented)."""
 
+    n_task = 1
+
     def __init__(self, args=None, dataloader=None):
         super().__init__(args, dataloader)
         self.args.task = "segment"
         self.metrics = SegmentMetrics()
 
     def postprocess(self, preds):
-        a = self.args
-        p = ops.non_max_suppression(preds[0], self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
-                                    max_det=a.max_det, nc=self.nc)
         proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]
-        return p, proto
+        return super().postprocess(preds[0], nc=self.nc), proto
 
     def update_metrics(self, preds, batch):
         dets, proto = preds
-        overlap = bool(getattr(self.args, "overlap_mask", True))
         height, width = batch["img"].shape[2:]
         pmasks = ops.process_masks_batched(proto, [d[:, :6 + proto.shape[1]] for d in dets], (height, width))
         masks = batch["masks"]
         if tuple(masks.shape[-2:]) != tuple(proto.shape[2:]):
             raise NotImplementedError(f"segment validation: gt masks {tuple(masks.shape[-2:])} are not at the proto resolution "
                                       f"{tuple(proto.shape[2:])} (the bilinear path is not implemented)")
-        masks = masks.to(self.device, non_blocking=True)
-        bi = batch["batch_idx"].cpu()
-        cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
-        for si, pred in enumerate(dets):
-            idx = bi == si
-            cls, bbox = cls_all[idx], box_all[idx]
-            nl, npr = cls.shape[0], pred.shape[0]
-            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
-            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
-            correct_b = torch.zeros(npr, self.niou, dtype=torch.bool)
-            correct_m = torch.zeros(npr, self.niou, dtype=torch.bool)
-            self.seen += 1
-            if npr == 0:
-                if nl:
-                    self.stats.append((correct_b, correct_m, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
-                continue
-            if nl:
-                gt = masks[si] if overlap else masks[idx.to(masks.device)]
-                iou_m = ops.mask_iou_binary(gt, pmasks[si], overlap, nl).cpu().numpy()
-            pred = pred.cpu()
-            if getattr(self.args, "single_cls", False):
-                pred[:, 5] = 0
-            predn = pred[:, :6].clone()
-            ops.scale_boxes((height, width), predn[:, :4], shape, ratio_pad=ratio_pad)
-            if nl:
-                tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
-                ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
-                correct_b = match_predictions(predn, torch.cat((cls, tbox), 1), self.iouv)
-                correct_m = match_from_iou(iou_m, cls[:, 0], predn[:, 5], self.iouv)
-            self.stats.append((correct_b, correct_m, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+        super().update_metrics(dets, dict(batch, masks=masks.to(self.device, non_blocking=True), pmasks=pmasks))
+
+    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
+        overlap, masks = bool(getattr(self.args, "overlap_mask", True)), batch["masks"]
+        gt = masks[si] if overlap else masks[idx.to(masks.device)]
+        iou_m = ops.mask_iou_binary(gt, batch["pmasks"][si], overlap, labelsn.shape[0]).cpu().numpy()
+        return (match_from_iou(iou_m, labelsn[:, 0], predn[:, 5], self.iouv),)
 
 
 class PoseValidator(DetectionValidator):
     """Pose validator (reference models/yolo/pose/val.py): NMS with multi_label and the K * ndim keypoint columns appended,
     boxes (scale_boxes) and keypoints (scale_coords) to ori_shape / ratio_pad, OKS against the gt keypoints in native space with
     area = gt box w * h * 0.53 (kpt_iou on dy_kpt_oks), box and pose `correct` matrices by the same matching rule, PoseMetrics.
-    sigma = OKS_SIGMA for kpt_shape [17, 3], else ones(K) / K."""
+    sigma = metrics.oks_sigmas(kpt_shape)."""
+
+    n_task = 1
 
     def __init__(self, args=None, dataloader=None):
         super().__init__(args, dataloader)
@@ -225,53 +212,27 @@ class PoseValidator(DetectionValidator):
     def init_metrics(self, model):
         super().init_metrics(model)
         self.kpt_shape = list(model.model[-1].kpt_shape)
-        nkpt = int(self.kpt_shape[0])
-        self.sigma = OKS_SIGMA if [int(v) for v in self.kpt_shape] == [17, 3] else np.ones(nkpt) / nkpt
+        self.sigma = oks_sigmas(self.kpt_shape)
 
     def postprocess(self, preds):
-        a = self.args
-        return ops.non_max_suppression(preds, self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
-                                       max_det=a.max_det, nc=self.nc)
+        return super().postprocess(preds, nc=self.nc)
 
     def update_metrics(self, preds, batch):
         """val.py:62-109 on host copies (the OKS matrix on the device)."""
-        bi = batch["batch_idx"].cpu()
-        cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
         if "keypoints" not in batch:
             raise ValueError("pose validation: the batch has no 'keypoints'")
-        kpt_all = batch["keypoints"].cpu().float()
+        super().update_metrics(preds, dict(batch, keypoints=batch["keypoints"].cpu().float()))
+
+    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
         height, width = batch["img"].shape[2:]
-        for si, pred in enumerate(preds):
-            pred = pred.cpu()
-            idx = bi == si
-            cls, bbox, kpts = cls_all[idx], box_all[idx], kpt_all[idx]
-            nl, npr = cls.shape[0], pred.shape[0]
-            nk = kpts.shape[1] if kpts.dim() == 3 else int(self.kpt_shape[0])
-            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
-            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
-            correct_b = torch.zeros(npr, self.niou, dtype=torch.bool)
-            correct_p = torch.zeros(npr, self.niou, dtype=torch.bool)
-            self.seen += 1
-            if npr == 0:
-                if nl:
-                    self.stats.append((correct_b, correct_p, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
-                continue
-            if getattr(self.args, "single_cls", False):
-                pred[:, 5] = 0
-            predn = pred.clone()
-            ops.scale_boxes((height, width), predn[:, :4], shape, ratio_pad=ratio_pad)
-            pred_kpts = predn[:, 6:].view(npr, nk, -1)
-            ops.scale_coords((height, width), pred_kpts, shape, ratio_pad=ratio_pad)
-            if nl:
-                tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
-                ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
-                tkpts = kpts.clone()
-                tkpts[..., 0] *= width
-                tkpts[..., 1] *= height
-                tkpts = ops.scale_coords((height, width), tkpts, shape, ratio_pad=ratio_pad)
-                labelsn = torch.cat((cls, tbox), 1)
-                correct_b = match_predictions(predn, labelsn, self.iouv)
-                area = ops.xyxy2xywh(labelsn[:, 1:])[:, 2:].prod(1) * 0.53
-                oks = kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma).cpu().numpy()
-                correct_p = match_from_iou(oks, cls[:, 0], predn[:, 5], self.iouv)
-            self.stats.append((correct_b, correct_p, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+        kpts = batch["keypoints"][idx]
+        nk = kpts.shape[1] if kpts.dim() == 3 else int(self.kpt_shape[0])
+        pred_kpts = predn[:, 6:].view(predn.shape[0], nk, -1)
+        ops.scale_coords((height, width), pred_kpts, shape, ratio_pad=ratio_pad)
+        tkpts = kpts.clone()
+        tkpts[..., 0] *= width
+        tkpts[..., 1] *= height
+        tkpts = ops.scale_coords((height, width), tkpts, shape, ratio_pad=ratio_pad)
+        area = ops.xyxy2xywh(labelsn[:, 1:])[:, 2:].prod(1) * 0.53
+        oks = kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma).cpu().numpy()
+        return (match_from_iou(oks, labelsn[:, 0], predn[:, 5], self.iouv),)

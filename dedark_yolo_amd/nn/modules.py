@@ -884,22 +884,37 @@ class Detect(DyModule):
         self.reg_max = 16
         self.no = nc + self.reg_max * 4
         self.stride = torch.zeros(self.nl)
-        c2, c3 = max((16, ch[0] // 4, self.reg_max * 4)), max(ch[0], min(self.nc, 100))
-        self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * self.reg_max, 1)) for x in ch)
-        self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, self.nc, 1)) for x in ch)
+        self._make_branches(ch)
         self.dfl = DFL(self.reg_max)
+
+    def _make_branches(self, ch):
+        c2, c3 = max((16, ch[0] // 4, self.reg_max * 4)), max(ch[0], min(self.nc, 100))
+        self.cv2 = self._chains(ch, c2, 4 * self.reg_max)
+        self.cv3 = self._chains(ch, c3, self.nc)
+
+    @staticmethod
+    def _chains(ch, c, c_out):
+        """One Conv3x3, Conv3x3, Conv2d(c -> c_out, 1) chain per level: cv2, cv3 and the cv4 of Segment and Pose."""
+        return nn.ModuleList(nn.Sequential(Conv(x, c, 3), Conv(c, c, 3), nn.Conv2d(c, c_out, 1)) for x in ch)
+
+    @staticmethod
+    def _chain_fwd(tape, chain, x, out=None):
+        a, b, c = chain
+        return plain_conv_fwd(tape, c, b._fwd(tape, a._fwd(tape, x)), out=out)
+
+    @staticmethod
+    def _chain_bwd(tape, chain, g, dx=None):
+        """Gradient wrt the chain's input; added to `dx` when one is given."""
+        gt = chain[1]._bwd(tape, conv_backward(tape, g))
+        return chain[0]._bwd(tape, gt, dx_out=dx, accumulate=dx is not None)
 
     def _level_fwd(self, tape, i, x):
         B, _, H, W = x.shape
         ve = ops.vec_elems(x.dtype)
         nc_pad = ops.round_up(self.nc, ve)
         buf = empty_nhwc(B, 4 * self.reg_max + nc_pad, H, W, x.dtype, x.device)
-        a, b, c = self.cv2[i]
-        t = b._fwd(tape, a._fwd(tape, x))
-        plain_conv_fwd(tape, c, t, out=buf[:, :4 * self.reg_max])
-        a, b, c = self.cv3[i]
-        t = b._fwd(tape, a._fwd(tape, x))
-        plain_conv_fwd(tape, c, t, out=buf[:, 4 * self.reg_max:4 * self.reg_max + nc_pad])
+        self._chain_fwd(tape, self.cv2[i], x, out=buf[:, :4 * self.reg_max])
+        self._chain_fwd(tape, self.cv3[i], x, out=buf[:, 4 * self.reg_max:4 * self.reg_max + nc_pad])
         return buf[:, :self.no]
 
     def _level_bwd(self, tape, i, g):
@@ -907,12 +922,8 @@ class Detect(DyModule):
         nc_pad = ops.round_up(self.nc, ops.vec_elems(g.dtype))
         if ld_of(g) < r + nc_pad:
             raise RuntimeError("Detect: gradient map lacks channel padding")
-        gt = conv_backward(tape, g[:, r:r + self.nc])                      # cv3[i][2]
-        gt = self.cv3[i][1]._bwd(tape, gt)
-        dx = self.cv3[i][0]._bwd(tape, gt)
-        gt = conv_backward(tape, g[:, :r])                                 # cv2[i][2]
-        gt = self.cv2[i][1]._bwd(tape, gt)
-        return self.cv2[i][0]._bwd(tape, gt, dx_out=dx, accumulate=True)
+        dx = self._chain_bwd(tape, self.cv3[i], g[:, r:r + self.nc])
+        return self._chain_bwd(tape, self.cv2[i], g[:, :r], dx)
 
     def _run_levels(self, fn, tapes, args):
         """fn(tapes[i], i, args[i]) for every pyramid level.  The levels are independent chains of small kernels (three convs
@@ -948,11 +959,15 @@ class Detect(DyModule):
             tape.push(subs)
         if self.training:
             return maps
+        return (self._decode(maps), *maps)
+
+    def _decode(self, maps):
+        """The eval output y [B, 4 + nc, A] f32 of the level maps (dy_detect_decode)."""
         m = ops.det_maps(maps, self.strides_as_floats(), self.nc)
         A = sum(t.shape[2] * t.shape[3] for t in maps)
         y = torch.empty((maps[0].shape[0], 4 + self.nc, A), dtype=torch.float32, device=maps[0].device)
         call("dy_detect_decode", C.byref(m), ptr(y), stream())
-        return (y, *maps)
+        return y
 
     def strides_as_floats(self):
         """self.stride as host floats, read back once (float(tensor) per call is a device synchronisation)."""
@@ -967,15 +982,23 @@ class Detect(DyModule):
             return list(out)
         return out[0], list(out[1:])
 
-    def _bwd(self, tape, *dmaps, needs=None):
+    def _require_training(self):
         if not self.training:
-            raise RuntimeError("Detect: backward through the eval decode is not supported")
-        subs = tape.pop()
-        dxs = self._run_levels(self._level_bwd, subs, list(dmaps))
+            raise RuntimeError(f"{type(self).__name__}: backward through the eval decode is not supported")
+
+    @staticmethod
+    def _fold_tapes(tape, subs):
+        """The head's own tapes (one per level, Segment's Proto) must be used up; their parameter gradients go to `tape`."""
         for t in subs:
-            assert not t.stack, "Detect: unbalanced level tape"
+            assert not t.stack, "Detect head: unbalanced tape"
             for p, g in t.pgrads.items():
                 ops._add_pgrad(tape, p, g)
+
+    def _bwd(self, tape, *dmaps, needs=None):
+        self._require_training()
+        subs = tape.pop()
+        dxs = self._run_levels(self._level_bwd, subs, list(dmaps))
+        self._fold_tapes(tape, subs)
         return dxs
 
     def bias_init(self):
@@ -989,16 +1012,9 @@ class AsffDetect(Detect):
     """Detect head with one 1x1 conv per branch and level (reference head.py:105-174): cv2[i] = Conv2d(ch_i, 64, 1),
     cv3[i] = Conv2d(ch_i, nc, 1); decode, anchors and bias_init as Detect."""
 
-    def __init__(self, nc=80, ch=()):
-        DyModule.__init__(self)
-        self.nc = nc
-        self.nl = len(ch)
-        self.reg_max = 16
-        self.no = nc + self.reg_max * 4
-        self.stride = torch.zeros(self.nl)
+    def _make_branches(self, ch):
         self.cv2 = nn.ModuleList(nn.Sequential(nn.Conv2d(x, 4 * self.reg_max, 1)) for x in ch)
         self.cv3 = nn.ModuleList(nn.Sequential(nn.Conv2d(x, self.nc, 1)) for x in ch)
-        self.dfl = DFL(self.reg_max)
 
     def _level_fwd(self, tape, i, x):
         B, _, H, W = x.shape
@@ -1055,8 +1071,7 @@ class Segment(Detect):
         self.npr = npr
         self.proto = Proto(ch[0], self.npr, self.nm)
         self.detect = Detect.forward
-        c4 = max(ch[0] // 4, self.nm)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+        self.cv4 = self._chains(ch, max(ch[0] // 4, self.nm), self.nm)
 
     @staticmethod
     def _offsets(ts):
@@ -1067,8 +1082,7 @@ class Segment(Detect):
         return offs, o
 
     def _seg_level_fwd(self, tape, i, x, mc, off):
-        a, b, c = self.cv4[i]
-        y = plain_conv_fwd(tape, c, b._fwd(tape, a._fwd(tape, x)))
+        y = self._chain_fwd(tape, self.cv4[i], x)
         B, _, H, W = y.shape
         mc[:, off:off + H * W].view(B, H, W, self.nm).copy_(y.permute(0, 2, 3, 1))
         return self._level_fwd(tape, i, x)            # Detect's branches: their contexts sit on top of the tape
@@ -1078,8 +1092,7 @@ class Segment(Detect):
         B, _, H, W = g.shape
         gl = empty_nhwc(B, self.nm, H, W, g.dtype, g.device)
         gl.permute(0, 2, 3, 1).view(B, H * W, self.nm).copy_(dmc[:, off:off + H * W])   # .view: raises if gl were not dense
-        gt = self.cv4[i][1]._bwd(tape, conv_backward(tape, gl))
-        return self.cv4[i][0]._bwd(tape, gt, dx_out=dx, accumulate=True)
+        return self._chain_bwd(tape, self.cv4[i], gl, dx)
 
     def _fwd(self, tape, *xs):
         if self.nm % ops.vec_elems(xs[0].dtype):
@@ -1096,10 +1109,7 @@ class Segment(Detect):
         mc4 = mc.permute(0, 2, 1).unsqueeze(2)         # [B, nm, 1, A]: a 4-d NHWC view (pixel stride nm) for the graph plumbing
         if self.training:
             return [*maps, mc4, p]
-        m = ops.det_maps(maps, self.strides_as_floats(), self.nc)
-        y = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev)
-        call("dy_detect_decode", C.byref(m), ptr(y), stream())
-        return (y, *maps, mc4, p)
+        return (self._decode(maps), *maps, mc4, p)
 
     def _wrap(self, out):
         n = self.nl
@@ -1109,20 +1119,15 @@ class Segment(Detect):
         return torch.cat([out[0], mc.float()], 1), (list(out[1:1 + n]), mc, out[2 + n])
 
     def _bwd(self, tape, *gs, needs=None):
-        if not self.training:
-            raise RuntimeError("Segment: backward through the eval decode is not supported")
+        self._require_training()
         n = self.nl
         subs, ptape = tape.pop()
         dmc = gs[n].squeeze(2).permute(0, 2, 1)        # [B, A, nm]
         offs, _ = self._offsets(gs[:n])
         dxs = self._run_levels(lambda t, i, g: self._seg_level_bwd(t, i, g, dmc, offs[i]), subs, list(gs[:n]))
         self.proto._bwd(ptape, gs[n + 1], dx_out=dxs[0], accumulate=True)
-        for t in subs + [ptape]:
-            assert not t.stack, "Segment: unbalanced tape"
-            for p, g in t.pgrads.items():
-                ops._add_pgrad(tape, p, g)
+        self._fold_tapes(tape, subs + [ptape])
         return dxs
-
 
 
 class Pose(Detect):
@@ -1140,19 +1145,16 @@ class Pose(Detect):
         self.kpt_shape = kpt_shape
         self.nk = kpt_shape[0] * kpt_shape[1]
         self.detect = Detect.forward
-        c4 = max(ch[0] // 4, self.nk)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+        self.cv4 = self._chains(ch, max(ch[0] // 4, self.nk), self.nk)
 
     def _pose_level_fwd(self, tape, i, x):
-        a, b, c = self.cv4[i]
-        k = plain_conv_fwd(tape, c, b._fwd(tape, a._fwd(tape, x)))
+        k = self._chain_fwd(tape, self.cv4[i], x)
         return self._level_fwd(tape, i, x), k          # Detect's branches: their contexts sit on top of the tape
 
     def _pose_level_bwd(self, tape, i, g, gk):
         gk.record_stream(torch.cuda.current_stream(gk.device))   # may be a branch stream: as Detect._run_levels does for g
         dx = self._level_bwd(tape, i, g)
-        gt = self.cv4[i][1]._bwd(tape, conv_backward(tape, gk))
-        return self.cv4[i][0]._bwd(tape, gt, dx_out=dx, accumulate=True)
+        return self._chain_bwd(tape, self.cv4[i], gk, dx)
 
     def _fwd(self, tape, *xs):
         subs = [Tape() if tape is not None else None for _ in xs]
@@ -1180,16 +1182,12 @@ class Pose(Detect):
         return out[0], (list(out[1:1 + n]), list(out[1 + n:1 + 2 * n]))
 
     def _bwd(self, tape, *gs, needs=None):
-        if not self.training:
-            raise RuntimeError("Pose: backward through the eval decode is not supported")
+        self._require_training()
         n = self.nl
         subs = tape.pop()
         gk = gs[n:2 * n]
         dxs = self._run_levels(lambda t, i, g: self._pose_level_bwd(t, i, g, gk[i]), subs, list(gs[:n]))
-        for t in subs:
-            assert not t.stack, "Pose: unbalanced level tape"
-            for p, g in t.pgrads.items():
-                ops._add_pgrad(tape, p, g)
+        self._fold_tapes(tape, subs)
         return dxs
 
 # ------------------------------------------------------------------------------------------------ low-light front-end

@@ -399,7 +399,7 @@ class BaseModel(nn.Module):
             params = cached[1]
             if params or x.requires_grad:
                 out = _GraphFn.apply(plan, (None, None), params, x, *params)
-                return list(out) if isinstance(out, tuple) else out
+                return self.model[-1]._wrap(out) if isinstance(out, tuple) else out     # the head's flat outputs -> its call result
 
         def call_layer(m, inp, out=None):
             if eval_front and isinstance(m, lowlight_recovery):
@@ -577,12 +577,6 @@ class SegmentationModel(DetectionModel):
         if not isinstance(self.model[-1], Segment):
             raise ValueError("SegmentationModel: the yaml's last layer is not a Segment head")
 
-    def _predict_once(self, x, profile=False, visualize=False):
-        out = super()._predict_once(x, profile, visualize)
-        if isinstance(out, list):              # the layer graph's own training output: maps..., mc [B, nm, 1, A], proto
-            return self.model[-1]._wrap(out)
-        return out
-
     def init_criterion(self):
         from ..utils.loss import v8SegmentationLoss
         return v8SegmentationLoss(self)
@@ -602,29 +596,32 @@ class PoseModel(DetectionModel):
         if not isinstance(self.model[-1], Pose):
             raise ValueError("PoseModel: the yaml's last layer is not a Pose head")
 
-    def _predict_once(self, x, profile=False, visualize=False):
-        out = super()._predict_once(x, profile, visualize)
-        if isinstance(out, list):              # the layer graph's own training output: maps..., kpt maps...
-            return self.model[-1]._wrap(out)
-        return out
-
     def init_criterion(self):
         from ..utils.loss import v8PoseLoss
         return v8PoseLoss(self)
 
 
+def task_table():
+    """task -> (model class, head class, validator class): the one place that says which classes serve which task, in the order
+    a head is matched (Segment and Pose subclass Detect, so 'detect' comes last).  A function, because the validators live in the
+    engine package, which imports this module."""
+    from ..engine.validator import DetectionValidator, PoseValidator, SegmentationValidator
+    return {"segment": (SegmentationModel, Segment, SegmentationValidator),
+            "pose": (PoseModel, Pose, PoseValidator),
+            "detect": (DetectionModel, Detect, DetectionValidator)}
+
+
 def guess_model_task(model):
-    """'segment' for a Segment head, 'pose' for a Pose head, 'detect' for Detect / AsffDetect (reference tasks.py:968-1030, from a
-    yaml dict or a model).  Pose subclasses Detect, so it is checked first.  The reference's yaml rule reads
-    `m == 'detect' or "asffdetect"`, which is always true; the intended rule is used here."""
+    """The task whose head class (task_table) the model's last layer is: 'segment', 'pose', or 'detect' for Detect / AsffDetect
+    (reference tasks.py:968-1030, from a yaml dict or a model).  The reference's yaml rule reads `m == 'detect' or "asffdetect"`,
+    which is always true; the intended rule is used here."""
     if isinstance(model, dict):
         kind = str(model["head"][-1][-2]).lower()
-        if kind in ("segment", "pose"):
-            return kind
-        if kind in ("detect", "asffdetect"):
-            return "detect"
-        raise NotImplementedError(f"head '{model['head'][-1][-2]}' is outside the Dedark-YOLO hot path")
-    if isinstance(model, nn.Module):
-        last = model.model[-1] if hasattr(model, "model") else model
-        return "segment" if isinstance(last, Segment) else "pose" if isinstance(last, Pose) else "detect"
-    raise TypeError(f"guess_model_task: expected a yaml dict or a model, got {type(model).__name__}")
+        head = next((c for name, c in _REGISTRY.items() if name.lower() == kind and issubclass(c, Detect)), None)
+        if head is None:
+            raise NotImplementedError(f"head '{model['head'][-1][-2]}' is outside the Dedark-YOLO hot path")
+    elif isinstance(model, nn.Module):
+        head = type(model.model[-1] if hasattr(model, "model") else model)
+    else:
+        raise TypeError(f"guess_model_task: expected a yaml dict or a model, got {type(model).__name__}")
+    return next((task for task, (_, h, _) in task_table().items() if issubclass(head, h)), "detect")

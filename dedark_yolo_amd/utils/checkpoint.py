@@ -278,6 +278,12 @@ class _RefPickler(pickle._Pickler):
     dispatch[type] = save_global
 
 
+def model_class_name(model):
+    """The reference class a model is written as: the model class of its task (nn.tasks.task_table), DetectionModel for any other."""
+    from ..nn.tasks import task_table
+    return next((m.__name__ for m, _, _ in task_table().values() if isinstance(model, m)), "DetectionModel")
+
+
 class _RefPickleModule:
     __name__ = "dedark_yolo_amd.utils.checkpoint"
     Pickler = _RefPickler
@@ -433,8 +439,7 @@ class _RefWriter:
         return self.filters
 
     def model(self, model, args):
-        cls = type(model).__name__ if type(model).__name__ in ("SegmentationModel", "PoseModel") else "DetectionModel"
-        obj = _standin_type("ultralytics.nn.tasks", cls)()
+        obj = _standin_type("ultralytics.nn.tasks", model_class_name(model))()
         state = _nn_base_state(self.training)
         layers = list(model.model)
         save = sorted(x % m.i for m in layers for x in ([m.f] if isinstance(m.f, int) else m.f) if x != -1)      # tasks.py:913

@@ -12,6 +12,7 @@ import torch
 
 from .. import _C, ops
 from .._C import call
+from ..nn.modules import Detect
 from ..ops import ld_of, ptr, stream
 
 REG_MAX = 16
@@ -97,54 +98,79 @@ def assign(maps, strides, nc, batch_idx, cls, bboxes, n_max=None, frozen=None):
     return a
 
 
+def _det_forward(crit, batch, maps, rec=None, lrl=0.0):
+    """The detection terms every criterion shares: assignment, dy_loss_fwd, dy_loss_finish (`rec`, `lrl`: the recovery term of the
+    detect criterion).  Returns (det, out): det = (maps, strides, assignment, acc) is what _det_backward needs, out the 4 floats
+    [loss, box, cls, dfl]."""
+    B, dev, st = maps[0].shape[0], maps[0].device, stream()
+    strides = Detect.strides_as_floats(crit.head)[:len(maps)]
+    a = assign(maps, strides, crit.nc, batch["batch_idx"], batch["cls"], batch["bboxes"], batch.get("n_max"),
+               frozen=crit.frozen_assignment)
+    dm = ops.det_maps(maps, strides, crit.nc)
+    acc = torch.zeros(4, dtype=torch.float64, device=dev)
+    call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
+         ptr(acc), st)
+    if rec is not None:
+        rec = rec.detach().to(dev, torch.float32).reshape(-1)
+        rec = rec.mean().reshape(1) if rec.numel() > 1 else rec
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    call("dy_loss_finish", ptr(acc), ptr(rec), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), float(lrl), B,
+         ptr(out[0:1]), ptr(out[1:4]), st)
+    crit.last_assignment = a
+    if crit.keep_maps:
+        crit.last_maps = maps
+    return (maps, strides, a, acc), out
+
+
+def _det_backward(crit, det, gloss):
+    """d(detection terms)/d(maps) with one dy_loss_bwd.  Returns (the per-level gradient views [B, no, h, w], g): g is the
+    incoming gradient as one f32 on the device, which the task kernels take as well."""
+    maps, strides, a, acc = det
+    dev, dt = maps[0].device, maps[0].dtype
+    dm = ops.det_maps(maps, strides, crit.nc)
+    width = 4 * REG_MAX + ops.round_up(crit.nc, ops.vec_elems(dt))
+    dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
+    arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
+    arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
+    g = gloss.detach().to(torch.float32).reshape(1).contiguous()
+    call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
+         ptr(a.target_box), ptr(acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), stream())
+    ops.emu_round(*dbufs)
+    no = 4 * REG_MAX + crit.nc
+    return [d[:, :no] for d in dbufs], g
+
+
+def _positives(a, batch_idx, with_rows):
+    """What the mask and keypoint kernels walk: the gt-row table rows [B, n_max] (where image b's j-th box sits in the batch's
+    label arrays; None unless `with_rows`) and the positive anchors pos [B, A] / npos [B] of assignment `a`."""
+    (B, A), dev, st = a.fg_mask.shape, a.fg_mask.device, stream()
+    rows = None
+    if with_rows:
+        n_t, n_max = int(batch_idx.numel()), max(a.n_max, 1)
+        bif = batch_idx.to(dev, torch.float32).contiguous().view(-1)
+        rows = torch.empty((B, n_max), dtype=torch.int32, device=dev)
+        call("dy_seg_gt_rows", ptr(bif) if n_t else None, n_t, B, n_max, ptr(rows), st)
+    pos = torch.empty((B, A), dtype=torch.int32, device=dev)
+    npos = torch.empty(B, dtype=torch.int32, device=dev)
+    call("dy_seg_positives", ptr(a.fg_mask), B, A, ptr(pos), ptr(npos), st)
+    return rows, pos, npos
+
+
 class _DetLossFn(torch.autograd.Function):
     """loss, loss_items = f(map0, map1, map2); backward writes d(loss)/d(maps) with one kernel."""
 
     @staticmethod
     def forward(ctx, crit, batch, n_maps, *maps):
-        maps = [ops.as_nhwc(m) for m in maps]
-        B = maps[0].shape[0]
-        dev = maps[0].device
-        st = stream()
-        strides = crit.strides_as_floats()[:n_maps]
-        a = assign(maps, strides, crit.nc, batch["batch_idx"], batch["cls"], batch["bboxes"], batch.get("n_max"),
-                   frozen=crit.frozen_assignment)
-        dm = ops.det_maps(maps, strides, crit.nc)
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
-             ptr(acc), st)
         rec = batch.get("recovery_loss_batch") if crit.use_recovery else None
-        if rec is not None:
-            rec = rec.detach().to(dev, torch.float32).reshape(-1)
-            rec = rec.mean().reshape(1) if rec.numel() > 1 else rec
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        call("dy_loss_finish", ptr(acc), ptr(rec), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl),
-             float(getattr(crit.hyp, "lrl", 0.0)), B, ptr(out[0:1]), ptr(out[1:4]), st)
-        ctx.crit, ctx.maps, ctx.assign, ctx.acc, ctx.strides = crit, maps, a, acc, strides
-        crit.last_assignment = a
-        if crit.keep_maps:
-            crit.last_maps = maps
+        ctx.crit = crit
+        ctx.det, out = _det_forward(crit, batch, [ops.as_nhwc(m) for m in maps], rec, getattr(crit.hyp, "lrl", 0.0))
         loss, items = out[0], out[1:4]
         ctx.mark_non_differentiable(items)
         return loss, items
 
     @staticmethod
     def backward(ctx, gloss, _gitems):
-        crit, maps, a = ctx.crit, ctx.maps, ctx.assign
-        dev = maps[0].device
-        dt = maps[0].dtype
-        ve = ops.vec_elems(dt)
-        dm = ops.det_maps(maps, ctx.strides, crit.nc)
-        width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
-        dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
-        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
-        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
-        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
-             ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), stream())
-        ops.emu_round(*dbufs)
-        no = 4 * REG_MAX + crit.nc
-        return (None, None, None, *[d[:, :no] for d in dbufs])
+        return (None, None, None, *_det_backward(ctx.crit, ctx.det, gloss)[0])
 
 
 class _DFL(torch.autograd.Function):
@@ -186,6 +212,7 @@ class v8DetectionLoss:
     def __init__(self, model):
         m = model.model[-1]
         self.hyp = model.args
+        self.head = m                        # asked for its host strides every call (Detect.strides_as_floats)
         self.stride = m.stride
         self.nc = m.nc
         self.no = m.no
@@ -196,14 +223,6 @@ class v8DetectionLoss:
         self.last_assignment = None
         self.frozen_assignment = None        # test hooks: reuse an earlier assignment / keep the Detect maps of the last call
         self.keep_maps, self.last_maps = False, None
-
-    def strides_as_floats(self):
-        """Detect.stride as host floats, read back once (a per-step float(tensor) is a device synchronisation)."""
-        key = (id(self.stride), self.stride._version)
-        if getattr(self, "_stride_key", None) != key:
-            self._stride_host = [float(s) for s in self.stride.detach().cpu()]
-            self._stride_key = key
-        return self._stride_host
 
     def __call__(self, preds, batch):
         feats = preds[1] if isinstance(preds, tuple) else preds
@@ -245,31 +264,14 @@ class _SegLossFn(torch.autograd.Function):
         if (mcr.dtype != dt or mcr.stride(2) != 1 or mcr.stride(1) != mcr.shape[2] or mcr.stride(0) != A * mcr.shape[2]
                 or mcr.data_ptr() % 16):
             mcr = mcr.to(dt).contiguous()
-        strides = crit.strides_as_floats()[:n_maps]
-        bi = batch["batch_idx"]
-        a = assign(maps, strides, crit.nc, bi, batch["cls"], batch["bboxes"], batch.get("n_max"), frozen=crit.frozen_assignment)
-        dm = ops.det_maps(maps, strides, crit.nc)
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
-             ptr(acc), st)
-        det = torch.empty(4, dtype=torch.float32, device=dev)
-        call("dy_loss_finish", ptr(acc), None, float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), 0.0, B, ptr(det[0:1]),
-             ptr(det[1:4]), st)
+        ctx.det, det = _det_forward(crit, batch, maps)
+        _, strides, a, _ = ctx.det
         masks = _gt_masks(batch, B, dev)
-        n_max = max(a.n_max, 1)
-        rows = None
-        if not crit.overlap:
-            n_t = int(bi.numel())
-            bif = bi.to(dev, torch.float32).contiguous().view(-1)
-            rows = torch.empty((B, n_max), dtype=torch.int32, device=dev)
-            call("dy_seg_gt_rows", ptr(bif) if n_t else None, n_t, B, n_max, ptr(rows), st)
-            if masks.dim() != 3 or masks.shape[0] != n_t:
-                raise ValueError(f"segment loss: overlap_mask=False needs masks [N={n_t}, h, w], got {tuple(masks.shape)}")
-        elif masks.dim() != 3 or masks.shape[0] != B:
-            raise ValueError(f"segment loss: overlap_mask=True needs masks [B={B}, h, w], got {tuple(masks.shape)}")
-        pos = torch.empty((B, A), dtype=torch.int32, device=dev)
-        npos = torch.empty(B, dtype=torch.int32, device=dev)
-        call("dy_seg_positives", ptr(a.fg_mask), B, A, ptr(pos), ptr(npos), st)
+        n_t, n_max = int(batch["batch_idx"].numel()), max(a.n_max, 1)
+        want = f"B={B}" if crit.overlap else f"N={n_t}"          # one index map per image, or one plane per label
+        if masks.dim() != 3 or masks.shape[0] != (B if crit.overlap else n_t):
+            raise ValueError(f"segment loss: overlap_mask={crit.overlap} needs masks [{want}, h, w], got {tuple(masks.shape)}")
+        rows, pos, npos = _positives(a, batch["batch_idx"], with_rows=not crit.overlap)
         d = _C.SegDesc()
         d.mc, d.mc_ld, d.proto, d.proto_ld = mcr.data_ptr(), mcr.stride(1), proto.data_ptr(), ld_of(proto)
         d.B, d.A, d.nm, d.mh, d.mw = B, A, mc.shape[1], proto.shape[2], proto.shape[3]
@@ -283,38 +285,26 @@ class _SegLossFn(torch.autograd.Function):
         lossp = torch.empty(B * A + B, dtype=torch.float32, device=dev)
         out = torch.empty(5, dtype=torch.float32, device=dev)
         call("dy_seg_loss_fwd", C.byref(d), float(crit.hyp.box), ptr(lossp), ptr(det), ptr(out), st)
-        ctx.crit, ctx.maps, ctx.assign, ctx.acc, ctx.strides = crit, maps, a, acc, strides
-        ctx.desc, ctx.keep = d, (mcr, proto, masks, rows, pos, npos)
+        ctx.crit, ctx.desc, ctx.keep = crit, d, (mcr, proto, masks, rows, pos, npos)
         ctx.mc_meta = (mc.shape, mc.dtype)
-        crit.last_assignment = a
         loss, items = out[0], out[1:5]
         ctx.mark_non_differentiable(items)
         return loss, items
 
     @staticmethod
     def backward(ctx, gloss, _gitems):
-        crit, maps, a = ctx.crit, ctx.maps, ctx.assign
-        dev, dt, st = maps[0].device, maps[0].dtype, stream()
-        ve = ops.vec_elems(dt)
-        dm = ops.det_maps(maps, ctx.strides, crit.nc)
-        width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
-        dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
-        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
-        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
-        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
-             ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), st)
+        crit, st = ctx.crit, stream()
+        dmaps, g = _det_backward(crit, ctx.det, gloss)
         mcr, proto = ctx.keep[0], ctx.keep[1]
-        B, A, nm = mcr.shape
+        (B, A, nm), dev = mcr.shape, mcr.device
         dmc = torch.zeros((B, A, nm), dtype=mcr.dtype, device=dev)      # rows of anchors without a positive stay zero
         dp = ops.empty_nhwc(B, nm, proto.shape[2], proto.shape[3], proto.dtype, dev)
         call("dy_seg_loss_bwd", C.byref(ctx.desc), ptr(g), float(crit.hyp.box), ptr(dmc), nm, ptr(dp), ld_of(dp), st)
-        ops.emu_round(*dbufs, dmc, dp)
-        no = 4 * REG_MAX + crit.nc
+        ops.emu_round(dmc, dp)
         shape, mdt = ctx.mc_meta
         dmc_out = dmc.transpose(1, 2) if mdt == dmc.dtype else dmc.transpose(1, 2).to(mdt)
         ctx.keep = None
-        return (None, None, None, *[d[:, :no] for d in dbufs], dmc_out, dp)
+        return (None, None, None, *dmaps, dmc_out, dp)
 
 
 class v8SegmentationLoss(v8DetectionLoss):
@@ -355,26 +345,11 @@ class _PoseLossFn(torch.autograd.Function):
         maps = [ops.as_nhwc(m) for m in ts[:n_maps]]
         kpts = [ops.as_nhwc(k, maps[0].dtype) for k in ts[n_maps:2 * n_maps]]
         B, dev, st = maps[0].shape[0], maps[0].device, stream()
-        strides = crit.strides_as_floats()[:n_maps]
-        bi = batch["batch_idx"]
-        K = int(crit.kpt_shape[0])
-        kp = _gt_keypoints(batch, K, dev)
-        a = assign(maps, strides, crit.nc, bi, batch["cls"], batch["bboxes"], batch.get("n_max"), frozen=crit.frozen_assignment)
-        dm = ops.det_maps(maps, strides, crit.nc)
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)
-        call("dy_loss_fwd", C.byref(dm), ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label), ptr(a.target_box),
-             ptr(acc), st)
-        det = torch.empty(4, dtype=torch.float32, device=dev)
-        call("dy_loss_finish", ptr(acc), None, float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), 0.0, B, ptr(det[0:1]),
-             ptr(det[1:4]), st)
-        n_t, n_max = int(bi.numel()), max(a.n_max, 1)
-        bif = bi.to(dev, torch.float32).contiguous().view(-1)
-        rows = torch.empty((B, n_max), dtype=torch.int32, device=dev)
-        call("dy_seg_gt_rows", ptr(bif) if n_t else None, n_t, B, n_max, ptr(rows), st)
-        A = a.fg_mask.shape[1]
-        pos = torch.empty((B, A), dtype=torch.int32, device=dev)
-        npos = torch.empty(B, dtype=torch.int32, device=dev)
-        call("dy_seg_positives", ptr(a.fg_mask), B, A, ptr(pos), ptr(npos), st)
+        kp = _gt_keypoints(batch, int(crit.kpt_shape[0]), dev)
+        ctx.det, det = _det_forward(crit, batch, maps)
+        _, strides, a, _ = ctx.det
+        n_t, n_max, A = int(batch["batch_idx"].numel()), max(a.n_max, 1), a.fg_mask.shape[1]
+        rows, pos, npos = _positives(a, batch["batch_idx"], with_rows=True)
         d = ops.pose_desc(kpts, strides, crit.kpt_shape)
         d.target_gt_idx, d.fg_mask, d.target_box = ptr(a.target_gt_idx), ptr(a.fg_mask), ptr(a.target_box)
         d.keypoints, d.n_targets = (kp.data_ptr() if n_t else None), n_t
@@ -385,51 +360,36 @@ class _PoseLossFn(torch.autograd.Function):
         work = torch.empty(3 * B * A + 3 * B, dtype=torch.float32, device=dev)
         out = torch.empty(6, dtype=torch.float32, device=dev)
         call("dy_pose_loss_fwd", C.byref(d), float(crit.hyp.pose), float(crit.hyp.kobj), ptr(work), ptr(det), ptr(out), st)
-        ctx.crit, ctx.maps, ctx.assign, ctx.acc, ctx.strides = crit, maps, a, acc, strides
-        ctx.desc, ctx.keep = d, (kpts, kp, rows, pos, npos, sigma, work)
-        crit.last_assignment = a
+        ctx.crit, ctx.desc, ctx.keep = crit, d, (kpts, kp, rows, pos, npos, sigma, work)
         loss, items = out[0], out[1:6]
         ctx.mark_non_differentiable(items)
         return loss, items
 
     @staticmethod
     def backward(ctx, gloss, _gitems):
-        crit, maps, a = ctx.crit, ctx.maps, ctx.assign
-        dev, dt, st = maps[0].device, maps[0].dtype, stream()
-        ve = ops.vec_elems(dt)
-        dm = ops.det_maps(maps, ctx.strides, crit.nc)
-        width = 4 * REG_MAX + ops.round_up(crit.nc, ve)
-        dbufs = [ops.empty_nhwc(m.shape[0], width, m.shape[2], m.shape[3], dt, dev) for m in maps]
-        arr_p = (C.c_void_p * len(dbufs))(*[d.data_ptr() for d in dbufs])
-        arr_l = (C.c_int64 * len(dbufs))(*[ld_of(d) for d in dbufs])
-        g = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        call("dy_loss_bwd", C.byref(dm), arr_p, arr_l, ptr(a.pred_boxes), ptr(a.fg_mask), ptr(a.norm), ptr(a.target_label),
-             ptr(a.target_box), ptr(ctx.acc), ptr(g), float(crit.hyp.box), float(crit.hyp.cls), float(crit.hyp.dfl), st)
+        crit, st = ctx.crit, stream()
+        dmaps, g = _det_backward(crit, ctx.det, gloss)
         kpts, work = ctx.keep[0], ctx.keep[-1]
-        nk = kpts[0].shape[1]
-        nk_pad = ops.round_up(nk, ve)
+        nk, dt, dev = kpts[0].shape[1], kpts[0].dtype, kpts[0].device
+        nk_pad = ops.round_up(nk, ops.vec_elems(dt))
         dks = [ops.empty_nhwc(k.shape[0], nk_pad, k.shape[2], k.shape[3], dt, dev) for k in kpts]
         arr_k = (C.c_void_p * len(dks))(*[k.data_ptr() for k in dks])
         call("dy_pose_loss_bwd", C.byref(ctx.desc), ptr(work), ptr(g), float(crit.hyp.pose), float(crit.hyp.kobj), arr_k, nk_pad, st)
-        ops.emu_round(*dbufs, *dks)
-        no = 4 * REG_MAX + crit.nc
+        ops.emu_round(*dks)
         ctx.keep = None
-        return (None, None, None, *[d[:, :no] for d in dbufs], *[k[:, :nk] for k in dks])
+        return (None, None, None, *dmaps, *[k[:, :nk] for k in dks])
 
 
 class v8PoseLoss(v8DetectionLoss):
     """reference loss.py:292-377 (KeypointLoss :87-99): the detection terms (dy_loss_fwd / dy_loss_bwd on the HIP assignment) plus
     the keypoint location and visibility terms on csrc/pose.hip.  Returns (loss.sum() * B, items [box, pose, kobj, cls, dfl]);
-    `model.args` carries .box/.cls/.dfl/.pose/.kobj (cfg/default.yaml).  The OKS sigmas are OKS_SIGMA for kpt_shape [17, 3]
-    (compared as a list, as the yaml gives it), else ones(K) / K."""
+    `model.args` carries .box/.cls/.dfl/.pose/.kobj (cfg/default.yaml).  The OKS sigmas are metrics.oks_sigmas(kpt_shape)."""
 
     def __init__(self, model):
         super().__init__(model)
-        from .metrics import OKS_SIGMA
+        from .metrics import oks_sigmas
         self.kpt_shape = model.model[-1].kpt_shape
-        K = int(self.kpt_shape[0])
-        is_pose = [int(v) for v in self.kpt_shape] == [17, 3]
-        self.sigmas = torch.from_numpy(OKS_SIGMA).float() if is_pose else torch.ones(K) / K
+        self.sigmas = torch.from_numpy(oks_sigmas(self.kpt_shape)).float()
         self._sigmas_dev = None
 
     def sigmas_on(self, dev):

@@ -213,36 +213,41 @@ class DetMetrics:
         return dict(zip(self.keys + ["fitness"], self.box.mean_results() + [self.fitness]))
 
 
-class SegmentMetrics:
-    """Box and mask tables of the segment validator (reference SegmentMetrics, metrics.py:804-900): `.process(tp_b, tp_m, conf,
-    pred_cls, target_cls)`, keys `metrics/...(B)` then `metrics/...(M)`, fitness = box fitness + mask fitness."""
-    keys = DetMetrics.keys + ["metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP50-95(M)"]
+class _BoxAndTaskMetrics:
+    """Box table plus the task's own table (the mask table `.seg` or the keypoint table `.pose`; `second` names it):
+    `.process(tp_b, tp_2, conf, pred_cls, target_cls)`, keys `metrics/...(B)` then the task table's, fitness = the task table's
+    fitness + the box fitness."""
+    second = keys = None
 
     def __init__(self, save_dir=None, plot=False, on_plot=None, names=()):
         self.save_dir, self.plot, self.on_plot, self.names = save_dir, plot, on_plot, names
         self.box = BoxSummary()
-        self.seg = BoxSummary()
+        setattr(self, self.second, BoxSummary())
         self.speed = dict(preprocess=0.0, inference=0.0, loss=0.0, postprocess=0.0)
 
-    def process(self, tp_b, tp_m, conf, pred_cls, target_cls):
-        self.seg.nc = len(self.names)
-        self.seg.update(ap_per_class(tp_m, conf, pred_cls, target_cls, names=self.names)[2:])
+    @property
+    def _task(self):
+        return getattr(self, self.second)
+
+    def process(self, tp_b, tp_2, conf, pred_cls, target_cls):
+        self._task.nc = len(self.names)
+        self._task.update(ap_per_class(tp_2, conf, pred_cls, target_cls, names=self.names)[2:])
         self.box.nc = len(self.names)
         self.box.update(ap_per_class(tp_b, conf, pred_cls, target_cls, names=self.names)[2:])
 
     def mean_results(self):
-        return self.box.mean_results() + self.seg.mean_results()
+        return self.box.mean_results() + self._task.mean_results()
 
     def class_result(self, i):
-        return self.box.class_result(i) + self.seg.class_result(i)
+        return self.box.class_result(i) + self._task.class_result(i)
 
     @property
     def maps(self):
-        return self.box.maps + self.seg.maps
+        return self.box.maps + self._task.maps
 
     @property
     def fitness(self):
-        return self.seg.fitness() + self.box.fitness()
+        return self._task.fitness() + self.box.fitness()
 
     @property
     def ap_class_index(self):
@@ -253,7 +258,24 @@ class SegmentMetrics:
         return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))
 
 
+class SegmentMetrics(_BoxAndTaskMetrics):
+    """Box and mask tables of the segment validator (reference SegmentMetrics, metrics.py:804-900): `.box`, `.seg`, keys `(M)`."""
+    second, keys = "seg", DetMetrics.keys + [k.replace("(B)", "(M)") for k in DetMetrics.keys]
+
+
+class PoseMetrics(_BoxAndTaskMetrics):
+    """Box and pose tables of the pose validator (reference PoseMetrics, metrics.py:913-1015): `.box`, `.pose`, keys `(P)`."""
+    second, keys = "pose", DetMetrics.keys + [k.replace("(B)", "(P)") for k in DetMetrics.keys]
+
+
 OKS_SIGMA = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0   # metrics.py:15
+
+
+def oks_sigmas(kpt_shape):
+    """The OKS sigmas of a keypoint layout: OKS_SIGMA for kpt_shape [17, 3] (compared as a list, as the yaml gives it), else
+    ones(K) / K (reference loss.py:303-305, pose/val.py:54-57)."""
+    K = int(kpt_shape[0])
+    return OKS_SIGMA if [int(v) for v in kpt_shape] == [17, 3] else np.ones(K) / K
 
 
 def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
@@ -274,43 +296,3 @@ def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
     sg = torch.as_tensor(np.asarray(sigma), dtype=torch.float32).to(dev).reshape(K).contiguous()
     _C.call("dy_kpt_oks", ptr(g), N, ptr(q), M, q.shape[2], ptr(a), ptr(sg), K, float(eps), ptr(out), stream())
     return out
-
-
-class PoseMetrics:
-    """Box and pose tables of the pose validator (reference PoseMetrics, metrics.py:913-1015): `.process(tp_b, tp_p, conf,
-    pred_cls, target_cls)`, keys `metrics/...(B)` then `metrics/...(P)`, fitness = pose fitness + box fitness."""
-    keys = DetMetrics.keys + ["metrics/precision(P)", "metrics/recall(P)", "metrics/mAP50(P)", "metrics/mAP50-95(P)"]
-
-    def __init__(self, save_dir=None, plot=False, on_plot=None, names=()):
-        self.save_dir, self.plot, self.on_plot, self.names = save_dir, plot, on_plot, names
-        self.box = BoxSummary()
-        self.pose = BoxSummary()
-        self.speed = dict(preprocess=0.0, inference=0.0, loss=0.0, postprocess=0.0)
-
-    def process(self, tp_b, tp_p, conf, pred_cls, target_cls):
-        self.pose.nc = len(self.names)
-        self.pose.update(ap_per_class(tp_p, conf, pred_cls, target_cls, names=self.names)[2:])
-        self.box.nc = len(self.names)
-        self.box.update(ap_per_class(tp_b, conf, pred_cls, target_cls, names=self.names)[2:])
-
-    def mean_results(self):
-        return self.box.mean_results() + self.pose.mean_results()
-
-    def class_result(self, i):
-        return self.box.class_result(i) + self.pose.class_result(i)
-
-    @property
-    def maps(self):
-        return self.box.maps + self.pose.maps
-
-    @property
-    def fitness(self):
-        return self.pose.fitness() + self.box.fitness()
-
-    @property
-    def ap_class_index(self):
-        return self.box.ap_class_index
-
-    @property
-    def results_dict(self):
-        return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))

@@ -348,3 +348,29 @@ def test_match_predictions_equals_the_references_sort_unique_formulation():
         det = torch.tensor(np.concatenate((dc - ds / 2, dc + ds / 2, g.random((nd, 1)), g.integers(0, 3, (nd, 1))), 1), dtype=torch.float32).reshape(nd, 6)
         a, b = match_predictions(det, lab, iouv), oval.match_predictions(det, lab, iouv)
         assert torch.equal(a, b), trial
+
+
+def test_task_table_guess_and_checkpoint_class_agree_for_every_model_yaml():
+    """For every yaml under cfg/models/v8 (built at scale n): the task guessed from the yaml, the task guessed from the model that
+    the task table builds for it, the table's head class and the class name the reference-format checkpoint writer gives it agree."""
+    from dedark_yolo_amd.nn.tasks import guess_model_task, task_table, yaml_model_load
+    from dedark_yolo_amd.utils.checkpoint import model_class_name
+    cfg_dir = os.path.join(ROOT, "dedark_yolo_amd", "cfg", "models", "v8")
+    names = sorted(f for f in os.listdir(cfg_dir) if f.endswith(".yaml"))
+    assert names
+    table = task_table()
+    assert list(table) == ["segment", "pose", "detect"]
+    seen = set()
+    for name in names:
+        stem, ext = os.path.splitext(name)
+        d = yaml_model_load(stem.replace("yolov8", "yolov8n", 1) + ext)
+        task = guess_model_task(d)
+        model_cls, head_cls, validator_cls = table[task]
+        model = model_cls(d)
+        assert guess_model_task(model) == task, name
+        assert isinstance(model.model[-1], head_cls), name
+        assert not any(isinstance(model.model[-1], h) for t, (_, h, _) in table.items() if t != "detect" and t != task), name
+        assert model_class_name(model) == model_cls.__name__, name
+        assert validator_cls.__name__ == model_cls.__name__.replace("Model", "Validator"), name
+        seen.add(task)
+    assert seen == {"segment", "pose", "detect"}

@@ -1,0 +1,94 @@
+"""Training throughput of a segment or pose model (yolov8l-seg / yolov8l-pose by default) on synthetic batches: bench.py's batch
+law plus the task's labels -- overlap index masks at the proto resolution (imgsz / 4), or 17 keypoints per box (normalised xy
+around the box centre, visibility 0 / 1 / 2) -- one train_step per iteration (preprocess + forward + detection and task loss +
+backward + optimizer), timed with device events after a warm-up.  Prints one JSON line.
+
+  python tools/task_bench.py --task {segment,pose} [--model yolov8l-seg.yaml | yolov8l-pose.yaml] [--imgsz 640] [--batch 32]
+                             [--dtype bf16] [--steps 10 | 15] [--warmup 3] [--deterministic] [--dump-outputs DIR]
+
+`--deterministic` trains on the one-stream schedule (two runs of one build then give the same bits); `--dump-outputs DIR` writes
+what the last timed step computed as DIR/*.npy (bench.dump_outputs), to compare two builds output for output.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def add_masks(b, i, B, S):
+    import torch
+    h = w = S // 4
+    m = torch.zeros((B, h, w), dtype=torch.uint8)
+    k = [0] * B
+    for bi, (cx, cy, bw, bh) in zip(b["batch_idx"].long().tolist(), b["bboxes"].tolist()):
+        k[bi] += 1
+        m[bi, max(int((cy - bh / 2) * h), 0):int((cy + bh / 2) * h), max(int((cx - bw / 2) * w), 0):int((cx + bw / 2) * w)] = k[bi]
+    b["masks"] = m.cuda()
+
+
+def add_keypoints(b, i, B, S, K=17):
+    import numpy as np
+    import torch
+    g = np.random.default_rng(200 + i)
+    n = b["bboxes"].shape[0]
+    wh = b["bboxes"][:, None, 2:].numpy()
+    xy = b["bboxes"][:, None, :2].numpy() + g.uniform(-0.5, 0.5, (n, K, 2)) * wh
+    v = g.integers(0, 3, (n, K, 1))
+    b["keypoints"] = torch.from_numpy(np.concatenate([xy, v], 2).astype(np.float32))
+
+
+# task -> (default model, default timed steps, what adds the task's labels to a batch, model class in nn.tasks)
+TASKS = dict(segment=("yolov8l-seg.yaml", 10, add_masks, "SegmentationModel"), pose=("yolov8l-pose.yaml", 15, add_keypoints, "PoseModel"))
+
+
+def main():
+    import torch
+    import bench
+    from dedark_yolo_amd.engine.trainer import DetectionTrainer, get_cfg
+    from dedark_yolo_amd.nn import tasks
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--task", choices=sorted(TASKS), required=True)
+    ap.add_argument("--model")
+    ap.add_argument("--imgsz", type=int, default=640)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--steps", type=int)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--deterministic", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR")
+    a = ap.parse_args()
+    model, steps, add_labels, model_cls = TASKS[a.task]
+    model, steps = a.model or model, a.steps or steps
+    nc, S, B = 20, a.imgsz, a.batch
+    torch.manual_seed(0)          # the initial weights: with the seeded batches, two runs start from the same state
+    tr = DetectionTrainer(get_cfg(dict(model=model, dtype=a.dtype, optimizer="SGD", batch=B, imgsz=S, deterministic=a.deterministic)))
+    tr.setup(getattr(tasks, model_cls)(tasks.yaml_model_load(model), nc=nc))
+    batches = []
+    for i in range(4):
+        b = bench.synth_batch(100 + i, B, S, nc, "cpu")
+        b.pop("gamma")
+        add_labels(b, i, B, S)
+        b["img"] = b["img"].cuda()
+        batches.append(b)
+    for i in range(a.warmup):
+        tr.train_step(dict(batches[i % 4]), [0.01] * 3, 0.9)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(steps):
+        loss, items = tr.train_step(dict(batches[i % 4]), [0.01] * 3, 0.9)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / steps
+    if a.dump_outputs:
+        bench.dump_outputs(a.dump_outputs, tr, loss, items)
+    print(json.dumps(dict(metric=f"{a.task} training img/s", model=model, imgsz=S, batch=B, dtype=a.dtype, steps=steps,
+                          warmup=a.warmup, ms_per_step=round(ms, 3), value=round(B * 1000.0 / ms, 2),
+                          items=[round(float(v), 4) for v in items])))
+
+
+if __name__ == "__main__":
+    main()
