@@ -159,6 +159,9 @@ _SIGS = {
     "dy_seg_mask_decode": [vp, i64, i32, i32, i32, vp, i64, vp, i32, f32, f32, i32, vp, vp],
     "dy_seg_crop_mask": [vp, vp, i32, i32, i32, vp],
     "dy_seg_mask_iou": [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp],
+    "dy_seg_mask_upsample": [vp, i64, i32, i32, i32, i32, vp, i64, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, i32, i32, i32,
+                             vp, vp],
+    "dy_mask_resize": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp],
     "dy_pose_loss_fwd": [C.POINTER(PoseDesc), f32, f32, vp, vp, vp, vp],
     "dy_pose_loss_bwd": [C.POINTER(PoseDesc), vp, vp, f32, f32, C.POINTER(vp), i64, vp],
     "dy_pose_kpt_decode": [C.POINTER(PoseDesc), i32, vp, vp],

@@ -22,6 +22,29 @@ def _resolve_task(task, d):
     return task or head
 
 
+def segment_postprocess(dets, proto, input_shape, orig_shapes=None, retina_masks=False, names=None):
+    """SegmentationPredictor.postprocess after its NMS (reference models/yolo/segment/predict.py:25-44): dets = one [n_i, 6 + nm]
+    tensor per image (non_max_suppression), proto [B, nm, mh, mw], input_shape = the network input (h, w) -> one `Results` per image.
+    retina_masks=False: masks at the input resolution (process_mask, upsample=True), then the boxes scaled to orig_shapes[i];
+    retina_masks=True: the boxes scaled first, then masks at orig_shapes[i] (process_mask_native).  The masks of the whole batch come
+    from one process_masks_batched call (one launch per distinct output shape); an image without detections has masks None.
+    `Masks.data` is f32 0 / 1 like the reference's; the uint8 planes the kernel writes are converted last."""
+    from ..utils import ops as uops
+    from .results import Results
+    H, W = int(input_shape[0]), int(input_shape[1])
+    shapes = [tuple(int(v) for v in s[:2]) for s in orig_shapes] if orig_shapes is not None else [(H, W)] * len(dets)
+    dets = [d.clone() for d in dets]
+    if retina_masks:
+        for d, shape in zip(dets, shapes):
+            uops.scale_boxes((H, W), d[:, :4], shape)
+        masks = uops.process_masks_batched(proto, dets, (H, W), mode="native", out_shapes=shapes)
+    else:
+        masks = uops.process_masks_batched(proto, dets, (H, W), mode="input")
+        for d, shape in zip(dets, shapes):
+            uops.scale_boxes((H, W), d[:, :4], shape)
+    return [Results(shape, d[:, :6], names=names, masks=m.float() if len(d) else None) for d, m, shape in zip(dets, masks, shapes)]
+
+
 class YOLO:
     def __init__(self, model="yolov8l.yaml", task=None):
         if task not in (None, "detect", "segment", "pose"):
@@ -96,16 +119,15 @@ class YOLO:
         return task_table()[self.task][2](get_cfg(ov))(self.model, loader)
 
     @torch.no_grad()
-    def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, **kw):
+    def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, **kw):
         """reference engine/predictor.py stream_inference + DetectionPredictor.postprocess (models/yolo/detect/predict.py:12-38)
         for an already letter-boxed batch: `source` is a uint8 [B,3,H,W] RGB tensor (or float in [0,1]); returns one `Results`
-        per image with boxes scaled back to `orig_shapes[i]` (default: the network input shape).  Image decoding / letter-boxing
-        (cv2) is outside the hot path."""
+        per image with boxes scaled back to `orig_shapes[i]` (default: the network input shape).  A segment model also fills
+        `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Image decoding / letter-boxing (cv2), plotting
+        and the mask contours (`Masks.xy`) are outside the hot path."""
         from ..utils import ops as uops
         from .results import Results
         from .validator import DetectionValidator
-        if self.task == "segment":
-            raise NotImplementedError("predict() of a segment model: mask outputs (process_mask_upsample) are not implemented")
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("predict() needs the model on a GPU (there is no CPU path)")
@@ -118,6 +140,15 @@ class YOLO:
         else:
             img = source.to(dev).float()
         preds = self.model(img)
+        if self.task == "segment":                            # models/yolo/segment/predict.py:16-26
+            dets = uops.non_max_suppression(preds[0], conf, iou, agnostic=agnostic_nms, max_det=max_det, nc=len(self.model.names))
+            proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]
+            if retina_masks is None:
+                retina_masks = bool(getattr(get_cfg(dict(self.overrides)), "retina_masks", False))
+            out = segment_postprocess([d[:, :6 + proto.shape[1]] for d in dets], proto, img.shape[2:], orig_shapes, retina_masks,
+                                      self.model.names)
+            self.model.train(was_training)
+            return out
         pose = self.task == "pose"
         nc = self.model.model[-1].nc if pose else 0
         dets = uops.non_max_suppression(preds, conf, iou, agnostic=agnostic_nms, max_det=max_det, nc=nc)

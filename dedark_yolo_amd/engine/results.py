@@ -1,6 +1,7 @@
 """Minimal prediction containers with the attribute surface of the reference's ultralytics/engine/results.py:
 `Results.boxes` -> `Boxes` with `.data` ([n,6] xyxy, conf, cls), `.xyxy`, `.conf`, `.cls`, `.xywh`, `.xyxyn`, `len()`; `Results`
-also carries `orig_shape`, `names` and, for a pose model, `keypoints` -> `Keypoints` (`.data`, `.xy`, `.xyn`, `.conf`).  Plotting / saving helpers are outside the hot path."""
+also carries `orig_shape`, `names`, for a pose model `keypoints` -> `Keypoints` (`.data`, `.xy`, `.xyn`, `.conf`) and for a segment
+model `masks` -> `Masks` (`.data`).  Plotting / saving helpers and the mask contours (`Masks.xy` / `.xyn`) are outside the hot path."""
 import torch
 
 from ..utils import ops
@@ -75,11 +76,42 @@ class Keypoints:
         return self.data.shape[0]
 
 
+class Masks:
+    """reference engine/results.py:464-518: data [n, h, w] of 0 / 1 (f32, as process_mask returns it), `orig_shape`, `len()`,
+    `.cpu()`; a single [h, w] mask gains the leading axis.  `.xy` / `.xyn` (the reference's masks2segments contours) need
+    cv2.findContours and are not implemented."""
+
+    def __init__(self, masks, orig_shape):
+        if masks.ndim == 2:
+            masks = masks[None, :]
+        self.data = masks
+        self.orig_shape = tuple(orig_shape)
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        raise NotImplementedError("Masks.xy: mask contours need cv2.findContours (masks2segments), which is outside the hot path")
+
+    @property
+    def xyn(self):
+        raise NotImplementedError("Masks.xyn: mask contours need cv2.findContours (masks2segments), which is outside the hot path")
+
+    def cpu(self):
+        return Masks(self.data.cpu(), self.orig_shape)
+
+    def __len__(self):
+        return self.data.shape[0]
+
+
 class Results:
-    def __init__(self, orig_shape, boxes, names=None, path=None, keypoints=None):
+    def __init__(self, orig_shape, boxes, names=None, path=None, keypoints=None, masks=None):
         self.orig_shape = tuple(orig_shape)
         self.boxes = Boxes(boxes, self.orig_shape)
         self.keypoints = Keypoints(keypoints, self.orig_shape) if keypoints is not None else None
+        self.masks = Masks(masks, self.orig_shape) if masks is not None else None
         self.names = names
         self.path = path
 

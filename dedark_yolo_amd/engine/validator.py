@@ -163,10 +163,13 @@ class DetectionValidator:
 
 
 class SegmentationValidator(DetectionValidator):
-    """Segment validator (reference models/yolo/segment/val.py): NMS with the mask-coefficient columns, masks decoded at the
-    proto resolution (process_mask, upsample=False; dy_seg_mask_decode), mask IoU against the gt masks with integer counts
-    (dy_seg_mask_iou), box and mask `correct` matrices by the same matching rule, SegmentMetrics.  The gt masks must be at the
-    proto resolution (the reference's bilinear resize of other sizes is not implemented)."""
+    """Segment validator (reference models/yolo/segment/val.py): NMS with the mask-coefficient columns, predicted masks of the whole
+    batch in one launch, mask IoU against the gt masks with integer counts (dy_seg_mask_iou), box and mask `correct` matrices by
+    the same matching rule, SegmentMetrics.  `process` as in init_metrics (val.py:31-39): save_json False -> process_mask at the
+    proto resolution (dy_seg_mask_decode), save_json True -> process_mask_upsample at the input resolution
+    (dy_seg_mask_upsample).  gt masks (index maps or planes) at another resolution than the predicted masks are resized
+    bilinearly and thresholded at 0.5 (val.py:146-148; dy_mask_resize).  Writing predictions.json itself (RLE through pycocotools,
+    scale_image through cv2) is out of scope: save_json only selects the masks that are evaluated."""
 
     n_task = 1
 
@@ -182,17 +185,18 @@ class SegmentationValidator(DetectionValidator):
     def update_metrics(self, preds, batch):
         dets, proto = preds
         height, width = batch["img"].shape[2:]
-        pmasks = ops.process_masks_batched(proto, [d[:, :6 + proto.shape[1]] for d in dets], (height, width))
-        masks = batch["masks"]
-        if tuple(masks.shape[-2:]) != tuple(proto.shape[2:]):
-            raise NotImplementedError(f"segment validation: gt masks {tuple(masks.shape[-2:])} are not at the proto resolution "
-                                      f"{tuple(proto.shape[2:])} (the bilinear path is not implemented)")
-        super().update_metrics(dets, dict(batch, masks=masks.to(self.device, non_blocking=True), pmasks=pmasks))
+        mode = "upsample" if getattr(self.args, "save_json", False) else "proto"
+        pmasks = ops.process_masks_batched(proto, [d[:, :6 + proto.shape[1]] for d in dets], (height, width), mode=mode)
+        super().update_metrics(dets, dict(batch, masks=batch["masks"].to(self.device, non_blocking=True), pmasks=pmasks))
 
     def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
         overlap, masks = bool(getattr(self.args, "overlap_mask", True)), batch["masks"]
         gt = masks[si] if overlap else masks[idx.to(masks.device)]
-        iou_m = ops.mask_iou_binary(gt, batch["pmasks"][si], overlap, labelsn.shape[0]).cpu().numpy()
+        pred, m = batch["pmasks"][si], labelsn.shape[0]
+        if tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]) and m:
+            gt = ops.resize_masks(gt, pred.shape[-2:], m=m if overlap else None)       # -> uint8 planes [m, h, w]
+            overlap = False
+        iou_m = ops.mask_iou_binary(gt, pred, overlap, m).cpu().numpy()
         return (match_from_iou(iou_m, labelsn[:, 0], predn[:, 5], self.iouv),)
 
 

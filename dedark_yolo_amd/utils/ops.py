@@ -1,5 +1,7 @@
-"""Box utilities and batched NMS with the call surface of the reference's ultralytics/utils/ops.py
-(xywh2xyxy :374-389, xyxy2xywh :357-371, clip_boxes :281-297, scale_boxes :95-125, non_max_suppression :144-278).
+"""Box and mask utilities and batched NMS with the call surface of the reference's ultralytics/utils/ops.py
+(xywh2xyxy :374-389, xyxy2xywh :357-371, clip_boxes :281-297, scale_boxes :95-125, non_max_suppression :144-278, crop_mask :553-569,
+process_mask / process_mask_upsample / process_mask_native :572-642, scale_masks :645-666).  Not here: scale_image (:319-354, a
+cv2.resize on the host) and masks2segments (:704-727, cv2.findContours).
 
 non_max_suppression runs the whole batch in three HIP launches (candidate keys -> segmented radix sort -> greedy scan,
 csrc/nms.hip) instead of the reference's per-image Python loop around torchvision.ops.nms; there is no CPU fallback."""
@@ -165,39 +167,157 @@ def crop_mask(masks, boxes):
     return out
 
 
-def process_masks_batched(protos, dets, shape):
-    """process_mask for every image of a batch in one launch.  protos [B, nm, mh, mw] NHWC (any compute dtype), dets: one
-    [n_i, 6+nm] tensor per image (non_max_suppression) -> one uint8 [n_i, mh, mw] tensor per image."""
+MASK_MODES = ("proto", "input", "upsample", "native")
+
+
+def scale_masks_window(mh, mw, shape, padding=True):
+    """(top, left, bottom, right) of the rows / columns of an mh x mw mask that scale_masks keeps before it resizes to `shape`
+    (reference ops.py:655-663: gain = old / new, the letterbox padding halved and truncated with int())."""
+    gain = min(mh / shape[0], mw / shape[1])
+    pad = [mw - shape[1] * gain, mh - shape[0] * gain]
+    if padding:
+        pad[0] /= 2
+        pad[1] /= 2
+    top, left = (int(pad[1]), int(pad[0])) if padding else (0, 0)
+    bottom, right = int(mh - pad[1]), int(mw - pad[0])
+    return top, left, bottom, right
+
+
+def _det_chunk(n_groups, max_group, oh, ow):
+    """Detections one workgroup of dy_seg_mask_upsample walks: as many as keep about 2048 workgroups in flight, at least 8 (the proto
+    tile it loads is then shared by that many detections)."""
+    tiles = ((oh + 63) // 64) * ((ow + 63) // 64) * n_groups
+    nsplit = max(1, min(max_group, -(-2048 // tiles)))
+    return max(-(-max_group // nsplit), min(8, max_group))
+
+
+def process_masks_batched(protos, dets, shape, mode="proto", out_shapes=None):
+    """The masks of every image of a batch, uint8.  protos [B, nm, mh, mw] NHWC (any compute dtype), dets: one [n_i, 6+nm] tensor
+    per image (non_max_suppression), shape = the network input (h, w) -> one uint8 [n_i, oh, ow] tensor per image.  mode:
+      "proto"     process_mask(upsample=False): masks at the proto resolution (dy_seg_mask_decode, one launch);
+      "input"     process_mask(upsample=True): crop at the proto resolution, bilinear resize to `shape`;
+      "upsample"  process_mask_upsample: bilinear resize to `shape`, then crop;
+      "native"    process_mask_native: scale_masks' padding crop, bilinear resize to out_shapes[i] (the original image), crop by the
+                  boxes, which the caller has already scaled to that image.
+    The three image-resolution modes run dy_seg_mask_upsample: one launch for the images whose output shape agrees (always one for
+    "input" / "upsample"), the f32 [n, h, w] planes of the reference never exist."""
     from .. import ops as kops
+    if mode not in MASK_MODES:
+        raise ValueError(f"process_masks_batched: mode '{mode}' is not one of {MASK_MODES}")
     B, nm, mh, mw = protos.shape
-    ih, iw = shape
     p = kops.as_nhwc(protos, protos.dtype)
     dev = p.device
     ns = [int(d.shape[0]) for d in dets]
     n = sum(ns)
-    out = torch.empty((n, mh, mw), dtype=torch.uint8, device=dev)
-    if n:
-        det = torch.cat([d.float() for d in dets], 0).contiguous()
-        img = torch.cat([torch.full((k,), i, dtype=torch.int32, device=dev) for i, k in enumerate(ns)])
-        call("dy_seg_mask_decode", ptr(p), kops.ld_of(p), nm, mh, mw, ptr(det), det.shape[1], ptr(img), n, float(mw / iw), float(mh / ih),
-             kops.dt_id(p.dtype), ptr(out), stream())
-    return list(out.split(ns, 0))
+    if mode == "proto":
+        ih, iw = shape
+        out = torch.empty((n, mh, mw), dtype=torch.uint8, device=dev)
+        if n:
+            det = torch.cat([d.float() for d in dets], 0).contiguous()
+            img = torch.cat([torch.full((k,), i, dtype=torch.int32, device=dev) for i, k in enumerate(ns)])
+            call("dy_seg_mask_decode", ptr(p), kops.ld_of(p), nm, mh, mw, ptr(det), det.shape[1], ptr(img), n, float(mw / iw), float(mh / ih),
+                 kops.dt_id(p.dtype), ptr(out), stream())
+        return list(out.split(ns, 0))
+    if mode == "native":
+        if out_shapes is None or len(out_shapes) != len(dets):
+            raise ValueError("process_masks_batched(mode='native') needs out_shapes: one original (h, w) per image")
+        shapes = [(int(s[0]), int(s[1])) for s in out_shapes]
+    else:
+        shapes = [(int(shape[0]), int(shape[1]))] * len(dets)
+    res = [None] * len(dets)
+    for hw in dict.fromkeys(shapes):                      # distinct output shapes, in order of appearance
+        oh, ow = hw
+        ids = [i for i, s in enumerate(shapes) if s == hw]
+        live = [i for i in ids if ns[i]]
+        cnt = [ns[i] for i in live]
+        out = torch.empty((sum(cnt), oh, ow), dtype=torch.uint8, device=dev)
+        if live:
+            det = torch.cat([dets[i].float() for i in live], 0).contiguous()
+            off = [0]
+            for k in cnt:
+                off.append(off[-1] + k)
+            meta = torch.tensor(off + live, dtype=torch.int32, device=dev)
+            if mode == "native":
+                top, left, bottom, right = scale_masks_window(mh, mw, hw)
+            else:
+                top, left, bottom, right = 0, 0, mh, mw
+            before = mode == "input"
+            call("dy_seg_mask_upsample", ptr(p), kops.ld_of(p), nm, mh, mw, kops.dt_id(p.dtype), ptr(det), det.shape[1], ptr(meta),
+                 ptr(meta[len(off):]), len(live), max(cnt), _det_chunk(len(live), max(cnt), oh, ow), int(before),
+                 float(mw / shape[1]) if before else 1.0, float(mh / shape[0]) if before else 1.0, top, left, bottom, right, oh, ow,
+                 int(not before), ptr(out), stream())
+        parts = dict(zip(live, out.split(cnt, 0)))
+        for i in ids:
+            res[i] = parts[i] if i in parts else out[:0]
+    return res
 
 
-def process_mask(protos, masks_in, bboxes, shape, upsample=False):
-    """Reference signature (ops.py:593-623): protos [nm, mh, mw], masks_in [n, nm], bboxes [n, 4] xyxy at the input size `shape`
-    -> [n, mh, mw] f32 of 0 / 1 (sigmoid(c . P) > 0.5 inside the box scaled to the proto grid).  upsample=True (the bilinear
-    resize to the input size) is not implemented."""
-    if upsample:
-        raise NotImplementedError("process_mask(upsample=True): the bilinear upsampling path is not implemented")
+def _one_image(protos, masks_in, bboxes, shape, mode, out_shape=None):
     if not protos.is_cuda:
-        raise RuntimeError("process_mask needs device tensors (there is no CPU path)")
+        raise RuntimeError(f"process_mask ({mode}) needs device tensors (there is no CPU path)")
     n = masks_in.shape[0]
     det = torch.zeros((n, 6 + masks_in.shape[1]), dtype=torch.float32, device=protos.device)
     det[:, :4] = bboxes.float()
     det[:, 6:] = masks_in.float()
     p = protos.float().unsqueeze(0).contiguous(memory_format=torch.channels_last)
-    return process_masks_batched(p, [det], shape)[0].float()
+    return process_masks_batched(p, [det], shape, mode=mode, out_shapes=None if out_shape is None else [out_shape])[0].float()
+
+
+def process_mask(protos, masks_in, bboxes, shape, upsample=False):
+    """Reference signature (ops.py:593-623): protos [nm, mh, mw], masks_in [n, nm], bboxes [n, 4] xyxy at the input size `shape`
+    -> f32 of 0 / 1: sigmoid(c . P) cropped to the box scaled to the proto grid, then [n, mh, mw] thresholded at 0.5
+    (upsample=False) or resized bilinearly to [n, *shape] and thresholded (upsample=True, dy_seg_mask_upsample)."""
+    return _one_image(protos, masks_in, bboxes, shape, "input" if upsample else "proto")
+
+
+def process_mask_upsample(protos, masks_in, bboxes, shape):
+    """Reference signature (ops.py:572-590): sigmoid(c . P) resized bilinearly to `shape`, cropped to the boxes there, > 0.5
+    -> [n, *shape] f32 of 0 / 1."""
+    return _one_image(protos, masks_in, bboxes, shape, "upsample")
+
+
+def process_mask_native(protos, masks_in, bboxes, shape):
+    """Reference signature (ops.py:625-642): `shape` is the ORIGINAL image's (h, w) and bboxes are in its pixels; sigmoid(c . P)
+    through scale_masks (letterbox padding removed, bilinear resize to `shape`), cropped, > 0.5 -> [n, *shape] f32 of 0 / 1."""
+    return _one_image(protos, masks_in, bboxes, shape, "native", out_shape=shape)
+
+
+def resize_masks(src, shape, m=None, window=None, binary=True):
+    """Bilinear resize (align_corners=False) of mask planes on the device (dy_mask_resize).  src: uint8 / f32 planes [m, h, w], or
+    with `m` given one index map [h, w] (uint8 / int32; plane k = (map == k + 1), the reference's torch.where(gt == index, 1.0, 0.0),
+    segment/val.py:143-145).  window = (top, left, bottom, right) rows / columns of the source to resize (default: all).
+    binary -> uint8 [m, *shape] of value > 0.5 (strict, like gt_(0.5)), else the f32 values."""
+    if not src.is_cuda:
+        raise RuntimeError("resize_masks needs device tensors (there is no CPU path)")
+    if m is None:
+        if src.dtype not in (torch.uint8, torch.float32):
+            src = src.to(torch.float32 if src.is_floating_point() else torch.uint8)
+        kind, planes = (0 if src.dtype == torch.uint8 else 3), int(src.shape[0])
+    else:
+        if src.dim() == 3 and src.shape[0] == 1:
+            src = src[0]
+        if src.dim() != 2:
+            raise ValueError("resize_masks: an index map is [h, w]")
+        if src.dtype not in (torch.uint8, torch.int32):
+            src = src.to(torch.int32)
+        kind, planes = (1 if src.dtype == torch.uint8 else 2), int(m)
+    src = src.contiguous()
+    h, w = int(src.shape[-2]), int(src.shape[-1])
+    top, left, bottom, right = window if window is not None else (0, 0, h, w)
+    oh, ow = int(shape[0]), int(shape[1])
+    out = torch.empty((planes, oh, ow), dtype=torch.uint8 if binary else torch.float32, device=src.device)
+    call("dy_mask_resize", ptr(src), kind, planes, h, w, int(top), int(left), int(bottom), int(right), ptr(out), int(not binary), oh, ow,
+         stream())
+    return out
+
+
+def scale_masks(masks, shape, padding=True):
+    """Reference signature (ops.py:645-666): masks [N, C, h, w] f32 -> [N, C, *shape] f32: the letterbox padding cropped
+    (scale_masks_window), then a bilinear resize (dy_mask_resize)."""
+    N, Cn, mh, mw = masks.shape
+    win = scale_masks_window(mh, mw, shape, padding)
+    out = resize_masks(masks.float().reshape(N * Cn, mh, mw), shape, window=win, binary=False)
+    return out.view(N, Cn, int(shape[0]), int(shape[1]))
 
 
 def mask_iou_binary(gt, pred, overlap, m):

@@ -483,6 +483,30 @@ int dy_seg_crop_mask(float* masks, const float* boxes, int n, int h, int w, void
 int dy_seg_mask_iou(const uint8_t* pred, int n, const void* gt, int gt_dtype, int overlap, int m, int64_t hw, int32_t* work,
                     float* iou, void* stream);
 
+/* ---- segment inference at image resolution (csrc/segmask.hip) -------------------------------------------------------------------------
+ * Fused process_mask(upsample=True) / process_mask_upsample / process_mask_native (U/utils/ops.py:593-623, 572-590, 625-642 with
+ * scale_masks :645-666 and crop_mask :553-569): per detection j of image b
+ *   s = sigmoid(c_j . P_b) at the proto resolution in f32; crop_before: s = 0 outside box_j * (sx, sy) (x1 <= col < x2);
+ *   window rows [top, bottom), columns [left, right) of the proto plane (scale_masks' padding crop; the whole plane = 0, 0, mh, mw);
+ *   bilinear resize of the window to (oh, ow) as F.interpolate(mode='bilinear', align_corners=False) does it: scale = in / out in f32,
+ *   src = scale * (dst + 0.5) - 0.5 clamped at 0, upper tap clamped to the window, wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d);
+ *   crop_after: 0 outside box_j as given (output pixels); out[j][oh][ow] = value > 0.5.
+ * No f32 plane reaches memory.  det rows (x1, y1, x2, y2, conf, cls, c_0 .. c_31) at stride det_ld, grouped by image: the rows of group g
+ * are img_off[g] .. img_off[g + 1] - 1 and belong to proto image img_ids[g] (n_groups groups, img_off [n_groups + 1]).  det_chunk > 0:
+ * detections one workgroup walks with its proto tile resident (the groups are split into ceil(max_group / det_chunk) chunks, max_group =
+ * the largest group).  proto NHWC [B][mh][mw][proto_ld] in `dtype`.  The resize may scale down by at most about 10 in either axis. */
+int dy_seg_mask_upsample(const void* proto, int64_t proto_ld, int nm, int mh, int mw, int dtype, const float* det, int64_t det_ld,
+                         const int32_t* img_off, const int32_t* img_ids, int n_groups, int max_group, int det_chunk, int crop_before,
+                         float sx, float sy, int top, int left, int bottom, int right, int oh, int ow, int crop_after, uint8_t* out,
+                         void* stream);
+/* Bilinear resize (align_corners=False, the arithmetic above) of m mask planes: the gt side of SegmentationValidator._process_batch
+ * (U/models/yolo/segment/val.py:140-148: torch.where(gt == k + 1, 1.0, 0.0), F.interpolate(..., mode='bilinear'), gt_(0.5)) and the body
+ * of scale_masks (U/utils/ops.py:645-666).  src_kind 0: uint8 planes [m][h][w]; 1 / 2: one uint8 / int32 index map [h][w], plane k = (map
+ * == k + 1); 3: f32 planes [m][h][w].  Source window rows [top, bottom), columns [left, right).  out_f32 == 0: uint8 [m][oh][ow] of value
+ * > 0.5 (strict), else the f32 value. */
+int dy_mask_resize(const void* src, int src_kind, int m, int h, int w, int top, int left, int bottom, int right, void* out, int out_f32,
+                   int oh, int ow, void* stream);
+
 /* ---- pose task (csrc/pose.hip) ------------------------------------------------------------------------------------------------------
  * Keypoint terms of v8PoseLoss / KeypointLoss (U/utils/loss.py:87-99, 292-377) on the assignment of dy_tal_assign, Pose.kpts_decode
  * (U/nn/modules/head.py:221-241) and kpt_iou (U/utils/metrics.py:150-169).  Fixed-order sums, no float atomics, no host
