@@ -45,7 +45,13 @@ __device__ __noinline__ float adj_edge(const float* line, int pitch, int m, int 
     c += c_taps[m] * line[(0 - o0 + R) * pitch];
   }
   if (m == n - 1) {
-    for (int i = 1; i <= R; ++i) c -= c_taps[i] * line[(n - 1 - i - o0 + R) * pitch];
+    // `line` is a generic pointer into LDS and these become flat loads `base + immediate`.  Written as
+    // line[(n - 1 - i - o0 + R) * pitch] the compiler took base = line + (n - 1 - o0 - R) * pitch with immediates up to
+    // R * pitch: a base BELOW the array -- below the LDS aperture for tileT, which starts the block's LDS -- whenever the last
+    // sample lies within R of its tile's origin (W = 65, 70, 76 ...), and the flat load then faults although base + immediate
+    // is in range.  q is the first sample read, never before `line` (the edge sample n - 1 belongs to this tile: n - 1 >= o0).
+    const float* q = line + (n - 1 - o0) * pitch;
+    for (int i = 1; i <= R; ++i) c -= c_taps[i] * q[(R - i) * pitch];
   } else if (m >= n - 1 - R && m <= n - 2) {
     c += c_taps[n - 1 - m] * line[(n - 1 - o0 + R) * pitch];
   }
