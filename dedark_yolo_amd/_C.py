@@ -166,6 +166,8 @@ _SIGS = {
     "dy_pose_loss_bwd": [C.POINTER(PoseDesc), vp, vp, f32, f32, C.POINTER(vp), i64, vp],
     "dy_pose_kpt_decode": [C.POINTER(PoseDesc), i32, vp, vp],
     "dy_kpt_oks": [vp, i32, vp, i32, i32, vp, vp, i32, f32, vp, vp],
+    "dy_polymask_raster": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
+    "dy_polymask_compose": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
 }
 
 _lib = None

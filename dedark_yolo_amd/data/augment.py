@@ -192,13 +192,105 @@ def _candidates(box1, box2, wh_thr=2, ar_thr=100, area_thr=0.1, eps=1e-16):
     return (w2 > wh_thr) & (h2 > wh_thr) & (w2 * h2 / (w1 * h1 + eps) > area_thr) & (ar < ar_thr)
 
 
-def train_labels(plan, labels, shapes):
+N_RESAMPLE = 1000                                             # points per polygon (resample_segments' default n)
+
+
+def resample_segments(segments, n=N_RESAMPLE):
+    """resample_segments (utils/ops.py:533-550) of a list of [k_i, 2] polygons: the closing point is appended and both coordinates are
+    interpolated (np.interp, float64) at n equidistant parameters, result float32 [len, n, 2].  Instances.__init__ does this to the
+    raw polygons of a label (utils/instance.py:200-204)."""
+    out = np.zeros((len(segments), n, 2), dtype=F32)
+    for i, sg in enumerate(segments):
+        sg = np.asarray(sg).reshape(-1, 2)
+        sg = np.concatenate((sg, sg[0:1, :]), axis=0)
+        x, xp = np.linspace(0, len(sg) - 1, n), np.arange(len(sg))
+        out[i] = np.concatenate([np.interp(x, xp, sg[:, k]) for k in range(2)], dtype=F32).reshape(2, -1).T
+    return out
+
+
+_RS_T = np.linspace(0, N_RESAMPLE, N_RESAMPLE) - np.arange(N_RESAMPLE)      # parameter i lies in interval [i, i + 1) of the closed polygon
+assert _RS_T[0] == 0 and np.all((_RS_T[:-1] >= 0) & (_RS_T[:-1] < 1)) and _RS_T[-1] == 1
+
+
+def _reresample(seg):
+    """What every further Instances(...) construction does to segments that are ALREADY [n, 1000, 2] (a reference quirk:
+    Instances.__init__ resamples whatever it is handed, utils/instance.py:200-204, and Instances.concatenate / __getitem__ and
+    RandomPerspective all construct new Instances): the 1001-point closed polygon resampled to 1000 points again.  np.interp's
+    arithmetic `slope * (x - xp[j]) + fp[j]` in float64 for all polygons at once (same operations, so the same bits); parameter i of
+    linspace(0, 1000, 1000) falls into interval j == i, the last one is the end point itself."""
+    if len(seg) == 0:
+        return seg
+    fp = np.concatenate((seg, seg[:, 0:1]), axis=1, dtype=np.float64)                         # [n, 1001, 2]
+    out = (fp[:, 1:] - fp[:, :-1]) * _RS_T[None, :, None] + fp[:, :-1]
+    out[:, -1] = fp[:, -1]                                                                    # x == xp[-1]: np.interp returns fp[-1]
+    return out.astype(F32)
+
+
+def _segments2boxes(sg, width, height):
+    """segment2box (utils/ops.py:75-92) of every polygon of sg [n, P, 2] at once, with its quirk: `any(x)` is false when no inside
+    point has a non-zero x -> zeros.  (min / max of float32 are exact, so masking with +-inf gives the reference's values.)"""
+    x, y = sg[..., 0], sg[..., 1]
+    inside = (x >= 0) & (y >= 0) & (x <= width) & (y <= height)
+    inf = sg.dtype.type(np.inf)
+    out = np.stack((np.where(inside, x, inf).min(1), np.where(inside, y, inf).min(1), np.where(inside, x, -inf).max(1),
+                    np.where(inside, y, -inf).max(1)), 1)
+    out[~(inside & (x != 0)).any(1)] = 0
+    return out
+
+
+def keypoints_with_visibility(keypoints):
+    """[n, K, 2 or 3] float32; for ndim == 2 the visibility column the label reader appends (data/utils.py:124-128): 0 where a
+    coordinate is negative, else 1"""
+    kp = np.array(keypoints, dtype=F32)
+    if kp.ndim != 3 or kp.shape[2] not in (2, 3):
+        raise ValueError("keypoints must be [n, K, 2 or 3]")
+    if kp.shape[2] == 2:
+        vis = np.ones(kp.shape[:2], dtype=F32)
+        vis = np.where(kp[..., 0] < 0, 0.0, vis)
+        vis = np.where(kp[..., 1] < 0, 0.0, vis)
+        kp = np.concatenate([kp, vis[..., None]], axis=-1).astype(F32)
+    return kp
+
+
+def check_flip_idx(hyp, flip_idx, n_kpt):
+    """the rule of v8_transforms (augment.py:780-787) for a pose dataset: no flip_idx and fliplr > 0 -> fliplr = 0 with a warning (a COPY
+    of hyp is returned, the caller's object is left alone); a flip_idx of the wrong length raises ValueError"""
+    import copy
+    import warnings
+    flip_idx = [] if flip_idx is None else [int(i) for i in flip_idx]
+    if len(flip_idx) == 0 and hyp.fliplr > 0.0:
+        hyp = copy.copy(hyp)
+        hyp.fliplr = 0.0
+        warnings.warn("no 'flip_idx' given for a pose dataset: setting augmentation fliplr=0.0")
+    elif flip_idx and len(flip_idx) != n_kpt:
+        raise ValueError(f"flip_idx={flip_idx} length must be equal to kpt_shape[0]={n_kpt}")
+    return hyp, (flip_idx or None)
+
+
+def train_labels(plan, labels, shapes, segments=None, keypoints=None, flip_idx=None):
     """The boxes of one planned sample through the reference's bookkeeping: per source xywhn -> xyxy pixels + mosaic offset
     (Mosaic._update_labels :262-268), concatenation, clip to the canvas and zero-area removal (_cat_labels :270-288), affine + clip
     + box_candidates against the scaled originals (RandomPerspective.__call__ :432-468), xywh-normalised (Albumentations' bookkeeping
     :681-692), flips on normalised centres (RandomFlip :521-534), Format's denormalise / normalise round trip (:719-733).
-    labels[i] = dict(cls [n,1] float32, bboxes [n,4] normalised xywh float32).  Returns (cls [m,1], bboxes [m,4]) float32."""
-    cls, boxes = [], []
+    labels[i] = dict(cls [n,1] float32, bboxes [n,4] normalised xywh float32).  Returns (cls [m,1], bboxes [m,4]) float32.
+
+    `segments[i]` (float32 [n_i, 1000, 2], normalised, resample_segments of image i's polygons) or `keypoints[i]` (float32 [n_i, K, 3],
+    normalised x, y + visibility) move through the same steps (Instances.denormalize / add_padding / clip :229-329,
+    RandomPerspective.apply_segments / apply_keypoints :375-421, Instances.flipud / fliplr, `flip_idx` on a horizontal flip :533-534) and a
+    third value is returned: the int32 [m, 1000, 2] pixel polygons exactly as polygon2mask hands them to cv2.fillPoly
+    (data/utils.py:146-147, astype(np.int32) of Format's denormalised segments), or the normalised keypoints [m, K, 3] of
+    Format(return_keypoint=True).  Rows are in LABEL order; the area order of Format._format_segments is applied on the device.
+    Reference quirks reproduced (the g20 fixtures decide):
+      * every Instances construction resamples non-empty segments again (_reresample): Instances.concatenate in Mosaic._cat_labels,
+        RandomPerspective's new_instances and its new_instances[i] -- three times on the mosaic path, twice on the letterbox path;
+      * with segments the boxes become segment2box of the transformed polygons (zeros when no inside point has a non-zero x) and
+        box_candidates uses area_thr 0.01 instead of 0.10 (:464-466);
+      * keypoints outside [0, w] x [0, h] after the affine map get visibility 0 and are then clipped like the rest (:419-420, :459);
+      * Albumentations' normalisation divides segments / keypoints by w, h while the boxes are multiplied by 1 / w, 1 / h."""
+    seg_on, kp_on = segments is not None, keypoints is not None
+    if seg_on and kp_on:
+        raise ValueError("Can not use both segments and keypoints.")
+    cls, boxes, segs, kps = [], [], [], []
     for src, rect in zip(plan.sources, plan.rects):
         h, w = shapes[src]
         b = _xywh2xyxy(np.array(labels[src]["bboxes"], dtype=F32, copy=True).reshape(-1, 4))
@@ -213,23 +305,65 @@ def train_labels(plan, labels, shapes):
         b[:, 3] += padh
         boxes.append(b)
         cls.append(np.array(labels[src]["cls"], dtype=F32).reshape(-1, 1))
+        for on, store, dst in ((seg_on, segments, segs), (kp_on, keypoints, kps)):
+            if on:
+                e = np.array(store[src], dtype=F32, copy=True)
+                e[..., :2] *= np.array([w, h], dtype=F32)             # per element the reference's `[..., 0] *= w`, `[..., 1] *= h`
+                e[..., :2] += np.array([padw, padh], dtype=F32)
+                dst.append(e)
     b, c = np.concatenate(boxes, 0), np.concatenate(cls, 0)
+    sg = np.concatenate(segs, 0) if seg_on else None
+    kp = np.concatenate(kps, 0) if kp_on else None
     if plan.mosaic:
         ch, cw = plan.canvas_hw
+        if seg_on:
+            sg = _reresample(sg)                                      # Instances.concatenate constructs a new Instances
         b[:, [0, 2]] = b[:, [0, 2]].clip(0, cw)
         b[:, [1, 3]] = b[:, [1, 3]].clip(0, ch)
+        for e in (sg, kp):
+            if e is not None:
+                np.clip(e[..., :2], 0, np.array([cw, ch], dtype=F32), out=e[..., :2])
         good = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]) > 0
         b, c = b[good], c[good]
+        sg, kp = (sg[good] if seg_on else None), (kp[good] if kp_on else None)
     nb = _apply_affine(b, plan.M)
     w, h = plan.size
+    if seg_on and len(sg):                                        # apply_segments: the boxes come from the polygons
+        n = len(sg)
+        xy = np.ones((n * sg.shape[1], 3), dtype=sg.dtype)
+        xy[:, :2] = sg.reshape(-1, 2)
+        xy = xy @ plan.M.T
+        xy = xy[:, :2] / xy[:, 2:3]
+        sg = xy.reshape(n, -1, 2)
+        nb = _segments2boxes(sg, w, h)
+        sg = _reresample(sg)                                          # Instances(bboxes, segments, keypoints)
+    if kp_on and len(kp):                                         # apply_keypoints
+        n, nk = kp.shape[:2]
+        xy = np.ones((n * nk, 3), dtype=kp.dtype)
+        vis = kp[..., 2].reshape(n * nk, 1).copy()
+        xy[:, :2] = kp[..., :2].reshape(n * nk, 2)
+        xy = xy @ plan.M.T
+        xy = xy[:, :2] / xy[:, 2:3]
+        vis[(xy[:, 0] < 0) | (xy[:, 1] < 0) | (xy[:, 0] > w) | (xy[:, 1] > h)] = 0
+        kp = np.concatenate([xy, vis], axis=-1).reshape(n, nk, 3)
     nb[:, [0, 2]] = nb[:, [0, 2]].clip(0, w)
     nb[:, [1, 3]] = nb[:, [1, 3]].clip(0, h)
+    for e in (sg, kp):
+        if e is not None:
+            np.clip(e[..., :2], 0, np.array([w, h], dtype=F32), out=e[..., :2])
     _mul(b, plan.scale, plan.scale)
-    keep = _candidates(b.T, nb.T, area_thr=0.10)
+    keep = _candidates(b.T, nb.T, area_thr=0.01 if (seg_on and len(sg)) else 0.10)
     nb, c = nb[keep], c[keep]
+    if seg_on:
+        sg = _reresample(sg[keep])                                    # new_instances[i]
+    if kp_on:
+        kp = kp[keep]
     if len(c):                                                # Albumentations.__call__ touches the boxes only when there are any
         nb = _xyxy2xywh(nb)
         _mul(nb, 1 / w, 1 / h)
+        for e in (sg, kp):
+            if e is not None:
+                e[..., :2] /= np.array([w, h], dtype=F32)
         normalized = True
     else:
         normalized = False
@@ -239,17 +373,41 @@ def train_labels(plan, labels, shapes):
     fh, fw = (1, 1) if normalized else (h, w)
     if plan.flipud:
         nb[:, 1] = fh - nb[:, 1]
+        for e in (sg, kp):
+            if e is not None:
+                e[..., 1] = fh - e[..., 1]
     if plan.fliplr:
         nb[:, 0] = fw - nb[:, 0]
+        for e in (sg, kp):
+            if e is not None:
+                e[..., 0] = fw - e[..., 0]
+        if kp_on and flip_idx is not None:
+            kp = np.ascontiguousarray(kp[:, flip_idx, :])
     if normalized:                                            # Format: denormalize(w, h) ...
         _mul(nb, w, h)
+        for e in (sg, kp):
+            if e is not None:
+                e[..., :2] *= np.array([w, h], dtype=F32)
+    polys = sg.astype(np.int32) if seg_on else None           # ... polygon2mask's truncation of the pixel polygons ...
     _mul(nb, 1 / w, 1 / h)                                    # ... then normalize(w, h)
+    if kp_on and normalized:
+        kp[..., 0] /= w
+        kp[..., 1] /= h
+    if seg_on:
+        return c, nb, polys
+    if kp_on:
+        return c, nb, kp
     return c, nb
 
 
-def val_labels(bboxes, shape, imgsz):
+def val_labels(bboxes, shape, imgsz, segments=None, keypoints=None):
     """LetterBox(scaleup=False)._update_labels + Format for the validation set (augment.py:593-603, 719-733).  Returns (bboxes
-    normalised xywh float32, ratio_pad ((r, r), (dw, dh)), geometry)."""
+    normalised xywh float32, ratio_pad ((r, r), (dw, dh)), geometry).  With `segments` (list of [k, 2] normalised polygons, or the
+    resampled [n, 1000, 2] array) or `keypoints` ([n, K, 2 or 3] normalised) a fourth value follows: the int32 [n, 1000, 2] polygons
+    polygon2mask hands to cv2.fillPoly (in label order), or the normalised keypoints [n, K, 3]: Instances.denormalize(w, h),
+    scale(r, r), add_padding(dw, dh), then Format's normalize(imgsz, imgsz)."""
+    if segments is not None and keypoints is not None:
+        raise ValueError("Can not use both segments and keypoints.")
     h, w = shape
     geo = letterbox_geometry((h, w), (imgsz, imgsz), scaleup=False)
     b = _xywh2xyxy(np.array(bboxes, dtype=F32, copy=True).reshape(-1, 4))
@@ -261,7 +419,25 @@ def val_labels(bboxes, shape, imgsz):
     b[:, 3] += geo.dh
     b = _xyxy2xywh(b)
     _mul(b, 1 / imgsz, 1 / imgsz)
-    return b, ((geo.r, geo.r), (geo.dw, geo.dh)), geo
+    out = (b, ((geo.r, geo.r), (geo.dw, geo.dh)), geo)
+    if segments is None and keypoints is None:
+        return out
+    if segments is not None:
+        e = segments if (isinstance(segments, np.ndarray) and segments.ndim == 3) else resample_segments(segments)
+        e = np.array(e, dtype=F32, copy=True)
+    else:
+        e = keypoints_with_visibility(keypoints)
+    e[..., 0] *= w
+    e[..., 1] *= h
+    e[..., 0] *= geo.r
+    e[..., 1] *= geo.r
+    e[..., 0] += geo.dw
+    e[..., 1] += geo.dh
+    if segments is not None:
+        return out + (e.astype(np.int32),)
+    e[..., 0] /= imgsz
+    e[..., 1] /= imgsz
+    return out + (e,)
 
 
 def collate(samples):
@@ -276,9 +452,14 @@ def collate(samples):
 class DeviceAugmenter:
     """Owns the decoded dataset images (uint8 HWC BGR at their load_image size, device-resident) and produces the reference's batch dict
     {img uint8 [B,3,s,s] RGB, cls, bboxes, batch_idx, n_max} for lists of sample plans.  `images`: list of uint8 HWC numpy arrays or
-    device tensors; `labels`: list of dict(cls, bboxes normalised xywh)."""
+    device tensors; `labels`: list of dict(cls, bboxes normalised xywh).
 
-    def __init__(self, images, labels, imgsz, hyp=None, device="cuda"):
+    task="segment": every label dict also carries `segments` (list of [k, 2] normalised polygons; resampled once here) and the batch
+    gains `masks` (uint8, device: [B, s / mask_ratio, s / mask_ratio] overlap index maps, or [N, ...] 0/1 planes with
+    overlap_mask=False) with cls / bboxes / batch_idx in the matching (area) order, on the device.  task="pose": `keypoints`
+    ([n, K, 2 or 3] normalised) -> batch `keypoints` [N, K, 3]."""
+
+    def __init__(self, images, labels, imgsz, hyp=None, device="cuda", task="detect", flip_idx=None, mask_ratio=4, overlap_mask=True):
         from .. import ops
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -292,6 +473,8 @@ class DeviceAugmenter:
         self.shapes = [(int(im.shape[0]), int(im.shape[1])) for im in self.images]
         self.labels = labels
         self.buffer = list(range(len(self.images)))
+        self.extras = TaskLabels(labels, task, self.hyp, flip_idx, mask_ratio, overlap_mask, self.imgsz)
+        self.hyp, self.task = self.extras.hyp, self.extras.task
 
     def plan(self, index, rnd=_random, nprnd=np.random):
         return plan_train_sample(index, self.shapes, self.buffer, self.imgsz, self.hyp, rnd, nprnd)
@@ -315,11 +498,125 @@ class DeviceAugmenter:
     def batch(self, indices, rnd=_random, nprnd=np.random):
         plans = [self.plan(i, rnd, nprnd) for i in indices]
         img = self.render(plans)
-        lab = [train_labels(p, self.labels, self.shapes) for p in plans]
-        bi, cls, bb = collate(lab)
-        n_max = max([len(c) for c, _ in lab] + [0])
-        return dict(img=img, batch_idx=bi, cls=cls, bboxes=bb, n_max=n_max, im_file=[f"{i}" for i in indices],
-                    ori_shape=[self.shapes[i] for i in indices], resized_shape=[(self.imgsz, self.imgsz)] * len(indices))
+        lab = [self.extras.train_labels(p, self.shapes) for p in plans]
+        n_max = max([len(l[0]) for l in lab] + [0])
+        meta = dict(n_max=n_max, im_file=[f"{i}" for i in indices], ori_shape=[self.shapes[i] for i in indices],
+                    resized_shape=[(self.imgsz, self.imgsz)] * len(indices))
+        if self.task == "segment":                            # labels on the device, in the order the masks index them
+            rows, polys, offsets = pack_rows(lab), pack_polygons(lab), instance_offsets(lab)
+            dev = lambda a: torch.from_numpy(a).to(self.device)
+            out = polygon_masks(dev(polys), dev(offsets), dev(rows), len(lab), self.imgsz, self.imgsz, self.extras.mask_ratio, self.extras.overlap_mask)
+            rows_d = out[1] if self.extras.overlap_mask else dev(rows)
+            return dict(img=img, batch_idx=rows_d[:, 0], cls=rows_d[:, 1:2], bboxes=rows_d[:, 2:6], masks=out[0],
+                        sorted_idx=out[2] if self.extras.overlap_mask else None, **meta)
+        bi, cls, bb = collate([l[:2] for l in lab])
+        batch = dict(img=img, batch_idx=bi, cls=cls, bboxes=bb, **meta)
+        if self.task == "pose":
+            batch["keypoints"] = torch.from_numpy(np.concatenate([l[2] for l in lab], 0))
+        return batch
+
+
+class TaskLabels:
+    """the per-task side of the label bookkeeping shared by DeviceAugmenter and DeviceAugmentLoader: polygons resampled once
+    (Instances.__init__), keypoints with their visibility column, the flip_idx rule of v8_transforms"""
+
+    def __init__(self, labels, task, hyp, flip_idx, mask_ratio, overlap_mask, imgsz):
+        if task not in ("detect", "segment", "pose"):
+            raise ValueError(f"task must be 'detect', 'segment' or 'pose', got {task!r}")
+        self.labels, self.task, self.hyp, self.flip_idx = labels, task, hyp, None
+        self.mask_ratio, self.overlap_mask = int(mask_ratio), bool(overlap_mask)
+        self.segments = self.keypoints = None
+        for lab in labels:
+            if lab.get("segments") is not None and lab.get("keypoints") is not None:
+                raise ValueError("Can not use both segments and keypoints.")         # dataset.py:27
+        if task == "segment":
+            if self.mask_ratio != 1 and (self.mask_ratio <= 0 or self.mask_ratio % 2):
+                raise ValueError("mask_ratio must be 1 or even")
+            if imgsz % self.mask_ratio:
+                raise ValueError("imgsz must be a multiple of mask_ratio")
+            self.segments = []
+            for lab in labels:
+                sg = lab.get("segments")
+                if sg is None or len(sg) != len(np.asarray(lab["cls"]).reshape(-1)):
+                    raise ValueError("task='segment': every label needs one polygon per instance in 'segments'")
+                self.segments.append(resample_segments(sg))
+        elif task == "pose":
+            if any(lab.get("keypoints") is None for lab in labels):
+                raise ValueError("task='pose': every label needs 'keypoints' [n, K, 2 or 3]")
+            self.keypoints = [keypoints_with_visibility(lab["keypoints"]) for lab in labels]
+            ks = {k.shape[1] for k in self.keypoints}
+            if len(ks) > 1:
+                raise ValueError(f"task='pose': labels disagree on the number of keypoints: {sorted(ks)}")
+            self.hyp, self.flip_idx = check_flip_idx(hyp, flip_idx, ks.pop() if ks else 0)
+
+    def train_labels(self, plan, shapes):
+        out = train_labels(plan, self.labels, shapes, self.segments, self.keypoints, self.flip_idx)
+        if self.task == "segment" and len(out[0]) > 255:
+            raise NotImplementedError("more than 255 instances in one image (the overlap mask is uint8)")
+        return out
+
+
+def instance_offsets(lab):
+    """int32 [B + 1]: first label row of every image"""
+    return np.concatenate(([0], np.cumsum([len(l[0]) for l in lab]))).astype(np.int32)
+
+
+def pack_rows(lab, out=None):
+    """f32 [N, 6] rows (batch_idx, cls, x, y, w, h) of a list of per-image (cls, bboxes, ...)"""
+    n = sum(len(l[0]) for l in lab)
+    rows = np.empty((n, 6), dtype=F32) if out is None else out[:n]
+    o = 0
+    for i, l in enumerate(lab):
+        m = len(l[0])
+        rows[o:o + m, 0], rows[o:o + m, 1], rows[o:o + m, 2:6] = i, l[0].reshape(-1), l[1]
+        o += m
+    return rows
+
+
+def pack_polygons(lab, out=None):
+    """int16 [N, 1000, 2]: the int32 polygons of train_labels / val_labels (already inside [0, s]) as the rasteriser reads them"""
+    n = sum(len(l[0]) for l in lab)
+    polys = np.empty((n, N_RESAMPLE, 2), dtype=np.int16) if out is None else out[:n]
+    o = 0
+    for l in lab:
+        m = len(l[0])
+        if m:
+            if int(l[2].min()) < -32768 or int(l[2].max()) > 32767:
+                raise ValueError("polygon vertex outside the int16 range")
+            polys[o:o + m] = l[2]
+        o += m
+    return polys
+
+
+def polygon_masks(polys, offsets, rows, B, h, w, mask_ratio=4, overlap=True):
+    """Ground-truth masks of a batch on the device (csrc/polymask.hip) = polygon2mask / polygons2masks / polygons2masks_overlap
+    (data/utils.py:137-190) + the re-ordering of Format._format_segments (augment.py:757-760), on the current stream, no host sync.
+    polys int16 [N, P, 2], offsets int32 [B + 1], rows f32 [N, 6] (device tensors).  overlap: (masks uint8 [B, h / r, w / r], rows in
+    area order [N, 6], sorted_idx int32 [N] = index within its image of the instance at each rank); else (planes uint8 [N, h / r, w / r]
+    in label order, None, None)."""
+    from .._C import call
+    from ..ops import ptr, stream
+    r = int(mask_ratio)
+    if r != 1 and (r <= 0 or r % 2):
+        raise ValueError("mask_ratio must be 1 or even")
+    if h % r or w % r:
+        raise ValueError("the image size must be a multiple of mask_ratio")
+    if polys.dtype != torch.int16 or polys.dim() != 3 or polys.shape[2] != 2 or not polys.is_cuda:
+        raise ValueError("polygon_masks: polys must be a device int16 tensor [N, P, 2]")
+    N, P = int(polys.shape[0]), int(polys.shape[1])
+    if offsets.dtype != torch.int32 or offsets.numel() != B + 1 or rows.dtype != torch.float32 or tuple(rows.shape) != (N, 6):
+        raise ValueError("polygon_masks: offsets must be int32 [B + 1] and rows f32 [N, 6]")
+    polys, offsets, rows = polys.contiguous(), offsets.contiguous(), rows.contiguous()
+    dev, mh, mw = polys.device, h // r, w // r
+    planes = torch.empty((N, mh, mw), dtype=torch.uint8, device=dev)
+    area = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    call("dy_polymask_raster", ptr(polys), N, max(P, 1), h, w, r, ptr(planes), ptr(area), stream())
+    if not overlap:
+        return planes, None, None
+    masks = torch.empty((B, mh, mw), dtype=torch.uint8, device=dev)
+    rows_out, perm = torch.empty_like(rows), torch.empty(N, dtype=torch.int32, device=dev)
+    call("dy_polymask_compose", ptr(planes), ptr(area), ptr(offsets), B, N, mh, mw, ptr(rows), ptr(rows_out), ptr(perm), ptr(masks), stream())
+    return masks, rows_out, perm
 
 
 def descriptor_bytes():

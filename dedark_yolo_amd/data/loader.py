@@ -10,21 +10,30 @@ import random as _random
 import numpy as np
 import torch
 
-from .augment import AugmentHyp, DeviceAugmenter, plan_train_sample, train_labels
+from .augment import (N_RESAMPLE, AugmentHyp, DeviceAugmenter, TaskLabels, instance_offsets, pack_polygons, pack_rows, plan_train_sample,
+                      polygon_masks)
 
 
 class DeviceAugmentLoader:
-    def __init__(self, images, labels, imgsz, batch_size, hyp=None, device="cuda", resident=True, seed=0, shuffle=True, drop_last=True):
+    """task="detect": batches of {img, batch_idx, cls, bboxes, n_max}.  task="segment" (labels carry `segments`): `masks` is added --
+    rasterised on the device from the augmented polygons (csrc/polymask.hip) -- and batch_idx / cls / bboxes are the device rows in the
+    area order the overlap masks index (`sorted_idx`: the permutation).  task="pose" (labels carry `keypoints`): `keypoints` [N, K, 3]
+    f32 is added.  Everything is uploaded from the pinned ring and issued on the loader's stream."""
+
+    def __init__(self, images, labels, imgsz, batch_size, hyp=None, device="cuda", resident=True, seed=0, shuffle=True, drop_last=True,
+                 task="detect", flip_idx=None, mask_ratio=4, overlap_mask=True):
         self.device = torch.device(device)
         self.imgsz, self.bs, self.hyp = int(imgsz), int(batch_size), hyp or AugmentHyp()
         self.labels = labels
+        self.extras = TaskLabels(labels, task, self.hyp, flip_idx, mask_ratio, overlap_mask, self.imgsz)
+        self.hyp, self.task = self.extras.hyp, task           # a pose set without flip_idx: fliplr = 0 (v8_transforms)
         self.resident = bool(resident)
         self.shapes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         self.shuffle, self.drop_last = shuffle, drop_last
         self.rnd = _random.Random(seed)                      # own generators: the loader must not disturb the caller's global RNG state
         self.nprnd = np.random.RandomState(seed + 1)
         if self.resident:
-            self.aug = DeviceAugmenter(images, labels, imgsz, self.hyp, device)
+            self.aug = DeviceAugmenter(images, [dict(cls=l["cls"], bboxes=l["bboxes"]) for l in labels], imgsz, self.hyp, device)
             self.host = None
         else:
             self.host = [(im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))).pin_memory() for im in images]
@@ -59,17 +68,28 @@ class DeviceAugmentLoader:
         launch -- on the loader's own stream, without a host synchronisation: it is issued while the previous training step is still
         running on the compute stream and shares the GPU with it.  Returns (batch dict of device tensors, event)."""
         plans = self._plans(indices)
-        lab = [train_labels(p, self.labels, self.shapes) for p in plans]
-        n = sum(len(c) for c, _ in lab)
+        lab = [self.extras.train_labels(p, self.shapes) for p in plans]
+        n = sum(len(l[0]) for l in lab)
         slot = self._slots()
         if n > slot["lab"].shape[0]:
             slot["lab"] = torch.empty((2 * n, 6), dtype=torch.float32).pin_memory()
-        rows = slot["lab"][:n].numpy()
-        o = 0
-        for i, (c, b) in enumerate(lab):
-            m = len(c)
-            rows[o:o + m, 0], rows[o:o + m, 1], rows[o:o + m, 2:6] = i, c.reshape(-1), b
-            o += m
+        pack_rows(lab, slot["lab"].numpy())
+        extra = None
+        if self.task == "segment":                               # polygons + per-image offsets ride in the same pinned slot
+            if "off" not in slot:
+                slot["off"] = torch.empty(self.bs + 1, dtype=torch.int32).pin_memory()
+            if slot.get("poly") is None or n > slot["poly"].shape[0]:
+                slot["poly"] = torch.empty((max(2 * n, 16 * self.bs), N_RESAMPLE, 2), dtype=torch.int16).pin_memory()
+            pack_polygons(lab, slot["poly"].numpy())
+            slot["off"].numpy()[:len(lab) + 1] = instance_offsets(lab)
+        elif self.task == "pose":
+            K = lab[0][2].shape[1]
+            if slot.get("kp") is None or n > slot["kp"].shape[0] or slot["kp"].shape[1] != K:
+                slot["kp"] = torch.empty((max(2 * n, 16 * self.bs), K, 3), dtype=torch.float32).pin_memory()
+            kph, o = slot["kp"].numpy(), 0
+            for l in lab:
+                kph[o:o + len(l[0])] = l[2]
+                o += len(l[0])
         with torch.cuda.stream(self.stream):
             if self.resident:
                 aug = self.aug
@@ -81,9 +101,26 @@ class DeviceAugmentLoader:
                 aug.device, aug.imgsz, aug.hyp, aug.images = self.device, self.imgsz, self.hyp, _Sparse(dev)
             img = aug.render(plans, staging=slot["desc"])
             labd = slot["lab"][:n].to(self.device, non_blocking=True)
+            if self.task == "segment":
+                polyd = slot["poly"][:n].to(self.device, non_blocking=True)
+                offd = slot["off"][:len(lab) + 1].to(self.device, non_blocking=True)
+                masks, rows, perm = polygon_masks(polyd, offd, labd, len(lab), self.imgsz, self.imgsz, self.extras.mask_ratio,
+                                                  self.extras.overlap_mask)
+                extra = dict(masks=masks)
+                tensors = (img, labd, polyd, offd, masks)
+                if self.extras.overlap_mask:
+                    labd, extra["sorted_idx"] = rows, perm
+                    tensors += (rows, perm)
+            elif self.task == "pose":
+                kpd = slot["kp"][:n].to(self.device, non_blocking=True)
+                extra, tensors = dict(keypoints=kpd), (img, labd, kpd)
+            else:
+                tensors = (img, labd)
             slot["ev"].record(self.stream)
-        batch = dict(img=img, batch_idx=labd[:, 0], cls=labd[:, 1:2], bboxes=labd[:, 2:6], n_max=max([len(c) for c, _ in lab] + [0]))
-        return batch, slot["ev"], (img, labd)
+        batch = dict(img=img, batch_idx=labd[:, 0], cls=labd[:, 1:2], bboxes=labd[:, 2:6], n_max=max([len(l[0]) for l in lab] + [0]))
+        if extra:
+            batch.update(extra)
+        return batch, slot["ev"], tensors
 
     def __iter__(self):
         order = list(range(len(self.shapes)))

@@ -430,6 +430,24 @@ int dy_aug_mosaic_warp(const dy_aug_sample* samples, int B, int out_h, int out_w
 int dy_dark_channel_prior(const float* img, int B, int H, int W, float* A, float* ica, void* stream);
 
 
+/* ---- ground-truth masks of the segment task from polygons (csrc/polymask.hip) -------------------------------------------------------
+ * Replaces polygon2mask (ultralytics/data/utils.py:137-155: cv2.fillPoly at the input resolution + cv2.resize by 1 / mask_ratio) for
+ * every instance of a batch in one launch.  polys: int16 [n_total][P][2] (x, y) vertices as polygon2mask truncates them
+ * (astype(np.int32)), 1 <= P <= 4096; coordinates outside the plane (x == w, y == h included) are legal and never touch memory outside
+ * it.  Pixel rule: full-resolution pixel (x, y) is set iff the integer point lies in the CLOSED polygon (even-odd interior or on an
+ * edge, closing edge included; integer arithmetic); the mask is cv2.resize(INTER_LINEAR) of that 0/1 plane: ratio 1 = the plane, even
+ * ratio = at least 2 of the 4 taps (rows / columns ratio i + ratio / 2 - 1 and + 1).  planes: uint8 [n_total][h / ratio][w / ratio]
+ * 0/1 (= polygons2masks, utils.py:158-170, in label order); area: int32 [n_total] set-pixel counts (utils.py:182).  w <= 2048. */
+int dy_polymask_raster(const int16_t* polys, int n_total, int P, int h, int w, int ratio, uint8_t* planes, int32_t* area, void* stream);
+/* polygons2masks_overlap (utils.py:173-190) + the re-ordering of Format._format_segments (augment.py:757-760) for B images: instances
+ * of image b are rows offsets[b] .. offsets[b + 1] (at most 255); they are ranked by area descending, equal areas by original index
+ * (the reference's unstable argsort leaves ties open); masks uint8 [B][mh][mw] = 1 + largest rank covering the pixel, else 0;
+ * rows_out [n_total][6] = the f32 label rows in rank order, perm int32 [n_total] = index within the image of the instance at each
+ * rank (`sorted_idx`). */
+int dy_polymask_compose(const uint8_t* planes, const int32_t* area, const int32_t* offsets, int B, int n_total, int mh, int mw,
+                        const float* rows_in, float* rows_out, int32_t* perm, uint8_t* masks, void* stream);
+
+
 /* ---- segment task (csrc/seg.hip) ---------------------------------------------------------------------------------------------------
  * Mask loss of v8SegmentationLoss (U/utils/loss.py:252-288, single_mask_loss; crop_mask U/utils/ops.py:553-569) on the assignment of
  * dy_tal_assign, and the bias of the Proto's ConvTranspose2d(k=2, s=2) (U/nn/modules/block.py:242-254; its weight runs on
