@@ -168,6 +168,13 @@ _SIGS = {
     "dy_kpt_oks": [vp, i32, vp, i32, i32, vp, vp, i32, f32, vp, vp],
     "dy_polymask_raster": [vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "dy_polymask_compose": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "dy_gap_fwd": [vp, i64, i32, i32, i32, i32, vp, i64, vp],
+    "dy_gap_bwd": [vp, i64, i32, i32, i32, i32, vp, i64, vp],
+    "dy_cls_xent_fwd": [vp, i64, i32, vp, i32, i32, vp, vp, vp],
+    "dy_cls_xent_bwd": [vp, i64, i32, vp, vp, vp, i32, i32, vp, i64, vp],
+    "dy_cls_softmax": [vp, i64, i32, i32, i32, vp, vp],
+    "dy_cls_topk": [vp, i64, i32, i32, i32, i32, vp, vp],
+    "dy_cls_metrics_update": [vp, i32, vp, i32, i32, vp, vp, vp],
 }
 
 _lib = None

@@ -1,23 +1,23 @@
 """`YOLO` facade with the reference call surface (ultralytics/engine/model.py:29-416): YOLO(model), .train(**kw), .val(**kw),
-.load(), .fuse(); the detect, segment and pose tasks (the others are outside the hot path)."""
+.load(), .fuse(); the detect, segment, pose and classify tasks."""
 from pathlib import Path
 
 import torch
 
-from ..nn.tasks import task_table
+from ..nn.tasks import all_tasks
 from .trainer import DetectionTrainer, get_cfg
 
 
 def _model_class(task):
-    return task_table()[task][0]
+    return all_tasks()[task][0]
 
 
 def _resolve_task(task, d):
-    """The yaml's own task unless one is given; 'pose' and a Pose head go together only (an explicit task that contradicts
-    them raises, as one outside the hot path does)."""
+    """The yaml's own task unless one is given; 'pose' and a Pose head go together only, and so do 'classify' and a Classify
+    head (an explicit task that contradicts them raises, as one outside the hot path does)."""
     from ..nn.tasks import guess_model_task
     head = guess_model_task(d)
-    if task is not None and (task == "pose") != (head == "pose"):
+    if task is not None and any((task == t) != (head == t) for t in ("pose", "classify")):
         raise NotImplementedError(f"task '{task}' does not match the model's {head} head")
     return task or head
 
@@ -47,8 +47,8 @@ def segment_postprocess(dets, proto, input_shape, orig_shapes=None, retina_masks
 
 class YOLO:
     def __init__(self, model="yolov8l.yaml", task=None):
-        if task not in (None, "detect", "segment", "pose"):
-            raise NotImplementedError("only the detect, segment and pose tasks are on the Dedark-YOLO hot path")
+        if task not in (None, "detect", "segment", "pose", "classify"):
+            raise NotImplementedError("only the detect, segment, pose and classify tasks are on the Dedark-YOLO hot path")
         self.task = task
         self.trainer = None
         self.overrides = {}
@@ -116,7 +116,7 @@ class YOLO:
     def val(self, loader=None, **kwargs):
         ov = dict(self.overrides)
         ov.update(kwargs)
-        return task_table()[self.task][2](get_cfg(ov))(self.model, loader)
+        return all_tasks()[self.task][2](get_cfg(ov))(self.model, loader)
 
     @torch.no_grad()
     def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, **kw):
@@ -124,7 +124,8 @@ class YOLO:
         for an already letter-boxed batch: `source` is a uint8 [B,3,H,W] RGB tensor (or float in [0,1]); returns one `Results`
         per image with boxes scaled back to `orig_shapes[i]` (default: the network input shape).  A segment model also fills
         `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Image decoding / letter-boxing (cv2), plotting
-        and the mask contours (`Masks.xy`) are outside the hot path."""
+        and the mask contours (`Masks.xy`) are outside the hot path.  A classify model returns `Results.probs` (the eval soft-max row
+        of each image; classify/predict.py:23-31) and no boxes."""
         from ..utils import ops as uops
         from .results import Results
         from .validator import DetectionValidator
@@ -140,6 +141,12 @@ class YOLO:
         else:
             img = source.to(dev).float()
         preds = self.model(img)
+        if self.task == "classify":
+            H, W = img.shape[2:]
+            out = [Results(tuple(orig_shapes[i]) if orig_shapes is not None else (H, W), names=self.model.names, probs=p)
+                   for i, p in enumerate(preds)]
+            self.model.train(was_training)
+            return out
         if self.task == "segment":                            # models/yolo/segment/predict.py:16-26
             dets = uops.non_max_suppression(preds[0], conf, iou, agnostic=agnostic_nms, max_det=max_det, nc=len(self.model.names))
             proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]

@@ -23,7 +23,7 @@ import yaml
 from .. import ops
 from .._C import call
 from ..nn.modules import DyModule
-from ..nn.tasks import DetectionModel, guess_model_task, task_table
+from ..nn.tasks import DetectionModel, all_tasks, guess_model_task
 from ..ops import ptr, stream
 
 DEFAULT_CFG_PATH = Path(__file__).resolve().parent.parent / "cfg" / "default.yaml"
@@ -267,6 +267,10 @@ class DetectionTrainer:
                            if self.compute_dtype == torch.float16 else None)
         self.model = (model if model is not None else self.get_model(nc=nc)).to(self.device)
         self.model.args = self.args
+        self.classify = guess_model_task(self.model) == "classify"
+        if self.classify:                                        # classify/train.py:30-44 sets Dropout.p = args.dropout
+            if float(getattr(self.args, "dropout", 0.0) or 0.0) > 0.0:
+                raise NotImplementedError("classify: dropout > 0 is not implemented (torch's Philox order cannot be matched)")
         self.model.train()
         if self.world_size > 1:
             if not dist.is_initialized():
@@ -310,6 +314,8 @@ class DetectionTrainer:
         """reference detect/train.py:70-111 (tensor part): clean_img, img (darkened), recovery_loss_batch."""
         a = self.args
         img = batch["img"]
+        if getattr(self, "classify", False):
+            return self._preprocess_classify(batch)
         if img.dtype != torch.uint8:
             raise RuntimeError("preprocess_batch expects the dataloader's uint8 image tensor")
         bi = batch.get("batch_idx")
@@ -335,6 +341,13 @@ class DetectionTrainer:
             from ..data.augment import dark_channel_prior
             batch["dedark_A"], batch["IcA"] = dark_channel_prior(out)
         return batch
+
+    def _preprocess_classify(self, batch):
+        """reference classify/train.py:87-91: img and cls to the device, nothing else -- no darkening and no recovery term
+        (lowlight_FLAG / dedark_FLAG are not read there either).  A uint8 img becomes f32 / 255 on the device, a float img passes
+        through; cls is int64 [B]."""
+        from ..utils.loss import classify_batch_to_device
+        return classify_batch_to_device(batch, self.device, self.mse_acc, nc=int(self.model.yaml["nc"]))
 
     # ---------------------------------------------------------------- step
     def lr_factors(self, ni, nw, epoch, epochs):
@@ -560,7 +573,7 @@ class DetectionTrainer:
     def validate(self, val_loader):
         """trainer.validate() (engine/trainer.py:471-480): the validator on the EMA weights, forced to fp32 as the fork does
         (engine/validator.py:105-107 `self.args.half = False`).  Returns (metrics dict, fitness)."""
-        V = task_table()[guess_model_task(self.model)][2]
+        V = all_tasks()[guess_model_task(self.model)][2]
         dt = ops.get_compute_dtype()
         try:
             with self.ema_weights() as model:
@@ -604,7 +617,7 @@ class DetectionTrainer:
                 loss, items = self.train_step(batch, lr, mom, step_optimizer=step)
                 if step:
                     self.last_opt_step = ni
-            history.append([float(v) for v in items])
+            history.append([float(v) for v in items.reshape(-1)])     # (classify: one column, a 0-dim tensor)
             if self.rank in (-1, 0):
                 final_epoch = epoch + 1 == epochs or self.stopper.possible_stop
                 if val_loader is not None and (getattr(self.args, "val", True) or final_epoch):

@@ -12,7 +12,7 @@ from .. import ops as kops
 from .._C import call
 from ..ops import ptr, stream
 from ..utils import ops
-from ..utils.metrics import DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou, oks_sigmas
+from ..utils.metrics import ClassifyMetrics, DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou, oks_sigmas
 
 
 def match_predictions(detections, labels, iouv):
@@ -240,3 +240,69 @@ class PoseValidator(DetectionValidator):
         area = ops.xyxy2xywh(labelsn[:, 1:])[:, 2:].prod(1) * 0.53
         oks = kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma).cpu().numpy()
         return (match_from_iou(oks, labelsn[:, 0], predn[:, 5], self.iouv),)
+
+
+class ClassificationValidator:
+    """Classify validator (reference models/yolo/classify/val.py:39-60, engine/validator.py:95-200): preprocess -> eval forward
+    (soft-max probabilities) -> dy_cls_topk (k = min(nc, 5)) -> dy_cls_metrics_update.  The hit counts and the confusion matrix
+    ([pred top-1][target], ConfusionMatrix.process_cls_preds, metrics.py:197-207) stay on the device: nothing is read back per
+    batch, `get_stats` reads both once.  A batch is {img: uint8 or float [B, 3, H, W], cls: int64 [B]}; there is no
+    validation-loss column and no plotting."""
+
+    def __init__(self, args=None, dataloader=None):
+        from .trainer import get_cfg
+        self.args = args if args is not None else get_cfg()
+        self.args.task = "classify"
+        self.dataloader = dataloader
+        self.metrics = ClassifyMetrics()
+        self.device = None
+        self.training = False
+        self.confusion_matrix = None
+        self._acc = None
+
+    def preprocess(self, batch):
+        """val.py:32-37: img to the device as float, cls to the device; a uint8 image additionally becomes f32 / 255 on the device."""
+        from ..utils.loss import classify_batch_to_device
+        if self._acc is None or self._acc.device != self.device:
+            self._acc = torch.zeros(1, dtype=torch.float64, device=self.device)
+        return classify_batch_to_device(batch, self.device, self._acc)
+
+    def init_metrics(self, model):
+        self.nc = len(model.names) if getattr(model, "names", None) else int(model.yaml["nc"])
+        self.names = getattr(model, "names", None) or {i: str(i) for i in range(self.nc)}
+        self.metrics.names = self.names
+        self.counts = torch.zeros(3, dtype=torch.int64, device=self.device)
+        self._confusion = torch.zeros((self.nc, self.nc), dtype=torch.int32, device=self.device)
+        self.confusion_matrix = None
+
+    def update_metrics(self, preds, batch):
+        """val.py:39-43 on the device: the k best classes per row, then the counters."""
+        preds = preds[0] if isinstance(preds, (list, tuple)) else preds
+        idx = kops.cls_topk(preds)
+        kops.cls_metrics_update(idx, batch["cls"], self.nc, self.counts, self._confusion)
+
+    def get_stats(self):
+        """val.py:45-60 (finalize_metrics, get_stats): the one read-back of the run."""
+        self.metrics.process_counts(self.counts.cpu().tolist())
+        self.confusion_matrix = self._confusion.cpu().numpy().astype(np.int64)
+        return self.metrics.results_dict
+
+    @torch.no_grad()
+    def __call__(self, model, dataloader=None, dtype=None):
+        loader = dataloader if dataloader is not None else self.dataloader
+        if loader is None:
+            raise ValueError("pass an iterable of {img, cls} batch dicts; dataset decoding is outside the hot path")
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("ClassificationValidator needs the model on a GPU (there is no CPU path)")
+        if dtype is not None:
+            kops.set_compute_dtype(dtype)
+        was_training = model.training
+        model.eval()
+        self.init_metrics(model)
+        for batch in loader:
+            batch = self.preprocess(dict(batch))
+            self.update_metrics(model(batch["img"]), batch)
+        stats = self.get_stats()
+        model.train(was_training)
+        return {k: float(v) for k, v in stats.items()}

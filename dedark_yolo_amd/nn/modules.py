@@ -18,7 +18,7 @@ from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
 __all__ = ("Conv", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
-           "AsffDetect", "Proto", "Segment", "Pose",
+           "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
 
@@ -1189,6 +1189,76 @@ class Pose(Detect):
         dxs = self._run_levels(lambda t, i, g: self._pose_level_bwd(t, i, g, gk[i]), subs, list(gs[:n]))
         self._fold_tapes(tape, subs)
         return dxs
+
+
+class _RowsFn(torch.autograd.Function):
+    """NHWC logits [B, n, 1, 1] -> the [B, n] view the caller sees, and the [B, n] gradient (rows of the padded buffer
+    dy_cls_xent_bwd wrote) back to an NHWC view: both directions are views, nothing is compacted or copied."""
+
+    @staticmethod
+    def forward(ctx, z):
+        ctx.ve = ops.vec_elems(z.dtype)
+        return ops.rows_2d(z)
+
+    @staticmethod
+    def backward(ctx, g):
+        g4 = ops.rows_4d(g, ctx.ve)
+        if g4 is None:                          # a gradient that did not come from the criterion: pad it on the way in
+            B, n = g.shape
+            buf = torch.zeros((B, ops.round_up(n, ctx.ve)), dtype=g.dtype, device=g.device)
+            buf[:, :n] = g
+            g4 = ops.rows_4d(buf[:, :n], ctx.ve)
+        return g4
+
+
+class Classify(DyModule):
+    """YOLOv8 classification head (reference head.py:244-260): Conv(c1, 1280, k, s) -> AdaptiveAvgPool2d(1) -> Dropout(0.0) ->
+    Linear(1280, c2).  Train: logits [B, c2] in the compute dtype (rows of a buffer padded to the vector width); eval: softmax(1),
+    f32 [B, c2].  The pool is dy_gap_fwd / dy_gap_bwd, the Linear runs as a 1x1 conv with bias on the pooled [B, 1280, 1, 1] map
+    and the soft-max is dy_cls_softmax.  `pool` and `drop` are containers only (the checkpoint writer names them); p > 0 has no
+    kernel (torch's Philox stream cannot be matched) and raises."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1):
+        super().__init__()
+        c_ = 1280
+        self.conv = Conv(c1, c_, k, s, p, g)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.drop = nn.Dropout(p=0.0, inplace=True)
+        self.linear = nn.Linear(c_, c2)
+
+    def _linear_view(self):
+        """linear.weight as a [c2, 1280, 1, 1] conv weight; the view OBJECT is kept, the packed-weight cache lives on it."""
+        w = self.linear.weight
+        c = self.__dict__.get("_lin_view_cache")
+        if c is None or c[0] != w.data_ptr():
+            c = (w.data_ptr(), w.detach().view(w.shape[0], w.shape[1], 1, 1))
+            self.__dict__["_lin_view_cache"] = c
+            ops.register_pack_view(c[1])
+        return c[1]
+
+    def _fwd(self, tape, x, *more):
+        if more:
+            raise NotImplementedError("Classify: a list of input layers (torch.cat in the reference) is outside the hot path")
+        if self.drop.p:
+            raise NotImplementedError("Classify: dropout > 0 is not implemented (torch's Philox order cannot be matched)")
+        y = self.conv._fwd(tape, x)
+        pooled = ops.gap_fwd(y)
+        if tape is not None:
+            tape.push((y.shape[2], y.shape[3]))
+        z = conv_forward(tape, pooled, self._linear_view(), self.linear.bias, None, ACT_NONE, 1, 0, 1, False, owner=self.linear.weight)
+        return z if self.training else ops.cls_softmax(z)
+
+    def _wrap(self, out):
+        if out.dim() != 4:
+            return out
+        return _RowsFn.apply(out) if out.requires_grad else ops.rows_2d(out)
+
+    def _bwd(self, tape, dz, needs=(True,)):
+        if not self.training:
+            raise RuntimeError("Classify: backward through the eval soft-max is not supported")
+        dp = conv_backward(tape, dz)
+        H, W = tape.pop()
+        return self.conv._bwd(tape, ops.gap_bwd(dp, H, W), needs=needs)
 
 # ------------------------------------------------------------------------------------------------ low-light front-end
 class ConvBlock(nn.Module):

@@ -15,7 +15,7 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Classify, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
                       PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SPPF, Segment, Tape, Upsample,
                       lowlight_recovery)
 
@@ -29,7 +29,7 @@ CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
-                 Segment=Segment, Pose=Pose)
+                 Segment=Segment, Pose=Pose, Classify=Classify)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -49,7 +49,7 @@ def yaml_model_load(path):
     """'yolov8l.yaml' -> dict of yolov8.yaml with d['scale']='l' (reference tasks.py:924-946)."""
     path = Path(path)
     unified = re.sub(r"(\d+)([nslmx])(.+)?$", r"\1\3", str(path))
-    for cand in (Path(unified), path, CFG_DIR / Path(unified).name, CFG_DIR / path.name):
+    for cand in (Path(unified), path, CFG_DIR / Path(unified).name, CFG_DIR / path.name, CFG_DIR / "cls" / Path(unified).name):
         if cand.is_file():
             with open(cand) as f:
                 d = yaml.safe_load(f)
@@ -103,6 +103,7 @@ _RULES = {
     AsffDetect: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),
     Segment: _rule_segment,
     Pose: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),                        # tasks.py:897-898
+    Classify: _rule_conv_like,                                                                 # tasks.py:743-753: [c1, nc], nc unscaled
 }
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
@@ -601,27 +602,65 @@ class PoseModel(DetectionModel):
         return v8PoseLoss(self)
 
 
+class ClassificationModel(BaseModel):
+    """YOLOv8 classification model (reference tasks.py:389-457, _from_yaml): the detection backbone under a Classify head,
+    criterion v8ClassificationLoss.  Training output: logits [B, nc]; eval output: softmax probabilities f32 [B, nc].  Unlike
+    DetectionModel the reference neither calls initialize_weights here (every BatchNorm keeps torch's eps 1e-5 / momentum 0.1)
+    nor runs warm-up passes (running statistics start at (0, 1)); stride is [1].  _from_detection_model, torchvision backbones
+    and reshape_outputs are out of scope."""
+
+    def __init__(self, cfg="yolov8n-cls.yaml", ch=3, nc=None, verbose=False):
+        super().__init__()
+        self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        ch = self.yaml["ch"] = self.yaml.get("ch", ch)
+        if nc and nc != self.yaml["nc"]:
+            self.yaml["nc"] = nc
+        elif not nc and not self.yaml.get("nc", None):
+            raise ValueError("nc not specified. Must specify nc in model.yaml or function arguments.")
+        self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
+        if not isinstance(self.model[-1], Classify):
+            raise ValueError("ClassificationModel: the yaml's last layer is not a Classify head")
+        self.stride = torch.Tensor([1])
+        self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
+
+    def _predict_once(self, x, profile=False, visualize=False):
+        return self.model[-1]._wrap(super()._predict_once(x))      # the graph's NHWC logits -> [B, nc]
+
+    def init_criterion(self):
+        from ..utils.loss import v8ClassificationLoss
+        return v8ClassificationLoss()
+
+
 def task_table():
-    """task -> (model class, head class, validator class): the one place that says which classes serve which task, in the order
-    a head is matched (Segment and Pose subclass Detect, so 'detect' comes last).  A function, because the validators live in the
-    engine package, which imports this module."""
+    """task -> (model class, head class, validator class) of the tasks whose head is a Detect: the one place that says which classes
+    serve which of them, in the order a head is matched (Segment and Pose subclass Detect, so 'detect' comes last).  A function,
+    because the validators live in the engine package, which imports this module.  `all_tasks()` adds the classify row."""
     from ..engine.validator import DetectionValidator, PoseValidator, SegmentationValidator
     return {"segment": (SegmentationModel, Segment, SegmentationValidator),
             "pose": (PoseModel, Pose, PoseValidator),
             "detect": (DetectionModel, Detect, DetectionValidator)}
 
 
+def all_tasks():
+    """task_table() plus the task whose head is no Detect: 'classify' (ClassificationModel, Classify, ClassificationValidator; its
+    yaml lives under cfg/models/v8/cls).  This is what the facade, the trainer, guess_model_task and the checkpoint writer dispatch
+    through."""
+    from ..engine.validator import ClassificationValidator
+    return {**task_table(), "classify": (ClassificationModel, Classify, ClassificationValidator)}
+
+
 def guess_model_task(model):
-    """The task whose head class (task_table) the model's last layer is: 'segment', 'pose', or 'detect' for Detect / AsffDetect
-    (reference tasks.py:968-1030, from a yaml dict or a model).  The reference's yaml rule reads `m == 'detect' or "asffdetect"`,
+    """The task whose head class (all_tasks) the model's last layer is: 'segment', 'pose', 'classify', or 'detect' for Detect /
+    AsffDetect (reference tasks.py:968-1030, from a yaml dict or a model).  The reference's yaml rule reads `m == 'detect' or "asffdetect"`,
     which is always true; the intended rule is used here."""
     if isinstance(model, dict):
         kind = str(model["head"][-1][-2]).lower()
-        head = next((c for name, c in _REGISTRY.items() if name.lower() == kind and issubclass(c, Detect)), None)
+        heads = tuple(h for _, h, _ in all_tasks().values())
+        head = next((c for name, c in _REGISTRY.items() if name.lower() == kind and issubclass(c, heads)), None)
         if head is None:
             raise NotImplementedError(f"head '{model['head'][-1][-2]}' is outside the Dedark-YOLO hot path")
     elif isinstance(model, nn.Module):
         head = type(model.model[-1] if hasattr(model, "model") else model)
     else:
         raise TypeError(f"guess_model_task: expected a yaml dict or a model, got {type(model).__name__}")
-    return next((task for task, (_, h, _) in task_table().items() if issubclass(head, h)), "detect")
+    return next((task for task, (_, h, _) in all_tasks().items() if issubclass(head, h)), "detect")

@@ -899,6 +899,108 @@ def pose_desc(kpts, strides, kpt_shape):
     d.A = A
     return d
 
+
+# ------------------------------------------------------------------------------------------------ classify task (csrc/classify.hip)
+def gap_fwd(x):
+    """AdaptiveAvgPool2d(1) of an NHWC view [N, C, H, W] -> NHWC [N, C, 1, 1] (pad lanes, if any, zero)."""
+    N, Cc, H, W = x.shape
+    Cp = round_up(Cc, vec_elems(x.dtype))
+    y = (empty_nhwc if Cp == Cc else zeros_nhwc)(N, Cp, 1, 1, x.dtype, x.device)
+    call("dy_gap_fwd", ptr(x), ld_of(x), N, H * W, Cc, dt_id(x.dtype), ptr(y), Cp, stream())
+    emu_round(y)
+    return y if Cp == Cc else y[:, :Cc]
+
+
+def gap_bwd(dy, H, W):
+    """Adjoint of gap_fwd: dy NHWC [N, C, 1, 1] -> dx NHWC [N, C, H, W] = dy / (H W) at every pixel."""
+    N, Cc = dy.shape[0], dy.shape[1]
+    Cp = round_up(Cc, vec_elems(dy.dtype))
+    dx = (empty_nhwc if Cp == Cc else zeros_nhwc)(N, Cp, H, W, dy.dtype, dy.device)
+    call("dy_gap_bwd", ptr(dy), ld_of(dy), N, H * W, Cc, dt_id(dy.dtype), ptr(dx), Cp, stream())
+    emu_round(dx)
+    return dx if Cp == Cc else dx[:, :Cc]
+
+
+def row_matrix(t):
+    """(B, n, leading dimension) of a device row matrix: [B, n] with unit column stride (a slice of a padded buffer included) or an
+    NHWC [B, n, 1, 1] view -- how logits travel, never compacted."""
+    require_gpu(t)
+    if t.dim() == 4 and t.shape[2] == 1 and t.shape[3] == 1:
+        return t.shape[0], t.shape[1], ld_of(t)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError(f"dedark_yolo_amd: expected rows [B, n] with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    B, n = t.shape
+    ld = t.stride(0) if B > 1 else n
+    if ld < n:
+        raise RuntimeError(f"dedark_yolo_amd: rows overlap: shape {tuple(t.shape)} strides {t.stride()}")
+    return B, n, ld
+
+
+def rows_2d(t):
+    """The [B, n] view (strides (ld, 1)) of an NHWC [B, n, 1, 1] view."""
+    return t[:, :, 0, 0] if t.dim() == 4 else t
+
+
+def rows_4d(t, ve):
+    """The NHWC [B, n, 1, 1] view of rows [B, n] whose leading dimension covers n rounded up to `ve` (a gradient written by
+    dy_cls_xent_bwd, pad columns zero); None when `t` is not such a view."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        return None
+    B, n = t.shape
+    ld = t.stride(0)
+    if ld < round_up(n, ve) or t.storage_offset() + (B - 1) * ld + round_up(n, ve) > t.untyped_storage().nbytes() // t.element_size():
+        return None
+    return torch.as_strided(t, (B, n, 1, 1), (ld, 1, ld, ld), t.storage_offset())
+
+
+def cls_xent_fwd(logits, cls):
+    """(loss f32 [1], row_lse f32 [B]) of cross_entropy(logits, cls, reduction='sum') / 64; cls int64 [B] on the device."""
+    B, nc, ld = row_matrix(logits)
+    if cls.dtype != torch.int64 or not cls.is_cuda or cls.numel() != B or not cls.is_contiguous():
+        raise RuntimeError(f"cls_xent_fwd: cls must be a contiguous int64 [{B}] device tensor")
+    lse = torch.empty(B, dtype=torch.float32, device=logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    call("dy_cls_xent_fwd", ptr(logits), ld, dt_id(logits.dtype), ptr(cls), B, nc, ptr(lse), ptr(loss), stream())
+    return loss, lse
+
+
+def cls_xent_bwd(logits, cls, lse, grad_out):
+    """d loss / d logits * grad_out (f32 device scalar): rows [B, nc] of a [B, round_up(nc, vector)] buffer whose pad columns are 0."""
+    B, nc, ld = row_matrix(logits)
+    dld = round_up(nc, vec_elems(logits.dtype))
+    d = torch.empty((B, dld), dtype=logits.dtype, device=logits.device)
+    call("dy_cls_xent_bwd", ptr(logits), ld, dt_id(logits.dtype), ptr(cls), ptr(lse), ptr(grad_out), B, nc, ptr(d), dld, stream())
+    emu_round(d)
+    return d[:, :nc]
+
+
+def cls_softmax(logits):
+    B, nc, ld = row_matrix(logits)
+    probs = torch.empty((B, nc), dtype=torch.float32, device=logits.device)
+    call("dy_cls_softmax", ptr(logits), ld, dt_id(logits.dtype), B, nc, ptr(probs), stream())
+    return probs
+
+
+def cls_topk(scores, k=None):
+    """int32 [B, k] indices of the k (default min(nc, 5)) largest scores per row, descending; ties by ascending index, NaN last."""
+    B, nc, ld = row_matrix(scores)
+    k = min(nc, 5) if k is None else int(k)
+    idx = torch.empty((B, k), dtype=torch.int32, device=scores.device)
+    call("dy_cls_topk", ptr(scores), ld, dt_id(scores.dtype), B, nc, k, ptr(idx), stream())
+    return idx
+
+
+def cls_metrics_update(idx, cls, nc, counts, confusion=None):
+    """counts int64 [3] += (rows, top-1 hits, top-k hits), confusion int32 [nc, nc] [pred][target] += 1 for one batch (device)."""
+    B, k = idx.shape
+    if idx.dtype != torch.int32 or cls.dtype != torch.int64 or cls.numel() != B or counts.dtype != torch.int64 or counts.numel() != 3:
+        raise RuntimeError("cls_metrics_update: idx int32 [B, k], cls int64 [B], counts int64 [3]")
+    if confusion is not None and (confusion.dtype != torch.int32 or tuple(confusion.shape) != (nc, nc) or not confusion.is_contiguous()):
+        raise RuntimeError(f"cls_metrics_update: confusion must be a contiguous int32 [{nc}, {nc}]")
+    for t in (idx, cls, counts):
+        require_gpu(t)
+    call("dy_cls_metrics_update", ptr(idx.contiguous()), k, ptr(cls.contiguous()), B, nc, ptr(counts), ptr(confusion), stream())
+
 # ------------------------------------------------------------------------------------------------ ConvTranspose2d(k=2, s=2)
 class ConvTCtx:
     __slots__ = ("x", "weight", "bias")

@@ -205,7 +205,8 @@ def intersect_dicts(da, db, exclude=()):
 # CPU against tests/golden/g12_ref_skeleton.json (what the reference itself pickles) and, in the build container, by loading the
 # file with the reference (tests/golden/make_ckpt_interop.py).
 _REF_HOME = {"DetectionModel": "ultralytics.nn.tasks", "SegmentationModel": "ultralytics.nn.tasks", "Proto": "ultralytics.nn.modules.block",
-             "Segment": "ultralytics.nn.modules.head", "PoseModel": "ultralytics.nn.tasks", "Pose": "ultralytics.nn.modules.head"}
+             "Segment": "ultralytics.nn.modules.head", "PoseModel": "ultralytics.nn.tasks", "Pose": "ultralytics.nn.modules.head",
+             "ClassificationModel": "ultralytics.nn.tasks", "Classify": "ultralytics.nn.modules.head"}
 _REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
@@ -237,7 +238,8 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "lowlight_recovery": (), "ExtractParameters2": ("output_dim", "channels"), "ConvBlock": (),
               "PConv": ("dim_conv3", "dim_untouched"), "FasterC2f_N": ("c",), "FasterC2f": ("c",), "PconvBottleneck_n": ("add",),
               "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr"),
-              "Pose": ("nc", "nl", "reg_max", "no", "stride", "kpt_shape", "nk")}
+              "Pose": ("nc", "nl", "reg_max", "no", "stride", "kpt_shape", "nk"),
+              "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}
 
@@ -279,9 +281,9 @@ class _RefPickler(pickle._Pickler):
 
 
 def model_class_name(model):
-    """The reference class a model is written as: the model class of its task (nn.tasks.task_table), DetectionModel for any other."""
-    from ..nn.tasks import task_table
-    return next((m.__name__ for m, _, _ in task_table().values() if isinstance(model, m)), "DetectionModel")
+    """The reference class a model is written as: the model class of its task (nn.tasks.all_tasks), DetectionModel for any other."""
+    from ..nn.tasks import all_tasks
+    return next((m.__name__ for m, _, _ in all_tasks().values() if isinstance(model, m)), "DetectionModel")
 
 
 class _RefPickleModule:
@@ -330,6 +332,7 @@ class _RefWriter:
         self.cfg = ed(_FILTER_CFG)                       # ONE object shared by the extractor and the five filters, like filter_cfg.cfg
         self.cfg.__dict__.update(_FILTER_CFG)            # (easydict keeps items and attributes in step)
         self.filters = None
+        self.initialized = True                          # initialize_weights ran (every model class but ClassificationModel)
 
     def tensor(self, key, like):
         v = self.sd.get(key)
@@ -378,7 +381,7 @@ class _RefWriter:
         name = type(mod).__name__
         if type(mod).__module__.startswith("torch.nn."):
             extra = {}
-            if isinstance(mod, (nn.SiLU, nn.LeakyReLU, nn.ReLU, nn.ReLU6, nn.Hardswish)):
+            if self.initialized and isinstance(mod, (nn.SiLU, nn.LeakyReLU, nn.ReLU, nn.ReLU6, nn.Hardswish)):
                 extra["inplace"] = True                   # initialize_weights (ultralytics/utils/torch_utils.py:266-267)
             extra.update(self.graph_attrs(mod, type(mod).__module__ + "." + name))
             return self.torch_leaf(mod, prefix, extra=extra)
@@ -439,7 +442,10 @@ class _RefWriter:
         return self.filters
 
     def model(self, model, args):
-        obj = _standin_type("ultralytics.nn.tasks", model_class_name(model))()
+        cname = model_class_name(model)
+        # ClassificationModel._from_yaml (tasks.py:417-432) neither calls initialize_weights nor sets `inplace`
+        self.initialized = cname != "ClassificationModel"
+        obj = _standin_type("ultralytics.nn.tasks", cname)()
         state = _nn_base_state(self.training)
         layers = list(model.model)
         save = sorted(x % m.i for m in layers for x in ([m.f] if isinstance(m.f, int) else m.f) if x != -1)      # tasks.py:913
@@ -447,6 +453,8 @@ class _RefWriter:
         nc = int(getattr(layers[-1], "nc", yaml_.get("nc", 0)))
         names = getattr(model, "names", None) or {i: f"{i}" for i in range(nc)}
         state.update(current_dedark_A=None, current_IcA=None, yaml=yaml_, save=save, names=dict(names), inplace=True)
+        if not self.initialized:
+            del state["inplace"]
         state["_modules"] = collections.OrderedDict(model=self.torch_leaf(
             model.model, "model.", children=collections.OrderedDict((k, self.convert(c, f"model.{k}.")) for k, c in model.model._modules.items())))
         stride = getattr(model, "stride", None)

@@ -403,6 +403,74 @@ class v8PoseLoss(v8DetectionLoss):
             raise ValueError(f"pose loss: {len(pred_kpts)} keypoint maps for {len(feats)} Detect levels")
         return _PoseLossFn.apply(self, batch, len(feats), *feats, *pred_kpts)
 
+
+class _ClsLossFn(torch.autograd.Function):
+    """loss = f(logits [B, nc], cls int64 [B]) on dy_cls_xent_fwd; backward: dy_cls_xent_bwd, scaled by the incoming gradient
+    on the device (the fp16 loss scale arrives through it)."""
+
+    @staticmethod
+    def forward(ctx, logits, cls):
+        loss, lse = ops.cls_xent_fwd(logits, cls)
+        ctx.keep = (logits, cls, lse)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        logits, cls, lse = ctx.keep
+        ctx.keep = None
+        if gloss.dtype != torch.float32 or not gloss.is_cuda:
+            gloss = gloss.to(logits.device, torch.float32)
+        return ops.cls_xent_bwd(logits, cls, lse, gloss.contiguous()), None
+
+
+CLS_IGNORE_INDEX = -100      # torch.nn.functional.cross_entropy's default ignore_index
+
+
+def check_host_class_labels(cls, nc):
+    """ValueError for a HOST label tensor with an entry outside [0, nc) other than -100, before anything is launched (torch asserts on
+    the device there); device labels are not read back: such a row adds nothing in the kernels."""
+    if not cls.is_cuda:
+        c = cls.reshape(-1)
+        if c.numel() and bool(((c != CLS_IGNORE_INDEX) & ((c < 0) | (c >= nc))).any()):
+            raise ValueError(f"classification labels must lie in [0, {nc}) (or be {CLS_IGNORE_INDEX})")
+
+
+def classify_batch_to_device(batch, device, acc, nc=None):
+    """The classify trainer's and validator's batch step (reference classify/train.py:87-91, classify/val.py:32-37): img to the device
+    as f32 (a uint8 image becomes f32 / 255 there: dy_preprocess_batch, `acc` its f64 [1] scratch accumulator; a float image passes
+    through), cls as a contiguous int64 [B] device tensor; host labels are range-checked when `nc` is given."""
+    img = batch["img"].to(device, non_blocking=True)
+    if img.dtype == torch.uint8:
+        img = img.contiguous()
+        out = torch.empty(img.shape, dtype=torch.float32, device=device)
+        acc.zero_()
+        call("dy_preprocess_batch", ptr(img), ptr(out), None, 1.0, 0, 0, ptr(acc), img.numel(), stream())
+        img = out
+    elif img.dtype != torch.float32:
+        img = img.float()
+    batch["img"] = img
+    if nc is not None:
+        check_host_class_labels(batch["cls"], nc)
+    batch["cls"] = batch["cls"].to(device, non_blocking=True).reshape(-1).long().contiguous()
+    return batch
+
+
+class v8ClassificationLoss:
+    """reference loss.py:380-385: cross_entropy(preds, batch['cls'], reduction='sum') / 64 -- the constant 64, not the batch size.
+    Returns (loss, loss.detach()).  A label of -100 adds nothing; any other label outside [0, nc) raises ValueError when cls
+    arrives on the host (torch asserts on the device there); on the device such a row adds nothing and indexes nothing."""
+
+    def __call__(self, preds, batch):
+        if isinstance(preds, (list, tuple)):
+            preds = preds[1]
+        cls = batch["cls"]
+        nc = preds.shape[1]
+        check_host_class_labels(cls, nc)
+        if cls.dtype != torch.int64 or not cls.is_cuda or cls.dim() != 1 or not cls.is_contiguous():
+            cls = cls.reshape(-1).to(preds.device, torch.int64).contiguous()
+        loss = _ClsLossFn.apply(preds, cls)
+        return loss, loss.detach()
+
 class TaskAlignedAssigner:
     """reference tal.py:59-243 (topk must be 10, alpha 0.5, beta 6.0: the constants compiled into the kernel).
 

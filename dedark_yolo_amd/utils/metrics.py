@@ -268,6 +268,36 @@ class PoseMetrics(_BoxAndTaskMetrics):
     second, keys = "pose", DetMetrics.keys + [k.replace("(B)", "(P)") for k in DetMetrics.keys]
 
 
+class ClassifyMetrics:
+    """Top-1 / top-5 accuracy of the classify validator (reference ClassifyMetrics, metrics.py:1018-1061).  The device keeps the
+    integer counts {rows, top-1 hits, top-5 hits} (dy_cls_metrics_update); `process_counts` turns them into the two accuracies
+    (the reference's float32 mean of 0 / 1 values, exact up to one rounding).  `process(targets, pred)` is the reference's own call
+    on host lists of targets [n] and top-k predictions [n, k].  fitness = (top1 + top5) / 2: the reference's code, not its
+    docstring."""
+    keys = ["metrics/accuracy_top1", "metrics/accuracy_top5"]
+
+    def __init__(self):
+        self.top1, self.top5 = 0, 0
+        self.speed = dict(preprocess=0.0, inference=0.0, loss=0.0, postprocess=0.0)
+
+    def process_counts(self, counts):
+        n, h1, h5 = (int(v) for v in counts)
+        self.top1, self.top5 = (h1 / n, h5 / n) if n else (0.0, 0.0)
+
+    def process(self, targets, pred):
+        pred, targets = torch.cat(list(pred)), torch.cat(list(targets))
+        hit = targets.view(-1, 1).to(pred.dtype) == pred
+        self.process_counts((hit.shape[0], int(hit[:, 0].sum()), int(hit.any(1).sum())))
+
+    @property
+    def fitness(self):
+        return (self.top1 + self.top5) / 2
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], [self.top1, self.top5, self.fitness]))
+
+
 OKS_SIGMA = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0   # metrics.py:15
 
 

@@ -566,6 +566,33 @@ int dy_pose_kpt_decode(const dy_pose_desc* d, int nc, float* y, void* stream);
 int dy_kpt_oks(const float* gt, int N, const float* pred, int M, int pred_dim, const float* area, const float* sigma, int K, float eps,
                float* out, void* stream);
 
+/* ---- classify task (csrc/classify.hip) ----------------------------------------------------------------------------------------------
+ * The device side of Classify (U/nn/modules/head.py:244-260), v8ClassificationLoss (U/utils/loss.py:380-385) and the top-k accuracy of
+ * ClassificationValidator / ClassifyMetrics (U/models/yolo/classify/val.py:39-60, U/utils/metrics.py:197-207, 1018-1061).  dtype =
+ * DY_F32 / DY_BF16 / DY_F16; every operand is addressed through its leading dimension (elements); rows are read with 16-byte loads where
+ * base and leading dimension are 16-byte aligned.  No float atomics: every sum runs in a fixed order. */
+/* AdaptiveAvgPool2d(1) (head.py:250): x NHWC [N][HW][x_ld] -> y [N][y_ld], channels [0, C); f32 accumulation, one rounding.  N <= 65535. */
+int dy_gap_fwd(const void* x, int64_t x_ld, int N, int HW, int C, int dtype, void* y, int64_t y_ld, void* stream);
+/* its adjoint: dx[n][p][c] = dy[n][c] / HW for c < C, overwritten (channels >= C of a pixel are not touched). */
+int dy_gap_bwd(const void* dy, int64_t dy_ld, int N, int HW, int C, int dtype, void* dx, int64_t dx_ld, void* stream);
+/* cross_entropy(logits, cls, reduction='sum') / 64 (loss.py:383-385): row_lse f32 [B] = log sum_j exp(z[b][j]) (one read of each logit),
+ * loss f32 [1] = sum_b (row_lse[b] - z[b][cls[b]]) / 64.  A label outside [0, nc) (torch's ignore_index -100 among them) adds 0 and
+ * indexes nothing. */
+int dy_cls_xent_fwd(const void* logits, int64_t ld, int dtype, const int64_t* cls, int B, int nc, float* row_lse, float* loss, void* stream);
+/* dlogits[b][j] = (exp(z - row_lse[b]) - [j == cls[b]]) * *grad_out / 64 in the logits' dtype, rows [B][dld]; rows with a label outside
+ * [0, nc) and columns nc <= j < dld are written as 0.  grad_out: f32 device scalar. */
+int dy_cls_xent_bwd(const void* logits, int64_t ld, int dtype, const int64_t* cls, const float* row_lse, const float* grad_out, int B,
+                    int nc, void* dlogits, int64_t dld, void* stream);
+/* softmax(1) of the eval head (head.py:259): probs f32 [B][nc], compact. */
+int dy_cls_softmax(const void* logits, int64_t ld, int dtype, int B, int nc, float* probs, void* stream);
+/* argsort(1, descending=True)[:, :k] (val.py:57): idx int32 [B][k], 1 <= k <= min(nc, 8).  Equal values rank by ascending index (the
+ * order of a stable descending sort; -0 equals +0); NaN ranks below every number. */
+int dy_cls_topk(const void* scores, int64_t ld, int dtype, int B, int nc, int k, int32_t* idx, void* stream);
+/* ClassifyMetrics.process / ConfusionMatrix.process_cls_preds (metrics.py:1043-1048, 197-207) for one batch: counts int64 [3] += (rows,
+ * rows with idx[b][0] == cls[b], rows with any idx[b][:] == cls[b]); confusion int32 [nc][nc] (or null): [idx[b][0]][cls[b]] += 1.
+ * Integer atomics.  A row whose label is outside [0, nc) is not counted. */
+int dy_cls_metrics_update(const int32_t* idx, int k, const int64_t* cls, int B, int nc, int64_t* counts, int32_t* confusion, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,12 @@
-"""Training throughput of a segment or pose model (yolov8l-seg / yolov8l-pose by default) on synthetic batches: bench.py's batch
-law plus the task's labels -- overlap index masks at the proto resolution (imgsz / 4), or 17 keypoints per box (normalised xy
-around the box centre, visibility 0 / 1 / 2) -- one train_step per iteration (preprocess + forward + detection and task loss +
-backward + optimizer), timed with device events after a warm-up.  Prints one JSON line.
+"""Training throughput of a segment, pose or classify model (yolov8l-seg / yolov8l-pose / yolov8l-cls by default) on synthetic
+batches: bench.py's batch law plus the task's labels -- overlap index masks at the proto resolution (imgsz / 4), or 17 keypoints per
+box (normalised xy around the box centre, visibility 0 / 1 / 2); for classify uint8 images and one int64 class per image (nc =
+1000) -- one train_step per iteration (preprocess + forward + loss + backward + optimizer), timed with device events after a
+warm-up.  Prints one JSON line.
 
-  python tools/task_bench.py --task {segment,pose} [--model yolov8l-seg.yaml | yolov8l-pose.yaml] [--imgsz 640] [--batch 32]
-                             [--dtype bf16] [--steps 10 | 15] [--warmup 3] [--deterministic] [--dump-outputs DIR] [--loader]
+  python tools/task_bench.py --task {segment,pose,classify} [--model yolov8l-seg.yaml | yolov8l-pose.yaml | yolov8l-cls.yaml]
+                             [--imgsz 640 | 224] [--batch 32 | 128] [--dtype bf16] [--steps 10 | 15] [--warmup 3]
+                             [--deterministic] [--dump-outputs DIR] [--loader]
 
 `--deterministic` trains on the one-stream schedule (two runs of one build then give the same bits); `--dump-outputs DIR` writes
 what the last timed step computed as DIR/*.npy (bench.dump_outputs), to compare two builds output for output.
@@ -88,7 +90,17 @@ def loader_batches(task, B, S):
 
 
 # task -> (default model, default timed steps, what adds the task's labels to a batch, model class in nn.tasks)
-TASKS = dict(segment=("yolov8l-seg.yaml", 10, add_masks, "SegmentationModel"), pose=("yolov8l-pose.yaml", 15, add_keypoints, "PoseModel"))
+TASKS = dict(segment=("yolov8l-seg.yaml", 10, add_masks, "SegmentationModel"), pose=("yolov8l-pose.yaml", 15, add_keypoints, "PoseModel"),
+             classify=("yolov8l-cls.yaml", 15, None, "ClassificationModel"))
+
+
+def classify_batch(i, B, S, nc):
+    """uint8 images and one class per image, resident on the device"""
+    import numpy as np
+    import torch
+    g = np.random.default_rng(100 + i)
+    return dict(img=torch.from_numpy(g.integers(0, 256, (B, 3, S, S), dtype=np.uint8)).cuda(),
+                cls=torch.from_numpy(g.integers(0, nc, B).astype(np.int64)).cuda())
 
 
 def main():
@@ -99,8 +111,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), required=True)
     ap.add_argument("--model")
-    ap.add_argument("--imgsz", type=int, default=640)
-    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--imgsz", type=int, help="default 640 (classify: 224)")
+    ap.add_argument("--batch", type=int, help="default 32 (classify: 128)")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--steps", type=int)
     ap.add_argument("--warmup", type=int, default=3)
@@ -110,7 +122,10 @@ def main():
     a = ap.parse_args()
     model, steps, add_labels, model_cls = TASKS[a.task]
     model, steps = a.model or model, a.steps or steps
-    nc, S, B = 20, a.imgsz, a.batch
+    cls_task = a.task == "classify"
+    nc, S, B = (1000 if cls_task else 20), a.imgsz or (224 if cls_task else 640), a.batch or (128 if cls_task else 32)
+    if cls_task and a.loader:
+        ap.error("--loader: there is no classify data pipeline (DeviceAugmentLoader serves detect, segment and pose)")
     torch.manual_seed(0)          # the initial weights: with the seeded batches, two runs start from the same state
     tr = DetectionTrainer(get_cfg(dict(model=model, dtype=a.dtype, optimizer="SGD", batch=B, imgsz=S, deterministic=a.deterministic)))
     tr.setup(getattr(tasks, model_cls)(tasks.yaml_model_load(model), nc=nc))
@@ -127,6 +142,9 @@ def main():
     else:
         batches = []
         for i in range(4):
+            if cls_task:
+                batches.append(classify_batch(i, B, S, nc))
+                continue
             b = bench.synth_batch(100 + i, B, S, nc, "cpu")
             b.pop("gamma")
             add_labels(b, i, B, S)
@@ -150,7 +168,7 @@ def main():
         bench.dump_outputs(a.dump_outputs, tr, loss, items)
     print(json.dumps(dict(metric=f"{a.task} training img/s", model=model, imgsz=S, batch=B, dtype=a.dtype, steps=steps,
                           warmup=a.warmup, ms_per_step=round(ms, 3), value=round(B * 1000.0 / ms, 2),
-                          items=[round(float(v), 4) for v in items],
+                          items=[round(float(v), 4) for v in items.reshape(-1)],
                           **(dict(loader=True, dataset_instances_per_image=10, label_rows_per_batch=round(sum(rows) / len(rows), 1),
                                   host_loader_ms_per_step=round(1e3 * sum(host) / len(host), 3)) if a.loader else {}))))
 
