@@ -15,53 +15,7 @@
 #include "dy_common.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
-
-// pipelined wide-channel bf16 kernel (conv_v2.hip)
-bool dy_conv_v2_eligible(const dy_conv_desc* d);
-int dy_conv_v2_launch(const dy_conv_desc* d, int mode, void* stream);
-int dy_conv_v2_launch_classes(const dy_conv_desc* classes, int ncls, void* stream);
-// band kernel for 3x3 / stride-1 bf16 convs (conv_v3.hip)
-bool dy_conv_v5_eligible(const dy_conv_desc* d, int mode);
-int dy_conv_v5_launch(const dy_conv_desc* d, int mode, void* stream);
-bool dy_conv_v4_eligible(const dy_conv_desc* d, int mode);
-int dy_conv_v4_launch(const dy_conv_desc* d, int mode, void* stream);
-bool dy_conv_v5_classes_eligible(const dy_conv_desc* classes, int ncls);
-int dy_conv_v5_launch_classes(const dy_conv_desc* classes, int ncls, void* stream);
-bool dy_conv_v4_classes_eligible(const dy_conv_desc* classes, int ncls);
-int dy_conv_v4_launch_classes(const dy_conv_desc* classes, int ncls, void* stream);
-bool dy_conv_v3_eligible(const dy_conv_desc* d);
-int dy_conv_v3_launch(const dy_conv_desc* d, int mode, void* stream);
-// pipelined bf16 weight gradient (wgrad_v2.hip)
-bool dy_wgrad_v2_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, long M, long x_ld, long dz_ld);
-int dy_wgrad_v2_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Ho, int Wo,
-                       int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, float* scratch,
-                       long scratch_elems, float* g_oihw, int dtype, void* stream);
-// whole-input windows = fully connected layers (dense.hip)
-bool dy_dense_fwd_eligible(const dy_conv_desc* d);
-int dy_dense_fwd_launch(const dy_conv_desc* d, void* stream);
-bool dy_dense_dgrad_eligible(const dy_conv_desc* d);
-int dy_dense_dgrad_launch(const dy_conv_desc* d, void* stream);
-bool dy_dense_wgrad_eligible(int Hi, int Wi, int Ho, int Wo, int KH, int KW, int pad, int dil);
-int dy_dense_wgrad_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Cout, int Cin,
-                          float* g_oihw, int dtype, void* stream);
-// band weight gradient for the 64-channel 3x3 layers (wgrad_v3.hip)
-bool dy_wgrad_v4_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, long M, int N, int Hi, int Wi, int Ho, int Wo, long x_ld,
-                          long dz_ld, long scratch_elems);
-int dy_wgrad_v4_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Ho, int Wo,
-                       int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, float* scratch,
-                       long scratch_elems, float* g_oihw, int dtype, void* stream);
-bool dy_wgrad_v3_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, int stride, int pad, int dil, int N, int Hi, int Wi,
-                          long x_ld, long dz_ld, long scratch_elems);
-int dy_wgrad_v3_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Cout_pad, int Cout,
-                       int Cin, float* scratch, long scratch_elems, float* g_oihw, int dtype, void* stream);
-// direct stem kernels (conv_small.hip)
-bool dy_conv_px_eligible(const dy_conv_desc* d);
-bool dy_conv_px_has_shape(const dy_conv_desc* d);
-int dy_conv_px_launch(const dy_conv_desc* d, void* stream);
-bool dy_conv_stem_fwd_eligible(const dy_conv_desc* d);
-int dy_conv_stem_fwd_launch(const dy_conv_desc* d, void* stream);
-bool dy_conv_small_dgrad_eligible(const dy_conv_desc* d);
-int dy_conv_small_dgrad_launch(const dy_conv_desc* d, void* stream);
+#include "conv_route.h"
 
 namespace {
 
@@ -94,22 +48,8 @@ struct ConvP {
   DyParityCls cls[4];
 };
 
-template <typename PP>
-__device__ inline long dst_offset(const PP& p, long m) {
-  if (p.dst_row == 0) return m * p.dst_ld;
-  const long HWd = (long)p.Hd * p.Wd;
-  const long img = m / HWd;
-  const int rem = (int)(m - img * HWd);
-  const int oh = rem / p.Wd, ow = rem - oh * p.Wd;
-  return img * p.dst_img + (long)oh * p.dst_row + (long)ow * p.dst_ld;
-}
-
-__device__ inline int xcd_remap(int bid, int nblk) {
-  // bijective: blocks b, b+8, ... share an XCD; give each XCD a contiguous chunk of tile ids
-  int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (bid >> 3);
-}
+using dy_route::dst_offset;
+using dy_route::xcd_remap;
 
 // ---- MFMA over one staged K-step. LDS rows hold 128 bytes of K. ------------------------------------------------
 template <typename T, int TM, int TN>
@@ -873,53 +813,17 @@ __global__ void unpack_wgrad_kernel(const float* __restrict__ dwp, float* __rest
   }
 }
 
-void fill_convp(ConvP& p, const dy_conv_desc* d, const dy_conv_desc* classes, int ncls) {
-  p.ncls = 0;
-  if (ncls > 1) {
-    p.ncls = ncls;
-    for (int c = 0; c < ncls; ++c) {
-      const dy_conv_desc& q = classes[c];
-      DyParityCls& k = p.cls[c];
-      k.dst = (char*)q.dst; k.M = (long)q.N * q.Hd * q.Wd; k.Hd = q.Hd; k.Wd = q.Wd; k.KH = q.KH; k.KW = q.KW; k.pad = q.pad;
-      k.kh0 = q.kh0; k.kw0 = q.kw0; k.Ktot = q.KH * q.KW * q.Cs; k.blk0 = 0; k._r = 0;
-    }
-  }
-  p.src = (const char*)d->src; p.src_ld = d->src_ld; p.N = d->N; p.Hs = d->Hs; p.Ws = d->Ws; p.Cs = d->Cs;
-  p.w = (const char*)d->w; p.dst = (char*)d->dst; p.dst_ld = d->dst_ld; p.Hd = d->Hd; p.Wd = d->Wd; p.Cd = d->Cd;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.scale = d->scale; p.shift = d->shift; p.act = d->act; p.stats = d->stats; p.accumulate = d->accumulate;
-  p.M = (long)d->N * d->Hd * d->Wd;
-  p.Ktot = d->KH * d->KW * d->Cs;
-  static const int ablate = dy_env("DY_ABLATE") ? atoi(dy_env("DY_ABLATE")) : 0;
-  p.ablate = ablate;
-  p.dst_row = d->dst_row_stride;
-  p.dst_img = d->dst_img_stride ? d->dst_img_stride : (long)d->Hd * d->dst_row_stride;
-  if (d->KHf > 0) {
-    p.kh0 = d->kh0; p.khs = d->kh_step; p.kw0 = d->kw0; p.kws = d->kw_step; p.KWf = d->KWf;
-    p.w_row = (long)d->KHf * d->KWf * d->Cs;
-  } else {
-    p.kh0 = 0; p.khs = 1; p.kw0 = 0; p.kws = 1; p.KWf = d->KW;
-    p.w_row = p.Ktot;
-  }
-}
-
 template <typename T, int MODE>
-int launch_conv(const dy_conv_desc* d, hipStream_t st, const dy_conv_desc* classes = nullptr, int ncls = 0) {
+int launch_conv(const dy_conv_desc* d, hipStream_t st, const dy_conv_desc* classes, int ncls) {
   ConvP p;
-  fill_convp(p, d, classes, ncls);
+  dy_route::fill_parity_classes(p, classes, ncls);
+  dy_route::fill_gather(p, d);
   constexpr int BM = 128;
   const int tiles_m = dy_cdiv(p.M, BM);
   auto blocks = [&](int bn) {                 // tiles_n / nblk (+ the block ranges of the classes)
     p.tiles_n = dy_cdiv(d->Cd, bn);
     p.nblk = tiles_m * p.tiles_n;
-    if (p.ncls > 1) {
-      long acc = 0;
-      for (int c = 0; c < p.ncls; ++c) {
-        p.cls[c].blk0 = (int)acc;
-        acc += dy_cdiv(p.cls[c].M, BM) * p.tiles_n;
-      }
-      p.nblk = (int)acc;
-    }
+    if (p.ncls > 1) p.nblk = dy_route::number_parity_blocks(p, BM, dy_route::CLS_SEQUENTIAL);
   };
   dy_note_kernel(d->Cd <= 32 ? "conv_igemm_kernel<BN=32>" : (d->Cd <= 64 ? "conv_igemm_kernel<BN=64>" : "conv_igemm_kernel<BN=128>"));
   if (d->Cd <= 32) {
@@ -954,17 +858,11 @@ bool thin_eligible(const dy_conv_desc* d, int mode, bool parity_class = false) {
 
 int launch_thin(const dy_conv_desc* d, int mode, hipStream_t st, const dy_conv_desc* classes = nullptr, int ncls = 0) {
   ConvP p;
-  fill_convp(p, d, classes, ncls);
+  dy_route::fill_parity_classes(p, classes, ncls);
+  dy_route::fill_gather(p, d);
   p.tiles_n = 1;
   p.nblk = dy_cdiv(p.M, THIN_BM);
-  if (p.ncls > 1) {
-    long acc = 0;
-    for (int c = 0; c < p.ncls; ++c) {
-      p.cls[c].blk0 = (int)acc;
-      acc += dy_cdiv(p.cls[c].M, THIN_BM);
-    }
-    p.nblk = (int)acc;
-  }
+  if (p.ncls > 1) p.nblk = dy_route::number_parity_blocks(p, THIN_BM, dy_route::CLS_SEQUENTIAL);
   dy_note_kernel("conv_thin_kernel");
 #define THIN(C_, M_) conv_thin_kernel<C_, M_><<<p.nblk, NTHREADS, 0, st>>>(p)
   const int c16 = d->Cs / 16;
@@ -973,6 +871,15 @@ int launch_thin(const dy_conv_desc* d, int mode, hipStream_t st, const dy_conv_d
 #undef THIN
   DY_LAUNCH_CHECK();
   return 0;
+}
+
+// the register-staged kernel takes every problem: its instantiation by dtype and mode
+int launch_generic(const dy_conv_desc* d, int mode, hipStream_t st, const dy_conv_desc* classes = nullptr, int ncls = 0) {
+  if (mode == 0)
+    return d->dtype == DY_F32 ? launch_conv<float, 0>(d, st, classes, ncls)
+                              : (d->dtype == DY_F16 ? launch_conv<f16_t, 0>(d, st, classes, ncls) : launch_conv<bf16_t, 0>(d, st, classes, ncls));
+  return d->dtype == DY_F32 ? launch_conv<float, 1>(d, st, classes, ncls)
+                            : (d->dtype == DY_F16 ? launch_conv<f16_t, 1>(d, st, classes, ncls) : launch_conv<bf16_t, 1>(d, st, classes, ncls));
 }
 
 int check_conv(const dy_conv_desc* d, const char* who) {
@@ -989,6 +896,48 @@ int check_conv(const dy_conv_desc* d, const char* who) {
   return 0;
 }
 
+// ---- the routes, in the order they are tried ----------------------------------------------------------------------------------------
+// One row per kernel family: the first row that serves the call site and whose `eligible` accepts the problem launches it.  The last
+// row accepts everything.  The parity-class launches of a stride-2 data gradient (all classes in ONE launch) are chosen in
+// dgrad_dispatch; its per-class fallback comes back here with SITE_CLASS.
+enum : unsigned {
+  SITE_FWD = 1,          // dy_conv2d_fwd (mode 0)
+  SITE_DGRAD_HEAD = 2,   // dy_conv2d_dgrad, before the parity split of a stride-2 problem (mode 1)
+  SITE_DGRAD = 4,        // dy_conv2d_dgrad, whole problem (mode 1)
+  SITE_CLASS = 8,        // one parity class of a stride-2 data gradient: a forward-style problem (mode 0)
+};
+
+struct Route {
+  bool (*eligible)(const dy_conv_desc* d, int mode);
+  int (*launch)(const dy_conv_desc* d, int mode, void* stream);
+  unsigned sites;
+  bool fuses_add;        // a data gradient's optional `add_src` view is added in the kernel's epilogue
+};
+
+const Route kRoutes[] = {
+    {dy_dense_fwd_eligible, dy_dense_fwd_launch, SITE_FWD, false},                                   // dense.hip: whole-input window
+    {dy_conv_stem_fwd_eligible, dy_conv_stem_fwd_launch, SITE_FWD, false},                           // conv_small.hip: network stem
+    {dy_dense_dgrad_eligible, dy_dense_dgrad_launch, SITE_DGRAD_HEAD, false},                        // dense.hip
+    {dy_conv_small_dgrad_eligible, dy_conv_small_dgrad_launch, SITE_DGRAD_HEAD, false},              // conv_small.hip: stem / thin 1x1 dgrads
+    {dy_conv_px_eligible, dy_conv_px_launch, SITE_FWD | SITE_DGRAD, true},                           // conv_px.hip: pixel-streaming 1x1
+    {dy_conv_v4_eligible, dy_conv_v4_launch, SITE_FWD | SITE_DGRAD | SITE_CLASS, true},              // conv_v4.hip: 256 x 256 tiles
+    {dy_conv_v5_eligible, dy_conv_v5_launch, SITE_FWD | SITE_DGRAD | SITE_CLASS, true},              // conv_v5.hip: 256 x 128 / 64, band
+    {dy_conv_v3_eligible, dy_conv_v3_launch, SITE_FWD | SITE_DGRAD, false},                          // conv_v3.hip: older 3x3 band kernel
+    {dy_conv_v2_eligible, dy_conv_v2_launch, SITE_FWD | SITE_DGRAD | SITE_CLASS, false},             // conv_v2.hip: pipelined, any window
+    {[](const dy_conv_desc* d, int mode) { return thin_eligible(d, mode); },                         // this file: conv_thin_kernel
+     [](const dy_conv_desc* d, int mode, void* stream) { return launch_thin(d, mode, (hipStream_t)stream); }, SITE_FWD | SITE_DGRAD, false},
+    {[](const dy_conv_desc*, int) { return true; },                                                  // this file: conv_igemm_kernel
+     [](const dy_conv_desc* d, int mode, void* stream) { return launch_generic(d, mode, (hipStream_t)stream); },
+     SITE_FWD | SITE_DGRAD | SITE_CLASS, false},
+};
+
+const Route* pick_route(const dy_conv_desc* d, unsigned site) {
+  const int mode = (site & (SITE_DGRAD_HEAD | SITE_DGRAD)) ? 1 : 0;
+  for (const Route& r : kRoutes)
+    if ((r.sites & site) && r.eligible(d, mode)) return &r;
+  return nullptr;        // SITE_DGRAD_HEAD only: the other sites end in the generic kernel
+}
+
 }  // namespace
 
 extern "C" int dy_conv2d_fwd(const dy_conv_desc* d, void* stream) {
@@ -996,18 +945,10 @@ extern "C" int dy_conv2d_fwd(const dy_conv_desc* d, void* stream) {
   const int ho = (d->Hs + 2 * d->pad - d->dil * (d->KH - 1) - 1) / d->stride + 1;
   const int wo = (d->Ws + 2 * d->pad - d->dil * (d->KW - 1) - 1) / d->stride + 1;
   DY_CHECK(ho == d->Hd && wo == d->Wd, "dy_conv2d_fwd: dst %dx%d does not match conv output %dx%d", d->Hd, d->Wd, ho, wo);
-  if (dy_dense_fwd_eligible(d)) return dy_dense_fwd_launch(d, stream);
-  if (dy_conv_stem_fwd_eligible(d)) return dy_conv_stem_fwd_launch(d, stream);
-  if (dy_conv_px_eligible(d) && dy_conv_px_has_shape(d) && !d->accumulate && !d->add_src) return dy_conv_px_launch(d, stream);
-  if (dy_conv_v4_eligible(d, 0)) return dy_conv_v4_launch(d, 0, stream);
-  if (dy_conv_v5_eligible(d, 0)) return dy_conv_v5_launch(d, 0, stream);
-  if (dy_conv_v3_eligible(d)) return dy_conv_v3_launch(d, 0, stream);
-  if (dy_conv_v2_eligible(d)) return dy_conv_v2_launch(d, 0, stream);
-  hipStream_t st = (hipStream_t)stream;
-  if (thin_eligible(d, 0)) return launch_thin(d, 0, st);
-  return d->dtype == DY_F32 ? launch_conv<float, 0>(d, st) : (d->dtype == DY_F16 ? launch_conv<f16_t, 0>(d, st) : launch_conv<bf16_t, 0>(d, st));
+  return pick_route(d, SITE_FWD)->launch(d, 0, stream);
 }
 
+// `*added` comes in false and is set only where the route taken fused d->add_src (the head routes and the parity split never do)
 static int dgrad_dispatch(const dy_conv_desc* d, void* stream, bool* added) {
   if (int e = check_conv(d, "dy_conv2d_dgrad")) return e;
   // src = dz (conv output geometry), dst = dx (conv input geometry)
@@ -1016,8 +957,7 @@ static int dgrad_dispatch(const dy_conv_desc* d, void* stream, bool* added) {
   DY_CHECK(ho == d->Hs && wo == d->Ws, "dy_conv2d_dgrad: dz %dx%d does not match conv output %dx%d", d->Hs, d->Ws, ho, wo);
   DY_CHECK(d->stats == nullptr, "dy_conv2d_dgrad: stats unsupported");
   DY_CHECK(d->KHf == 0 && d->dst_row_stride == 0, "dy_conv2d_dgrad: tap subsets / strided destinations are forward-only");
-  if (dy_dense_dgrad_eligible(d)) return dy_dense_dgrad_launch(d, stream);
-  if (dy_conv_small_dgrad_eligible(d)) return dy_conv_small_dgrad_launch(d, stream);
+  if (const Route* r = pick_route(d, SITE_DGRAD_HEAD)) return r->launch(d, 1, stream);
   DY_CHECK(d->dst_planar == nullptr, "dy_conv2d_dgrad: dst_planar is only supported by the direct stem kernel (bf16, 3x3 s2 p1, Cd == 8)");
   static const bool no_parity = dy_env("DY_NO_PARITY_DGRAD") != nullptr;
   if (d->stride == 2 && d->dil == 1 && !no_parity) {
@@ -1064,7 +1004,7 @@ static int dgrad_dispatch(const dy_conv_desc* d, void* stream, bool* added) {
         bool all_v2 = true, none_v2 = true;
         for (int i = 0; i < nc; ++i) {
           r[i] = c[nc - 1 - i];
-          const bool e2 = dy_conv_v2_eligible(&r[i]);
+          const bool e2 = dy_conv_v2_eligible(&r[i], 0);
           all_v2 = all_v2 && e2;
           none_v2 = none_v2 && !e2;
         }
@@ -1080,34 +1020,18 @@ static int dgrad_dispatch(const dy_conv_desc* d, void* stream, bool* added) {
           bool thin = true;
           for (int i = 0; i < nc; ++i) thin = thin && thin_eligible(&r[i], 0, true);
           if (thin) return launch_thin(&r[0], 0, (hipStream_t)stream, r, nc);
-          if (class_tiles <= 256)
-            return d->dtype == DY_F32 ? launch_conv<float, 0>(&r[0], (hipStream_t)stream, r, nc)
-                 : (d->dtype == DY_F16 ? launch_conv<f16_t, 0>(&r[0], (hipStream_t)stream, r, nc)
-                                       : launch_conv<bf16_t, 0>(&r[0], (hipStream_t)stream, r, nc));
+          if (class_tiles <= 256) return launch_generic(&r[0], 0, (hipStream_t)stream, r, nc);
         }
       }
       for (int i = nc - 1; i >= 0; --i) {    // heaviest class (most taps) first
-        const dy_conv_desc* q = &c[i];
-        int e;
-        if (dy_conv_v4_eligible(q, 0)) e = dy_conv_v4_launch(q, 0, stream);
-        else if (dy_conv_v5_eligible(q, 0)) e = dy_conv_v5_launch(q, 0, stream);
-        else if (dy_conv_v2_eligible(q)) e = dy_conv_v2_launch(q, 0, stream);
-        else e = q->dtype == DY_F32 ? launch_conv<float, 0>(q, (hipStream_t)stream)
-                                    : (q->dtype == DY_F16 ? launch_conv<f16_t, 0>(q, (hipStream_t)stream) : launch_conv<bf16_t, 0>(q, (hipStream_t)stream));
-        if (e) return e;
+        if (int e = pick_route(&c[i], SITE_CLASS)->launch(&c[i], 0, stream)) return e;
       }
       return 0;
     }
   }
-  // the pixel-streaming 1x1 kernel and the two large-tile kernels add the optional `add_src` view in their epilogue
-  if (dy_conv_px_eligible(d) && dy_conv_px_has_shape(d)) { *added = true; return dy_conv_px_launch(d, stream); }
-  if (dy_conv_v4_eligible(d, 1)) { *added = true; return dy_conv_v4_launch(d, 1, stream); }
-  if (dy_conv_v5_eligible(d, 1)) { *added = true; return dy_conv_v5_launch(d, 1, stream); }
-  if (dy_conv_v3_eligible(d)) return dy_conv_v3_launch(d, 1, stream);
-  if (dy_conv_v2_eligible(d)) return dy_conv_v2_launch(d, 1, stream);
-  hipStream_t st = (hipStream_t)stream;
-  if (thin_eligible(d, 1)) return launch_thin(d, 1, st);
-  return d->dtype == DY_F32 ? launch_conv<float, 1>(d, st) : (d->dtype == DY_F16 ? launch_conv<f16_t, 1>(d, st) : launch_conv<bf16_t, 1>(d, st));
+  const Route* r = pick_route(d, SITE_DGRAD);
+  *added = r->fuses_add;
+  return r->launch(d, 1, stream);
 }
 
 extern "C" int dy_conv2d_dgrad(const dy_conv_desc* d, void* stream) {
@@ -1167,6 +1091,20 @@ int launch_wgrad(WgP p, float* scratch, long scratch_elems, float* g_oihw, int C
   DY_LAUNCH_CHECK();
   return 0;
 }
+
+int wgrad_generic(const DyWgradArgs& a, void* stream) {
+  WgP p;
+  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad;
+  p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
+  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil; p.part = a.scratch;
+  p.M = (long)a.N * a.Ho * a.Wo;
+  p.Ktot = a.KH * a.KW * a.Cin_pad;
+  p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  return a.dtype == DY_F32 ? launch_wgrad<float>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st)
+                           : (a.dtype == DY_F16 ? launch_wgrad<f16_t>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st)
+                                                : launch_wgrad<bf16_t>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st));
+}
 }  // namespace
 
 extern "C" int dy_conv2d_wgrad(const void* x, int64_t x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, int64_t dz_ld,
@@ -1181,27 +1119,13 @@ extern "C" int dy_conv2d_wgrad(const void* x, int64_t x_ld, int N, int Hi, int W
   DY_CHECK(((uintptr_t)x) % 16 == 0 && ((uintptr_t)dz) % 16 == 0, "dy_conv2d_wgrad: pointer not 16-byte aligned");
   const int ho = (Hi + 2 * pad - dil * (KH - 1) - 1) / stride + 1, wo = (Wi + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
   DY_CHECK(ho == Ho && wo == Wo, "dy_conv2d_wgrad: dz %dx%d does not match conv output %dx%d", Ho, Wo, ho, wo);
-  if (dy_dense_wgrad_eligible(Hi, Wi, Ho, Wo, KH, KW, pad, dil))
-    return dy_dense_wgrad_launch(x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Cout, Cin, g_oihw, dtype, stream);
-  if (dy_wgrad_v3_eligible(dtype, Cin_pad, Cout_pad, KH, KW, stride, pad, dil, N, Hi, Wi, x_ld, dz_ld, scratch_elems))
-    return dy_wgrad_v3_launch(x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Cout_pad, Cout, Cin, scratch, scratch_elems, g_oihw, dtype, stream);
-  if (dy_wgrad_v4_eligible(dtype, Cin_pad, Cout_pad, KH, KW, (long)N * Ho * Wo, N, Hi, Wi, Ho, Wo, x_ld, dz_ld, scratch_elems))
-    return dy_wgrad_v4_launch(x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Ho, Wo, Cout_pad, KH, KW, stride, pad, dil, Cout, Cin, scratch,
-                              scratch_elems, g_oihw, dtype, stream);
-  if (dy_wgrad_v2_eligible(dtype, Cin_pad, Cout_pad, KH, KW, (long)N * Ho * Wo, x_ld, dz_ld))
-    return dy_wgrad_v2_launch(x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Ho, Wo, Cout_pad, KH, KW, stride, pad, dil, Cout, Cin, scratch,
-                              scratch_elems, g_oihw, dtype, stream);
-  WgP p;
-  p.x = (const char*)x; p.x_ld = x_ld; p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin_pad;
-  p.dz = (const char*)dz; p.dz_ld = dz_ld; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout_pad;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil; p.part = scratch;
-  p.M = (long)N * Ho * Wo;
-  p.Ktot = KH * KW * Cin_pad;
-  p.pointwise = (KH == 1 && KW == 1 && stride == 1 && pad == 0) ? 1 : 0;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == DY_F32 ? launch_wgrad<float>(p, scratch, scratch_elems, g_oihw, Cout, Cin, st)
-                         : (dtype == DY_F16 ? launch_wgrad<f16_t>(p, scratch, scratch_elems, g_oihw, Cout, Cin, st)
-                                            : launch_wgrad<bf16_t>(p, scratch, scratch_elems, g_oihw, Cout, Cin, st));
+  const DyWgradArgs a = {x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Ho, Wo, Cout_pad, KH, KW, stride, pad, dil, Cout, Cin,
+                         scratch, scratch_elems, g_oihw, dtype};
+  if (dy_dense_wgrad_eligible(a)) return dy_dense_wgrad_launch(a, stream);                 // dense.hip
+  if (dy_wgrad_v3_eligible(a)) return dy_wgrad_v3_launch(a, stream);                       // wgrad_v3.hip
+  if (dy_wgrad_v4_eligible(a)) return dy_wgrad_v4_launch(a, stream);                       // wgrad_v4.hip
+  if (dy_wgrad_v2_eligible(a)) return dy_wgrad_v2_launch(a, stream);                       // wgrad_v2.hip
+  return wgrad_generic(a, stream);                                                         // this file: conv_wgrad_kernel
 }
 
 extern "C" int dy_pack_weight(const float* w, void* packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int KH, int KW,

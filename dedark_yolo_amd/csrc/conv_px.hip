@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace px {
 
@@ -164,10 +165,18 @@ __global__ __launch_bounds__(NT) void px1x1_kernel(const P p) {
 
 }  // namespace px
 
+// (kb, ns) pairs px1x1_kernel is instantiated for (dy_conv_px_launch)
+static bool px_has_shape(const dy_conv_desc* d) {
+  const int kb = d->Cs / 32, ns = d->Cd / 32;
+  return (kb == 2 && ns == 2) || (kb == 4 && ns == 2) || (kb == 4 && ns == 4) || (kb == 10 && ns == 4) || (kb == 4 && ns == 10) || (kb == 2 && ns == 4) ||
+         kb == 8;
+}
+
 // Raw-output 1x1 / stride-1 layers on an unchanged pixel grid, K in {64, 128, 320}, N a multiple of 32, the weight image within LDS;
 // BatchNorm sums only up to 128 output channels (they live in registers); long pixel ranges (the layers of the 160x160 / 320x320 stages);
 // K = 256 with up to 1024 output channels in chunks of 256 (the wide 1x1 data gradients of the 80x80 stage; no sums).
-bool dy_conv_px_eligible(const dy_conv_desc* d) {
+// mode 0: the forward dispatch takes it for plain stores only; a data gradient (mode 1) may also accumulate and add the `add_src` view
+bool dy_conv_px_eligible(const dy_conv_desc* d, int mode) {
   static const bool off = dy_env("DY_NO_CONV_PX") != nullptr;
   if (off || (d->dtype != DY_BF16 && d->dtype != DY_F16)) return false;
   if (!(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->KHf == 0 && d->dst_row_stride == 0 && d->dst && !d->dst_planar &&
@@ -183,7 +192,8 @@ bool dy_conv_px_eligible(const dy_conv_desc* d) {
   if (d->stats && (d->Cd > 128 || d->accumulate || d->add_src)) return false;
   if ((d->src_ld * 2) % 16 != 0 || (d->dst_ld * 2) % 16 != 0 || ((uintptr_t)d->dst) % 16 != 0 || ((uintptr_t)d->src) % 16 != 0) return false;
   if (d->add_src && ((d->add_src_ld * 2) % 16 != 0 || ((uintptr_t)d->add_src) % 16 != 0)) return false;
-  return (long)d->N * d->Hd * d->Wd >= 262144;
+  if ((long)d->N * d->Hd * d->Wd < 262144 || !px_has_shape(d)) return false;
+  return mode == 1 || (!d->accumulate && !d->add_src);
 }
 
 // (the statistics variant keeps 2 x 8 x NS register sums: it exists for NS <= 4 only -- dy_conv_px_eligible admits BatchNorm sums up to 128
@@ -217,7 +227,7 @@ static int px_go(const px::P& p, bool stats, size_t shm, unsigned blocks, hipStr
   return 0;
 }
 
-int dy_conv_px_launch(const dy_conv_desc* d, void* stream) {
+int dy_conv_px_launch(const dy_conv_desc* d, int, void* stream) {
   px::P p;
   p.x = (const char*)d->src; p.x_ld = d->src_ld; p.w = (const char*)d->w; p.y = (char*)d->dst; p.y_ld = d->dst_ld;
   p.M = (long)d->N * d->Hd * d->Wd; p.K = d->Cs; p.N = d->Cd; p.accumulate = d->accumulate;
@@ -250,10 +260,4 @@ int dy_conv_px_launch(const dy_conv_desc* d, void* stream) {
   if (rc) return rc;
   DY_LAUNCH_CHECK();
   return 0;
-}
-
-bool dy_conv_px_has_shape(const dy_conv_desc* d) {
-  const int kb = d->Cs / 32, ns = d->Cd / 32;
-  return (kb == 2 && ns == 2) || (kb == 4 && ns == 2) || (kb == 4 && ns == 4) || (kb == 10 && ns == 4) || (kb == 4 && ns == 10) || (kb == 2 && ns == 4) ||
-         kb == 8;
 }

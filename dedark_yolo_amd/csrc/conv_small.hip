@@ -10,6 +10,7 @@
 // K = 16..64 per parity class) took 1.08 ms on the 32x640x640 stem; this kernel is bounded by ~315 MB of traffic.
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -404,7 +405,7 @@ int launch_small_dgrad(const dy_conv_desc* d, hipStream_t st) {
 }  // namespace
 
 // Taken for the raw-output forward (training: BatchNorm follows; also plain inference convs without affine / activation)
-bool dy_conv_stem_fwd_eligible(const dy_conv_desc* d) {
+bool dy_conv_stem_fwd_eligible(const dy_conv_desc* d, int) {
   static const bool off = dy_env("DY_NO_CONV_SMALL") != nullptr;
   return !off && (d->dtype == DY_BF16 || d->dtype == DY_F16) && d->KH == 3 && d->KW == 3 && d->stride == 2 && d->pad == 1 && d->dil == 1 &&
          d->Cs == 8 && d->KHf == 0 && d->dst_row_stride == 0 && d->dst && (d->Cd == 16 || d->Cd == 32 || d->Cd == 64) && !d->scale &&
@@ -412,7 +413,7 @@ bool dy_conv_stem_fwd_eligible(const dy_conv_desc* d) {
          ((uintptr_t)d->dst) % 16 == 0 && (long)d->N * d->Hd * d->Wd < (1L << 31);
 }
 
-int dy_conv_stem_fwd_launch(const dy_conv_desc* d, void* stream) {
+int dy_conv_stem_fwd_launch(const dy_conv_desc* d, int, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const long groups = ((long)d->N * d->Hd * d->Wd + 15) / 16;
   long blocks = (groups + 3) / 4;
@@ -437,7 +438,7 @@ static bool thin_eligible(const dy_conv_desc* d) {
          d->Hs == d->Hd && d->Ws == d->Wd;
 }
 
-bool dy_conv_small_dgrad_eligible(const dy_conv_desc* d) {
+bool dy_conv_small_dgrad_eligible(const dy_conv_desc* d, int) {
   static const bool off = dy_env("DY_NO_CONV_SMALL") != nullptr;
   if (off) return false;
   if (thin_eligible(d)) return true;
@@ -446,7 +447,7 @@ bool dy_conv_small_dgrad_eligible(const dy_conv_desc* d) {
          ((d->dst_planar && d->dst_valid_channels > 0 && d->dst_valid_channels <= 8) || (d->dst && (d->dst_ld * 2) % 16 == 0));
 }
 
-int dy_conv_small_dgrad_launch(const dy_conv_desc* d, void* stream) {
+int dy_conv_small_dgrad_launch(const dy_conv_desc* d, int, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (thin_eligible(d)) {
     const long M = (long)d->N * d->Hd * d->Wd;

@@ -14,6 +14,7 @@
 #include "dy_common.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace v2 {
 
@@ -60,20 +61,8 @@ struct P {
   DyParityCls cls[4];
 };
 
-__device__ inline long dst_offset(const P& p, long m) {
-  if (p.dst_row == 0) return m * p.dst_ld;
-  const long HWd = (long)p.Hd * p.Wd;
-  const long img = m / HWd;
-  const int rem = (int)(m - img * HWd);
-  const int oh = rem / p.Wd, ow = rem - oh * p.Wd;
-  return img * p.dst_img + (long)oh * p.dst_row + (long)ow * p.dst_ld;
-}
-
-__device__ inline int xcd_remap(int bid, int nblk) {
-  int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (bid >> 3);
-}
+using dy_route::dst_offset;
+using dy_route::xcd_remap;
 
 // SMALLC: Cs is not a multiple of 64 (the n-scale layers, 8..48 channels): a 64-wide K-step then spans several taps, so every
 // lane derives (tap, channel) of ITS 16-byte chunk; K = KH*KW*Cs is padded to the step with zero-page loads.
@@ -316,14 +305,7 @@ int launch_t(P& p, hipStream_t st) {
   }
   p.tiles_n = dy_cdiv(p.Cd, BN);
   p.nblk = dy_cdiv(p.M, BM) * p.tiles_n;
-  if (p.ncls > 1) {
-    long acc = 0;
-    for (int c = 0; c < p.ncls; ++c) {
-      p.cls[c].blk0 = (int)acc;
-      acc += dy_cdiv(p.cls[c].M, BM) * p.tiles_n;
-    }
-    p.nblk = (int)acc;
-  }
+  if (p.ncls > 1) p.nblk = dy_route::number_parity_blocks(p, BM, dy_route::CLS_SEQUENTIAL);
   static char name[64];
   if (!name[0]) snprintf(name, sizeof(name), "v2::conv_kernel<%d, %d, %d, %s, %d>", BM, BN, MODE, SMALLC ? "true" : "false", NSTAGE);
   dy_note_kernel(name);
@@ -354,7 +336,7 @@ bool dy_conv_prefers_256(const dy_conv_desc* d) {
   return d->Cd >= 256 && ((M + 255) / 256) * tn >= 192 && tn * 256 * 4 <= (long)d->Cd * 5;
 }
 
-bool dy_conv_v2_eligible(const dy_conv_desc* d) {
+bool dy_conv_v2_eligible(const dy_conv_desc* d, int) {
   static const bool off = dy_env("DY_NO_CONV_V2") != nullptr;
   if (off) return false;
   const long M = (long)d->N * d->Hd * d->Wd;
@@ -380,34 +362,9 @@ int dy_conv_v2_launch_classes(const dy_conv_desc* classes, int ncls, void* strea
 static int v2_launch_impl(const dy_conv_desc* d, int mode, const dy_conv_desc* classes, int ncls, void* stream) {
   v2::P p;
   p.f16 = d->dtype == DY_F16;
-  p.ncls = 0;
-  if (ncls > 1) {
-    DY_CHECK(ncls <= 4, "conv_v2: at most 4 classes");
-    p.ncls = ncls;
-    for (int c = 0; c < ncls; ++c) {
-      const dy_conv_desc& q = classes[c];
-      DyParityCls& k = p.cls[c];
-      k.dst = (char*)q.dst; k.M = (long)q.N * q.Hd * q.Wd; k.Hd = q.Hd; k.Wd = q.Wd; k.KH = q.KH; k.KW = q.KW; k.pad = q.pad;
-      k.kh0 = q.kh0; k.kw0 = q.kw0; k.Ktot = q.KH * q.KW * q.Cs; k.blk0 = 0; k._r = 0;
-    }
-  }
-  p.src = (const char*)d->src; p.src_ld = d->src_ld; p.N = d->N; p.Hs = d->Hs; p.Ws = d->Ws; p.Cs = d->Cs;
-  p.w = (const char*)d->w; p.dst = (char*)d->dst; p.dst_ld = d->dst_ld; p.Hd = d->Hd; p.Wd = d->Wd; p.Cd = d->Cd;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.scale = d->scale; p.shift = d->shift; p.act = d->act; p.stats = d->stats; p.accumulate = d->accumulate;
-  p.M = (long)d->N * d->Hd * d->Wd;
-  p.Ktot = d->KH * d->KW * d->Cs;
-  static const int ablate = dy_env("DY_ABLATE") ? atoi(dy_env("DY_ABLATE")) : 0;
-  p.ablate = ablate;
-  p.dst_row = d->dst_row_stride;
-  p.dst_img = d->dst_img_stride ? d->dst_img_stride : (long)d->Hd * d->dst_row_stride;
-  if (d->KHf > 0) {
-    p.kh0 = d->kh0; p.khs = d->kh_step; p.kw0 = d->kw0; p.kws = d->kw_step; p.KWf = d->KWf;
-    p.w_row = (long)d->KHf * d->KWf * d->Cs;
-  } else {
-    p.kh0 = 0; p.khs = 1; p.kw0 = 0; p.kws = 1; p.KWf = d->KW;
-    p.w_row = p.Ktot;
-  }
+  DY_CHECK(ncls <= 4, "conv_v2: at most 4 classes");
+  dy_route::fill_parity_classes(p, classes, ncls);
+  dy_route::fill_gather(p, d);
   hipStream_t st = (hipStream_t)stream;
   const bool wide = d->Cd > 64;
   if (d->Cs % 64 != 0) {

@@ -15,6 +15,7 @@
 #include "dy_common.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace v3 {
 
@@ -58,11 +59,7 @@ struct P {
   int f16;              // payload is IEEE half instead of bf16 (host side: selects the instantiation)
 };
 
-__device__ inline int xcd_remap(int bid, int nblk) {
-  int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (bid >> 3);
-}
+using dy_route::xcd_remap;
 
 template <int BN, int MODE, typename T = bf16_t>
 __global__ __launch_bounds__(NT) void conv3x3_kernel(P p) {
@@ -345,9 +342,7 @@ extern "C" int dy_debug_conv3_stamps(unsigned long long* out) {
 }
 
 // the band kernel takes 3x3 / stride 1 / pad 1 / dil 1 bf16 convs whose band (and its double buffer) fit in LDS
-bool dy_conv_prefers_256(const dy_conv_desc* d);      // conv_v2.hip
-
-bool dy_conv_v3_eligible(const dy_conv_desc* d) {
+bool dy_conv_v3_eligible(const dy_conv_desc* d, int) {
   static const bool off = dy_env("DY_NO_CONV_V3") != nullptr;
   if (off) return false;
   if (!((d->dtype == DY_BF16 || d->dtype == DY_F16) && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1)) return false;

@@ -32,6 +32,7 @@
 #include "dy_common.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace v4 {
 
@@ -76,20 +77,8 @@ struct P {
   DyParityCls cls[4];
 };
 
-__device__ inline int xcd_remap(int bid, int nblk) {
-  int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (bid >> 3);
-}
-
-__device__ inline long dst_offset(const P& p, long m) {
-  if (p.dst_row == 0) return m * p.dst_ld;
-  const long HWd = (long)p.Hd * p.Wd;
-  const long img = m / HWd;
-  const int rem = (int)(m - img * HWd);
-  const int oh = rem / p.Wd, ow = rem - oh * p.Wd;
-  return img * p.dst_img + (long)oh * p.dst_row + (long)ow * p.dst_ld;
-}
+using dy_route::xcd_remap;
+using dy_route::dst_offset;
 
 // ABL: compile-time ablation mask for tools/v4_diag (the library only instantiates ABL = 0): 1 no DMA inside the loop, 2 no MFMA,
 // 4 no LDS fragment reads, 8 no stagger between the wave groups, 16 no A-side DMA, 32 no B-side DMA, 64 no epilogue stores,
@@ -501,13 +490,7 @@ static int v4_variant(const dy_conv_desc* d, int mode) {
   if (!(d->Cs % 64 == 0 && d->KH * d->KW <= 25)) return 0;
   if (mode == 1 && d->stride != 1) return 0;
   if ((d->src_ld * 2) % 16 != 0 || (d->dst_ld * 2) % 16 != 0 || ((uintptr_t)d->dst) % 16 != 0) return 0;
-  const long src_bytes = (((long)d->N * d->Hs * d->Ws - 1) * d->src_ld + d->Cs) * 2;
-  const long w_row = d->KHf > 0 ? (long)d->KHf * d->KWf * d->Cs : (long)d->KH * d->KW * d->Cs;
-  const long w_bytes = (long)d->Cd * w_row * 2;
-  // activation descriptor: extent + the most negative tap offset folded into its base (v4_launch: a_min) stays below 2^31, the bit
-  // that marks a padded lane
-  const long halo = ((long)d->KH * d->dil * d->Ws + (long)d->KW * d->dil) * d->src_ld * 2;
-  if (!(src_bytes + halo <= 0x7fffffffL && w_bytes <= 0x3fffffffL)) return 0;
+  if (!dy_route::dma_extents_ok(d, d->KH, d->KW, d->dil)) return 0;
   const long tiles_m = ((long)d->N * d->Hd * d->Wd + 255) / 256;
   const long t256 = (d->Cd + 255) / 256;
   // K >= 512.  (K >= 256 is 11 % faster on the 1024->256 1x1 data gradient at 80x80 -- 487 -> 434 us -- and equal on 256->256; it was
@@ -515,14 +498,6 @@ static int v4_variant(const dy_conv_desc* d, int mode) {
   static const long min_k = dy_env("DY_V4_MINK") ? atol(dy_env("DY_V4_MINK")) : 512;
   if (d->Cd >= 192 && t256 * 256 * 4 <= (long)d->Cd * 5 && tiles_m * t256 >= 192 && (long)d->KH * d->KW * d->Cs >= min_k) return 256;
   return 0;
-}
-
-#ifdef DY_V4_DIAG_BUILD
-static
-#endif
-bool dy_conv_v4_eligible(const dy_conv_desc* d, int mode) {
-  static const bool off = dy_env("DY_NO_CONV_V4") != nullptr;
-  return !off && v4_variant(d, mode) != 0;
 }
 
 // Tile quantisation: T tiles on the chip's CUs (one block per CU) run in ceil(T / CUs) rounds, and a last round that is mostly empty
@@ -577,57 +552,15 @@ static int v4_launch(const dy_conv_desc* d, int mode, void* stream, int force_va
   DY_CHECK(variant != 0, "conv_v4: problem not eligible");
   DY_CHECK((long)d->N * d->Hd * d->Wd < (1L << 31), "conv_v4: too many output pixels");
   v4::P p;
-  p.src = (const char*)d->src; p.w = (const char*)d->w; p.dst = (char*)d->dst;
-  p.src_ld = d->src_ld; p.dst_ld = d->dst_ld;
-  p.src_bytes = (unsigned)((((long)d->N * d->Hs * d->Ws - 1) * d->src_ld + d->Cs) * 2);
-  p.Hs = d->Hs; p.Ws = d->Ws; p.Cs = d->Cs; p.Hd = d->Hd; p.Wd = d->Wd; p.Cd = d->Cd;
-  p.KH = d->KH; p.KW = d->KW;
-  if (mode == 0) {
-    p.stride = d->stride; p.dh0 = -d->pad; p.dhs = d->dil; p.dw0 = -d->pad; p.dws = d->dil;
-  } else {               // stride-1 data gradient: dx[h] += dz[h + pad - kh*dil] * w[kh]
-    p.stride = 1; p.dh0 = d->pad; p.dhs = -d->dil; p.dw0 = d->pad; p.dws = -d->dil;
-  }
-  if (d->KHf > 0) {
-    p.kh0 = d->kh0; p.khs = d->kh_step; p.kw0 = d->kw0; p.kws = d->kw_step; p.KWf = d->KWf;
-    p.w_row = (long)d->KHf * d->KWf * d->Cs;
-  } else {
-    p.kh0 = 0; p.khs = 1; p.kw0 = 0; p.kws = 1; p.KWf = d->KW;
-    p.w_row = (long)d->KH * d->KW * d->Cs;
-  }
-  p.w_bytes = (unsigned)((long)d->Cd * p.w_row * 2);
-  {
-    const int dh_lo = p.dhs < 0 ? p.dh0 + p.dhs * (p.KH - 1) : p.dh0, dw_lo = p.dws < 0 ? p.dw0 + p.dws * (p.KW - 1) : p.dw0;
-    const long lo = ((long)dh_lo * p.Ws + dw_lo) * p.src_ld * 2;
-    p.a_min = lo < 0 ? (int)lo : 0;
-  }
-  p.scale = d->scale; p.shift = d->shift; p.act = d->act; p.stats = d->stats; p.accumulate = d->accumulate;
-  // (bit 1: an output beyond 128 MB is streamed past the L2 with non-temporal stores -- its lines would evict the operand lines the
-  //  taps re-read, and whoever reads it next streams it from memory anyway)
-  if ((long)d->N * d->Hd * d->Wd * d->Cd * 2 > (128L << 20)) p.accumulate |= 2;
-  p.M = (long)d->N * d->Hd * d->Wd;
-  p.add_src = mode == 1 ? (const char*)d->add_src : nullptr; p.add_src_ld = d->add_src_ld;
+  dy_route::fill_taps_extents(p, d, mode);
   p.nk = d->KH * d->KW * d->Cs / v4::BK;
-  p.dst_row = d->dst_row_stride;
-  p.dst_img = d->dst_img_stride ? d->dst_img_stride : (long)d->Hd * d->dst_row_stride;
   p.tiles_n = dy_cdiv(d->Cd, variant);
   v4_split(p.M, p.tiles_n, p.n_full, p.rb_tail, p.nblk);
-  p.ncls = 0;
-  if (ncls > 1) {
-    DY_CHECK(ncls <= 4 && mode == 0, "conv_v4: at most 4 forward-style classes");
-    p.ncls = ncls;
-    int slot = 0;
-    for (int c = 0; c < ncls; ++c) {
-      const dy_conv_desc& q = classes[c];
-      DyParityCls& k = p.cls[c];
-      k.dst = (char*)q.dst; k.M = (long)q.N * q.Hd * q.Wd; k.Hd = q.Hd; k.Wd = q.Wd; k.KH = q.KH; k.KW = q.KW; k.pad = q.pad;
-      k.kh0 = q.kh0; k.kw0 = q.kw0; k.Ktot = q.KH * q.KW * q.Cs;
-      DY_CHECK(k.M < (1L << 31), "conv_v4: too many output pixels");
-      const int tiles = (int)dy_cdiv(k.M, (long)v4::BM) * p.tiles_n;
-      k.blk0 = slot;
-      k._r = dy_cdiv(tiles, 8);
-      slot += k._r;
-    }
-    p.nblk = 8 * slot;
+  DY_CHECK(ncls <= 1 || (ncls <= 4 && mode == 0), "conv_v4: at most 4 forward-style classes");
+  dy_route::fill_parity_classes(p, classes, ncls);
+  if (p.ncls > 1) {
+    for (int c = 0; c < p.ncls; ++c) DY_CHECK(p.cls[c].M < (1L << 31), "conv_v4: too many output pixels");
+    p.nblk = dy_route::number_parity_blocks(p, v4::BM, dy_route::CLS_XCD_SLOTS);
     p.n_full = p.nblk; p.rb_tail = 4;
   }
   constexpr int EPI256 = dy_epi::row_image_bytes<256, 256>();
@@ -648,7 +581,12 @@ static int v4_launch(const dy_conv_desc* d, int mode, void* stream, int force_va
   return 0;
 }
 
-#ifndef DY_V4_DIAG_BUILD
+#ifndef DY_V4_DIAG_BUILD          // tools/v4_diag compiles this file into itself and calls v4_launch directly: no public names there
+bool dy_conv_v4_eligible(const dy_conv_desc* d, int mode) {
+  static const bool off = dy_env("DY_NO_CONV_V4") != nullptr;
+  return !off && v4_variant(d, mode) != 0;
+}
+
 int dy_conv_v4_launch(const dy_conv_desc* d, int mode, void* stream) {
   return d->dtype == DY_F16 ? v4_launch<0, f16_t>(d, mode, stream) : v4_launch<0, bf16_t>(d, mode, stream);
 }
@@ -662,21 +600,12 @@ bool dy_conv_v4_classes_eligible(const dy_conv_desc* c, int ncls) {
   const dy_conv_desc* d = &c[0];
   if (d->dtype != DY_BF16 && d->dtype != DY_F16) return false;
   if (!(d->Cs % 64 == 0 && d->KHf > 0 && d->KHf * d->KWf <= 25 && d->stride == 1)) return false;
-  const long src_bytes = (((long)d->N * d->Hs * d->Ws - 1) * d->src_ld + d->Cs) * 2;
-  const long w_bytes = (long)d->Cd * d->KHf * d->KWf * d->Cs * 2;
-  const long halo = ((long)d->KHf * d->Ws + d->KWf) * d->src_ld * 2;
-  if (!(src_bytes + halo <= 0x7fffffffL && w_bytes <= 0x3fffffffL)) return false;
+  if (!dy_route::dma_extents_ok(d, d->KHf, d->KWf, 1) || !dy_route::parity_classes_uniform(c, ncls)) return false;
   const long t256 = (d->Cd + 255) / 256;
   if (!(d->Cd >= 192 && t256 * 256 * 4 <= (long)d->Cd * 5)) return false;
   long tiles = 0, kmax = 0;
   for (int i = 0; i < ncls; ++i) {
     const dy_conv_desc& q = c[i];
-    if (q.src != d->src || q.w != d->w || q.Cs != d->Cs || q.Cd != d->Cd || q.dtype != d->dtype || q.stride != 1 || q.dil != 1 || q.KHf != d->KHf ||
-        q.KWf != d->KWf || q.kh_step != d->kh_step || q.kw_step != d->kw_step || q.dst_ld != d->dst_ld || q.dst_row_stride != d->dst_row_stride ||
-        q.dst_img_stride != d->dst_img_stride || q.src_ld != d->src_ld || q.accumulate != d->accumulate || q.scale || q.shift || q.stats ||
-        q.act != DY_ACT_NONE)
-      return false;
-    if ((q.dst_ld * 2) % 16 != 0 || ((uintptr_t)q.dst) % 16 != 0 || (q.src_ld * 2) % 16 != 0) return false;
     tiles += (((long)q.N * q.Hd * q.Wd + 255) / 256) * t256;
     const long k = (long)q.KH * q.KW * q.Cs;
     kmax = k > kmax ? k : kmax;

@@ -5,6 +5,7 @@
 // (forward) or thread (gradients); the three kernels are latency-trivial and together move < 2 MB.
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -78,12 +79,12 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(const T* __restrict__ 
 
 }  // namespace
 
-bool dy_dense_fwd_eligible(const dy_conv_desc* d) {
+bool dy_dense_fwd_eligible(const dy_conv_desc* d, int) {
   return d->Hd == 1 && d->Wd == 1 && d->KH == d->Hs && d->KW == d->Ws && d->pad == 0 && d->dil == 1 && d->src_ld == d->Cs &&
          d->stats == nullptr && !d->accumulate && d->KHf == 0 && d->dst_row_stride == 0 && d->KH * d->KW > 1 && d->dst;
 }
 
-int dy_dense_fwd_launch(const dy_conv_desc* d, void* stream) {
+int dy_dense_fwd_launch(const dy_conv_desc* d, int, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int K = d->KH * d->KW * d->Cs;
   const long x_img = (long)d->Hs * d->Ws * d->src_ld;
@@ -101,12 +102,12 @@ int dy_dense_fwd_launch(const dy_conv_desc* d, void* stream) {
   return 0;
 }
 
-bool dy_dense_dgrad_eligible(const dy_conv_desc* d) {
+bool dy_dense_dgrad_eligible(const dy_conv_desc* d, int) {
   return d->Hs == 1 && d->Ws == 1 && d->KH == d->Hd && d->KW == d->Wd && d->pad == 0 && d->dil == 1 && d->stride == 1 && d->KHf == 0 &&
          d->dst_row_stride == 0 && d->KH * d->KW > 1 && d->dst && !d->dst_planar;
 }
 
-int dy_dense_dgrad_launch(const dy_conv_desc* d, void* stream) {
+int dy_dense_dgrad_launch(const dy_conv_desc* d, int, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int HW = d->Hd * d->Wd;
   const unsigned grid = (unsigned)(((long)d->N * HW * d->Cd + 255) / 256);
@@ -123,21 +124,20 @@ int dy_dense_dgrad_launch(const dy_conv_desc* d, void* stream) {
   return 0;
 }
 
-bool dy_dense_wgrad_eligible(int Hi, int Wi, int Ho, int Wo, int KH, int KW, int pad, int dil) {
-  return Ho == 1 && Wo == 1 && KH == Hi && KW == Wi && pad == 0 && dil == 1 && KH * KW > 1;
+bool dy_dense_wgrad_eligible(const DyWgradArgs& a) {
+  return a.Ho == 1 && a.Wo == 1 && a.KH == a.Hi && a.KW == a.Wi && a.pad == 0 && a.dil == 1 && a.KH * a.KW > 1;
 }
 
-int dy_dense_wgrad_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Cout, int Cin,
-                          float* g_oihw, int dtype, void* stream) {
+int dy_dense_wgrad_launch(const DyWgradArgs& a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int HW = Hi * Wi;
-  const unsigned grid = (unsigned)(((long)Cout * HW * Cin_pad + 255) / 256);
-  if (dtype == DY_F32)
-    dense_wgrad_kernel<float><<<grid, 256, 0, st>>>((const float*)x, x_ld, (const float*)dz, dz_ld, g_oihw, N, HW, Cin, Cin_pad, Cout);
-  else if ((dtype) == DY_F16)
-    dense_wgrad_kernel<f16_t><<<grid, 256, 0, st>>>((const f16_t*)x, x_ld, (const f16_t*)dz, dz_ld, g_oihw, N, HW, Cin, Cin_pad, Cout);
+  const int HW = a.Hi * a.Wi;
+  const unsigned grid = (unsigned)(((long)a.Cout * HW * a.Cin_pad + 255) / 256);
+  if (a.dtype == DY_F32)
+    dense_wgrad_kernel<float><<<grid, 256, 0, st>>>((const float*)a.x, a.x_ld, (const float*)a.dz, a.dz_ld, a.g_oihw, a.N, HW, a.Cin, a.Cin_pad, a.Cout);
+  else if (a.dtype == DY_F16)
+    dense_wgrad_kernel<f16_t><<<grid, 256, 0, st>>>((const f16_t*)a.x, a.x_ld, (const f16_t*)a.dz, a.dz_ld, a.g_oihw, a.N, HW, a.Cin, a.Cin_pad, a.Cout);
   else
-    dense_wgrad_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, x_ld, (const bf16_t*)dz, dz_ld, g_oihw, N, HW, Cin, Cin_pad, Cout);
+    dense_wgrad_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a.x, a.x_ld, (const bf16_t*)a.dz, a.dz_ld, a.g_oihw, a.N, HW, a.Cin, a.Cin_pad, a.Cout);
   DY_LAUNCH_CHECK();
   return 0;
 }

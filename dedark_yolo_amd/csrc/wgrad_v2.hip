@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace wg2 {
 
@@ -276,40 +277,38 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ p
 
 }  // namespace wg2
 
-bool dy_wgrad_v2_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, long M, long x_ld, long dz_ld) {
+bool dy_wgrad_v2_eligible(const DyWgradArgs& a) {
   static const bool off = dy_env("DY_NO_WGRAD_V2") != nullptr;
   if (off) return false;
-  const long Ktot = (long)KH * KW * Cin_pad;
+  const long M = (long)a.N * a.Ho * a.Wo, Ktot = (long)a.KH * a.KW * a.Cin_pad;
   // Cout <= 32 stays on the register-staged kernel (32->32 3x3 at 80x80: 59 us there, 66 us here: 3/4 of the co tile would be
   // padding); DY_WG2_NARROW=<min Cout> overrides for experiments.
   static const int exp_narrow = dy_env("DY_WG2_NARROW") ? atoi(dy_env("DY_WG2_NARROW")) : 0;
   const int min_co = exp_narrow > 0 ? exp_narrow : 64;
-  return (dtype == DY_BF16 || dtype == DY_F16) && Cin_pad % 8 == 0 && Cout_pad % 8 == 0 && Cout_pad >= min_co && Ktot >= 64 && M >= 4096 && M < (1L << 31) &&
-         (x_ld * 2) % 16 == 0 && (dz_ld * 2) % 16 == 0;
+  return (a.dtype == DY_BF16 || a.dtype == DY_F16) && a.Cin_pad % 8 == 0 && a.Cout_pad % 8 == 0 && a.Cout_pad >= min_co && Ktot >= 64 && M >= 4096 &&
+         M < (1L << 31) && (a.x_ld * 2) % 16 == 0 && (a.dz_ld * 2) % 16 == 0;
 }
 
-int dy_wgrad_v2_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Ho, int Wo,
-                       int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, float* scratch,
-                       long scratch_elems, float* g_oihw, int dtype, void* stream) {
+int dy_wgrad_v2_launch(const DyWgradArgs& a, void* stream) {
   using namespace wg2;
   // Tile choice (tools/conv_bench, B = 64).  The kernel streams its operands from L2 / Infinity Cache every step, so the tile's
   // flop-per-byte decides: 256 x 256 (128 flop/B, 128 KiB, one block per CU) when the layer has >= 256 output channels
   // (256->256 3x3 at 40x40: 271 -> 200 us = 604 TF; 256->512 3x3 s2: 567 -> 386 us), otherwise 128 x 128 on 4 waves with two
   // co-resident blocks (64 KiB each), which beats 256 x 128 x 3 stages.  DY_WG2_EXP = 1 / 2 / 3 forces 256x128x3 / 256x256 / 128x128.
   static const int exp_env = dy_env("DY_WG2_EXP") ? atoi(dy_env("DY_WG2_EXP")) : 0;
-  const int exp_mode = exp_env == 3 ? 0 : (exp_env > 0 ? exp_env : (Cout_pad >= 256 ? 2 : 0));
+  const int exp_mode = exp_env == 3 ? 0 : (exp_env > 0 ? exp_env : (a.Cout_pad >= 256 ? 2 : 0));
   P p;
-  p.x = (const char*)x; p.x_ld = x_ld; p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin_pad;
-  p.dz = (const char*)dz; p.dz_ld = dz_ld; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout_pad;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil; p.part = scratch;
-  p.M = (long)N * Ho * Wo;
-  p.Ktot = KH * KW * Cin_pad;
-  p.pointwise = (KH == 1 && KW == 1 && stride == 1 && pad == 0) ? 1 : 0;
+  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad;
+  p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
+  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil; p.part = a.scratch;
+  p.M = (long)a.N * a.Ho * a.Wo;
+  p.Ktot = a.KH * a.KW * a.Cin_pad;
+  p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
   const int bp = (exp_mode == 1 || exp_mode == 2 || exp_mode == 4) ? 256 : 128;
   const int BQ = exp_mode == 2 ? 256 : 128;
   const int nstage = exp_mode == 1 ? 3 : 2;      // exp_mode 4: 256 x 128 x 2 stages (96 KiB)
   const int shmem = nstage * (bp / 128 + BQ / 128) * IMG;
-  const bool f16 = dtype == DY_F16;
+  const bool f16 = a.dtype == DY_F16;
 #define WG2_FN(...) (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<__VA_ARGS__, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<__VA_ARGS__, bf16_t>))
   const void* fn = exp_mode == 1 ? WG2_FN(256, 128, 3) : exp_mode == 2 ? WG2_FN(256, 256, 2) : exp_mode == 4 ? WG2_FN(256, 128, 2) : WG2_FN(128, 128, 2);
 #undef WG2_FN
@@ -324,7 +323,7 @@ int dy_wgrad_v2_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
     configured |= cfg_bit;
   }
   const int tiles_p = dy_cdiv(p.Ktot, bp);
-  p.tiles_q = dy_cdiv(Cout_pad, BQ);
+  p.tiles_q = dy_cdiv(a.Cout_pad, BQ);
   const int tiles = tiles_p * p.tiles_q;
   // about one wave of blocks over the chip (two 128x128 blocks per CU), at least 8 steps per block, and the slabs must fit the
   // scratch buffer.  1,024 blocks were no faster on the YOLOv8-n shapes (sum of 19 layers 913 us vs 908 us) and write + re-read
@@ -334,8 +333,8 @@ int dy_wgrad_v2_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
   long splits = (target + tiles - 1) / tiles;
   const long max_splits = (p.M + 8L * BKP - 1) / (8L * BKP);
   if (splits > max_splits) splits = max_splits;
-  const long fit = scratch_elems / ((long)tiles * bp * BQ);
-  DY_CHECK(fit >= 1, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", scratch_elems, (long)tiles * bp * BQ);
+  const long fit = a.scratch_elems / ((long)tiles * bp * BQ);
+  DY_CHECK(fit >= 1, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", a.scratch_elems, (long)tiles * bp * BQ);
   if (splits > fit) splits = fit;
   if (splits < 1) splits = 1;
   if (splits > 65535) splits = 65535;
@@ -356,8 +355,8 @@ int dy_wgrad_v2_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
   else WG2_GO(256, 128, 128, 2);
 #undef WG2_GO
   DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(Cout, 32), p.Ktot), 256, 0, st>>>(scratch, (int)splits, tiles, p.tiles_q, bp, BQ, Cout, Cin, Cin_pad,
-                                                                            KH, KW, p.Ktot, g_oihw);
+  reduce_kernel<<<dim3(dy_cdiv(a.Cout, 32), p.Ktot), 256, 0, st>>>(a.scratch, (int)splits, tiles, p.tiles_q, bp, BQ, a.Cout, a.Cin, a.Cin_pad,
+                                                                            a.KH, a.KW, p.Ktot, a.g_oihw);
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 // diagnostics only (tools/gpu/wg3_ablate.sh builds variant libraries with -DWG3_ABLATE=n; results are wrong, only the time matters):
 // 1 = DMA + one barrier per row only, 2 = DMA + MFMAs on register constants (no fragment reads), 3 = the bare MFMA loop (no DMA either)
@@ -277,57 +278,55 @@ static int wg3_strips(int Wi, int Cin_pad) {
   return 0;
 }
 
-bool dy_wgrad_v3_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, int stride, int pad, int dil, int N, int Hi, int Wi,
-                          long x_ld, long dz_ld, long scratch_elems) {
+bool dy_wgrad_v3_eligible(const DyWgradArgs& a) {
   static const bool off = dy_env("DY_NO_WGRAD_V3") != nullptr;
   if (off) return false;
-  if (!((dtype == DY_BF16 || dtype == DY_F16) && (Cin_pad == 64 || Cin_pad == 128) && Cout_pad % 64 == 0 && Cout_pad <= 128 && KH == 3 && KW == 3 && stride == 1 &&
-        pad == 1 && dil == 1))
+  if (!((a.dtype == DY_BF16 || a.dtype == DY_F16) && (a.Cin_pad == 64 || a.Cin_pad == 128) && a.Cout_pad % 64 == 0 && a.Cout_pad <= 128 && a.KH == 3 && a.KW == 3 &&
+        a.stride == 1 && a.pad == 1 && a.dil == 1))
     return false;
-  if ((x_ld * 2) % 16 != 0 || (dz_ld * 2) % 16 != 0) return false;
-  if (wg3_strips(Wi, Cin_pad) == 0) return false;       // the six row buffers must fit LDS, in up to four column strips
+  if ((a.x_ld * 2) % 16 != 0 || (a.dz_ld * 2) % 16 != 0) return false;
+  if (wg3_strips(a.Wi, a.Cin_pad) == 0) return false;       // the six row buffers must fit LDS, in up to four column strips
   // worth it when the pixel loop is long enough to amortise the slab per block (64->64 at 40x40, B = 32 is not)
   static const long min_m = dy_env("DY_WG3_MINM") ? atol(dy_env("DY_WG3_MINM")) : 131072;
-  return (long)N * Hi * Wi >= min_m &&
-         scratch_elems >= (long)N * wg3_strips(Wi, Cin_pad) * (Cout_pad / wg3::CO) * 9 * Cin_pad * wg3::CO;     // >= 1 block per image and strip
+  return (long)a.N * a.Hi * a.Wi >= min_m &&
+         a.scratch_elems >= (long)a.N * wg3_strips(a.Wi, a.Cin_pad) * (a.Cout_pad / wg3::CO) * 9 * a.Cin_pad * wg3::CO;     // >= 1 block per image and strip
 }
 
-int dy_wgrad_v3_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Cout_pad, int Cout,
-                       int Cin, float* scratch, long scratch_elems, float* g_oihw, int dtype, void* stream) {
+int dy_wgrad_v3_launch(const DyWgradArgs& a, void* stream) {
   using namespace wg3;
   P p;
-  p.x = (const char*)x; p.x_ld = x_ld; p.dz = (const char*)dz; p.dz_ld = dz_ld;
-  p.N = N; p.H = Hi; p.W = Wi;
-  p.nstrip = wg3_strips(Wi, Cin_pad);
+  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld;
+  p.N = a.N; p.H = a.Hi; p.W = a.Wi;
+  p.nstrip = wg3_strips(a.Wi, a.Cin_pad);
   DY_CHECK(p.nstrip >= 1, "wgrad_v3: image rows too wide for the LDS row buffers");
-  p.SW = p.nstrip == 1 ? Wi : ((Wi + p.nstrip - 1) / p.nstrip + 15) / 16 * 16;
-  p.nstrip = (Wi + p.SW - 1) / p.SW;
+  p.SW = p.nstrip == 1 ? a.Wi : ((a.Wi + p.nstrip - 1) / p.nstrip + 15) / 16 * 16;
+  p.nstrip = (a.Wi + p.SW - 1) / p.SW;
   p.PW = (p.SW + 2 + 15) / 16 * 16;
   p.XW = p.PW + 8;
   p.co_stride = 0;
-  p.part = scratch;
-  const int ny = Cout_pad / CO;
+  p.part = a.scratch;
+  const int ny = a.Cout_pad / CO;
   // ONE round of blocks over the 256 CUs (1 block per CU: the row buffers take 131 KB), whole rows of one image each: every block
   // parks a 295 / 147 KB slab, so a second round costs more in slab traffic than its finer tail saves (B = 64: 128->128 at 80x80
   // 203 -> 159 us, 64->64 at 160x160 183 -> 170 us with 256 instead of 512 blocks); and the slabs must fit the scratch buffer
-  const long slab = (long)9 * Cin_pad * CO;
-  const long maxblk = scratch_elems / (slab * ny);
+  const long slab = (long)9 * a.Cin_pad * CO;
+  const long maxblk = a.scratch_elems / (slab * ny);
   static const int target_blocks = dy_env("DY_WG3_BLOCKS") ? atoi(dy_env("DY_WG3_BLOCKS")) : 256;
-  int nseg = target_blocks / (N * ny * p.nstrip);
-  if ((long)N * nseg * p.nstrip > maxblk) nseg = (int)(maxblk / ((long)N * p.nstrip));
+  int nseg = target_blocks / (a.N * ny * p.nstrip);
+  if ((long)a.N * nseg * p.nstrip > maxblk) nseg = (int)(maxblk / ((long)a.N * p.nstrip));
   if (nseg < 1) nseg = 1;
-  if (nseg > Hi) nseg = Hi;
-  p.rb = (Hi + nseg - 1) / nseg;
-  p.nseg = (Hi + p.rb - 1) / p.rb;
-  const int nblk = N * p.nseg * p.nstrip;
-  DY_CHECK((long)nblk * ny * slab <= scratch_elems, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", scratch_elems,
+  if (nseg > a.Hi) nseg = a.Hi;
+  p.rb = (a.Hi + nseg - 1) / nseg;
+  p.nseg = (a.Hi + p.rb - 1) / p.rb;
+  const int nblk = a.N * p.nseg * p.nstrip;
+  DY_CHECK((long)nblk * ny * slab <= a.scratch_elems, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", a.scratch_elems,
            (long)nblk * ny * slab);
-  const int shmem = 4 * p.XW * Cin_pad * 2 + 2 * p.PW * ZPB;
+  const int shmem = 4 * p.XW * a.Cin_pad * 2 + 2 * p.PW * ZPB;
   static int configured = 0;
-  const bool f16 = dtype == DY_F16;
-  const int bit = (Cin_pad == 64 ? 1 : 2) << (f16 ? 2 : 0);
+  const bool f16 = a.dtype == DY_F16;
+  const int bit = (a.Cin_pad == 64 ? 1 : 2) << (f16 ? 2 : 0);
   if (!(configured & bit)) {
-    const void* fn = Cin_pad == 64 ? (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<64, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<64, bf16_t>))
+    const void* fn = a.Cin_pad == 64 ? (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<64, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<64, bf16_t>))
                                    : (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<128, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<128, bf16_t>));
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
@@ -337,8 +336,8 @@ int dy_wgrad_v3_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
     configured |= bit;
   }
   hipStream_t st = (hipStream_t)stream;
-  dy_note_kernel(Cin_pad == 64 ? "wg3::wgrad_kernel<64>+reduce_kernel" : "wg3::wgrad_kernel<128>+reduce_kernel");
-  if (Cin_pad == 64) {
+  dy_note_kernel(a.Cin_pad == 64 ? "wg3::wgrad_kernel<64>+reduce_kernel" : "wg3::wgrad_kernel<128>+reduce_kernel");
+  if (a.Cin_pad == 64) {
     if (f16) wgrad_kernel<64, f16_t><<<dim3(nblk, ny), 384, shmem, st>>>(p);
     else wgrad_kernel<64, bf16_t><<<dim3(nblk, ny), 384, shmem, st>>>(p);
   } else {
@@ -346,7 +345,7 @@ int dy_wgrad_v3_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
     else wgrad_kernel<128, bf16_t><<<dim3(nblk, ny), 768, shmem, st>>>(p);
   }
   DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(Cout, 32), 9 * Cin_pad), 256, 0, st>>>(scratch, nblk, Cin_pad, Cout, Cin, g_oihw);
+  reduce_kernel<<<dim3(dy_cdiv(a.Cout, 32), 9 * a.Cin_pad), 256, 0, st>>>(a.scratch, nblk, a.Cin_pad, a.Cout, a.Cin, a.g_oihw);
   DY_LAUNCH_CHECK();
   return 0;
 }

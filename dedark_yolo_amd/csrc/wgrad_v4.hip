@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include "conv_route.h"
 
 namespace wg4 {
 
@@ -57,11 +58,7 @@ struct P {
   int q_h, r_h;                 // q64_w = q_h * Ho + r_h
 };
 
-__device__ inline int xcd_remap(int bid, int nblk) {
-  int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (bid >> 3);
-}
+using dy_route::xcd_remap;
 
 // POINTWISE: 1x1 / stride 1 / no padding: x rows are the output pixels themselves (no gather arithmetic at all).
 template <bool POINTWISE, typename T = bf16_t>
@@ -438,47 +435,45 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ p
 
 }  // namespace wg4
 
-bool dy_wgrad_v4_eligible(int dtype, int Cin_pad, int Cout_pad, int KH, int KW, long M, int N, int Hi, int Wi, int Ho, int Wo, long x_ld,
-                          long dz_ld, long scratch_elems) {
+bool dy_wgrad_v4_eligible(const DyWgradArgs& a) {
+  const long M = (long)a.N * a.Ho * a.Wo;
   static const bool off = dy_env("DY_NO_WGRAD_V4") != nullptr;
-  if (off || (dtype != DY_BF16 && dtype != DY_F16)) return false;
-  if (Cin_pad % 8 != 0 || Cout_pad % 8 != 0 || (x_ld * 2) % 16 != 0 || (dz_ld * 2) % 16 != 0) return false;
-  const long Ktot = (long)KH * KW * Cin_pad;
-  const long tq = (Cout_pad + 255) / 256, tp = (Ktot + 255) / 256;
+  if (off || (a.dtype != DY_BF16 && a.dtype != DY_F16)) return false;
+  if (a.Cin_pad % 8 != 0 || a.Cout_pad % 8 != 0 || (a.x_ld * 2) % 16 != 0 || (a.dz_ld * 2) % 16 != 0) return false;
+  const long Ktot = (long)a.KH * a.KW * a.Cin_pad;
+  const long tq = (a.Cout_pad + 255) / 256, tp = (Ktot + 255) / 256;
   // 256-wide tiles must not be mostly padding (Cout >= 192 within 20 %, K within 20 %) and the pixel loop must be long enough to
   // amortise a slab -- except against the 128 x 128 kernel on long pixel loops: there even a quarter-filled tile wins (C3, B = 64:
   // 256->64 3x3 at 80x80 672 -> 365 us, 512->64 at 40x40 338 -> 196, 320->128 1x1 at 160x160 436 -> 321, 64->128 3x3 s2 at 320x320
   // 829 -> 521), so from 65,536 pixels on any Cout >= 64 and K >= 192 is taken
-  const bool tight = Cout_pad >= 192 && tq * 256 * 4 <= (long)Cout_pad * 5 && tp * 256 * 4 <= Ktot * 5;
+  const bool tight = a.Cout_pad >= 192 && tq * 256 * 4 <= (long)a.Cout_pad * 5 && tp * 256 * 4 <= Ktot * 5;
   // ... as long as the tile is at least a quarter full (32->64 3x3 s2 at 160x160, B = 32: K = 288, 14 % full, 48 -> 135 us: not taken)
-  const bool long_loop = Cout_pad >= 64 && M >= 65536 && Ktot * Cout_pad * 4 >= tp * 256 * tq * 256;
+  const bool long_loop = a.Cout_pad >= 64 && M >= 65536 && Ktot * a.Cout_pad * 4 >= tp * 256 * tq * 256;
   if (!(Ktot >= 192 && (tight || long_loop))) return false;
   if (M < 16384 || M >= (1L << 31)) return false;
-  const long x_bytes = (((long)N * Hi * Wi - 1) * x_ld + Cin_pad) * 2, dz_bytes = ((M - 1) * dz_ld + Cout_pad) * 2;
+  const long x_bytes = (((long)a.N * a.Hi * a.Wi - 1) * a.x_ld + a.Cin_pad) * 2, dz_bytes = ((M - 1) * a.dz_ld + a.Cout_pad) * 2;
   if (x_bytes > 0x7fffffffL || dz_bytes > 0x3fffffffL) return false;
-  return scratch_elems >= tp * tq * 65536L * 2;        // at least two splits' worth of slabs
+  return a.scratch_elems >= tp * tq * 65536L * 2;        // at least two splits' worth of slabs
 }
 
-int dy_wgrad_v4_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, long dz_ld, int Ho, int Wo,
-                       int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin, float* scratch,
-                       long scratch_elems, float* g_oihw, int dtype, void* stream) {
+int dy_wgrad_v4_launch(const DyWgradArgs& a, void* stream) {
   using namespace wg4;
   P p;
-  p.x = (const char*)x; p.dz = (const char*)dz; p.x_ld = x_ld; p.dz_ld = dz_ld;
-  p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin_pad; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout_pad;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
-  p.M = (long)N * Ho * Wo;
-  p.Ktot = KH * KW * Cin_pad;
-  p.x_bytes = (unsigned)((((long)N * Hi * Wi - 1) * x_ld + Cin_pad) * 2);
-  p.dz_bytes = (unsigned)(((p.M - 1) * dz_ld + Cout_pad) * 2);
-  p.part = scratch;
-  p.tiles_q = dy_cdiv(Cout_pad, BQ);
+  p.x = (const char*)a.x; p.dz = (const char*)a.dz; p.x_ld = a.x_ld; p.dz_ld = a.dz_ld;
+  p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
+  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil;
+  p.M = (long)a.N * a.Ho * a.Wo;
+  p.Ktot = a.KH * a.KW * a.Cin_pad;
+  p.x_bytes = (unsigned)((((long)a.N * a.Hi * a.Wi - 1) * a.x_ld + a.Cin_pad) * 2);
+  p.dz_bytes = (unsigned)(((p.M - 1) * a.dz_ld + a.Cout_pad) * 2);
+  p.part = a.scratch;
+  p.tiles_q = dy_cdiv(a.Cout_pad, BQ);
   p.tiles = dy_cdiv(p.Ktot, BP) * p.tiles_q;
   // one round of blocks over the 256 CUs, at least 8 K-steps each, slabs must fit the workspace
   long splits = 256 / p.tiles;
   const long max_splits = (p.M + 8L * BKP - 1) / (8L * BKP);
   if (splits > max_splits) splits = max_splits;
-  const long fit = scratch_elems / ((long)p.tiles * BP * BQ);
+  const long fit = a.scratch_elems / ((long)p.tiles * BP * BQ);
   if (splits > fit) splits = fit;
   if (splits < 1) splits = 1;
   long chunk = (p.M + splits - 1) / splits;
@@ -486,9 +481,9 @@ int dy_wgrad_v4_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
   splits = (p.M + chunk - 1) / chunk;
   p.chunk = chunk;
   p.nblk = (int)(splits * p.tiles);
-  p.q64_w = BKP / Wo; p.r64_w = BKP % Wo;
-  p.q_h = p.q64_w / Ho; p.r_h = p.q64_w % Ho;
-  const bool pointwise = KH == 1 && KW == 1 && stride == 1 && pad == 0;
+  p.q64_w = BKP / a.Wo; p.r64_w = BKP % a.Wo;
+  p.q_h = p.q64_w / a.Ho; p.r_h = p.q64_w % a.Ho;
+  const bool pointwise = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
   constexpr int SHMEM = 2 * BUF;
   static bool configured = false;
   if (!configured) {
@@ -504,7 +499,7 @@ int dy_wgrad_v4_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
   }
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("wg4::wgrad_kernel+reduce_kernel");
-  if (dtype == DY_F16) {
+  if (a.dtype == DY_F16) {
     if (pointwise) wgrad_kernel<true, f16_t><<<p.nblk, 512, SHMEM, st>>>(p);
     else wgrad_kernel<false, f16_t><<<p.nblk, 512, SHMEM, st>>>(p);
   } else {
@@ -512,7 +507,7 @@ int dy_wgrad_v4_launch(const void* x, long x_ld, int N, int Hi, int Wi, int Cin_
     else wgrad_kernel<false, bf16_t><<<p.nblk, 512, SHMEM, st>>>(p);
   }
   DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(Cin, 256), Cout, KH * KW), 256, 0, st>>>(scratch, (int)splits, p.tiles, p.tiles_q, Cout, Cin, Cin_pad, KH * KW, g_oihw);
+  reduce_kernel<<<dim3(dy_cdiv(a.Cin, 256), a.Cout, a.KH * a.KW), 256, 0, st>>>(a.scratch, (int)splits, p.tiles, p.tiles_q, a.Cout, a.Cin, a.Cin_pad, a.KH * a.KW, a.g_oihw);
   DY_LAUNCH_CHECK();
   return 0;
 }

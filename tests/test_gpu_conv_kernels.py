@@ -82,16 +82,40 @@ PIPELINED = [(2, 64, 128, 40, 40, 3, 1, 1), (3, 128, 64, 32, 32, 3, 2, 1), (2, 6
              (2, 3, 16, 64, 64, 3, 2, 1), (2, 3, 64, 33, 47, 3, 2, 1)]   # stem: direct dot2 dgrad with planar dx
 
 
+_DTYPE_NAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+_snapshot = None
+
+
+def route_key(dtype, shape):
+    return _DTYPE_NAME[dtype] + ":" + "x".join(map(str, shape))
+
+
+def _assert_routes(dtype, shape, routes):
+    """Default dispatch launches, per C-ABI entry, the kernel it launched before the route table of csrc/conv.hip replaced the three
+    written-out chains: golden/g22_conv_routes.json, recorded by tools/conv_route_snapshot.py from the library of the commit before."""
+    global _snapshot
+    if _snapshot is None:
+        import json
+        import os
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g22_conv_routes.json")) as f:
+            _snapshot = json.load(f)
+    assert routes == _snapshot[route_key(dtype, shape)], (route_key(dtype, shape), routes)
+
+
 @pytest.mark.parametrize("shape", GENERIC, ids=lambda s: "x".join(map(str, s)))
 def test_conv_f32_exact_mfma(shape):
-    r = _case(torch.float32, *shape)
+    routes = {}
+    r = _case(torch.float32, *shape, routes=routes)
     assert max(r.values()) < 1e-5, r
+    _assert_routes(torch.float32, shape, routes)
 
 
 @pytest.mark.parametrize("shape", GENERIC + PIPELINED, ids=lambda s: "x".join(map(str, s)))
 def test_conv_bf16(shape):
-    r = _case(torch.bfloat16, *shape)
+    routes = {}
+    r = _case(torch.bfloat16, *shape, routes=routes)
     assert max(r.values()) < 1e-2, r
+    _assert_routes(torch.bfloat16, shape, routes)
 
 
 # the large-tile kernels only take layers that fill the chip (>= 192 tiles of 256 x 256, >= 256 tiles of 256 x 128 / 256 x 64,
@@ -139,6 +163,7 @@ def test_conv_bf16_large_tile_routes(shape, want):
     for entry, sym in zip(("dy_conv2d_fwd", "dy_conv2d_dgrad", "dy_conv2d_wgrad"), want):
         if sym is not None:
             assert routes.get(entry, "").startswith(sym), (entry, sym, routes)
+    _assert_routes(torch.bfloat16, shape, routes)
 
 
 # + the direct dot2 kernels in f16 (v_dot2_f32_f16): thin 1x1 dgrad, stem dgrad with planar dx
@@ -150,8 +175,14 @@ F16_SHAPES = GENERIC[:9] + PIPELINED[::3] + [r[0] for r in ROUTED[:10]] + [r[0] 
 def test_conv_f16(shape):
     """IEEE half (BASELINE configs[4]: the reference's AMP dtype) through the same dispatch: the generic kernel and every pipelined
     kernel are instantiated for the f16 MFMA.  11-bit mantissa: bound 2e-3 * max|ref| (bf16: 1e-2)."""
-    r = _case(torch.float16, *shape)
+    routes = {}
+    r = _case(torch.float16, *shape, routes=routes)
     assert max(r.values()) < 2e-3, r
+    _assert_routes(torch.float16, shape, routes)
+
+
+# every (dtype, shapes) whose routes golden/g22_conv_routes.json pins (tools/conv_route_snapshot.py walks this list)
+ROUTE_CASES = [(torch.float32, GENERIC), (torch.bfloat16, GENERIC + PIPELINED + [r[0] for r in ROUTED]), (torch.float16, F16_SHAPES)]
 
 
 THIN = [(12, 16, 32, 41, 39, 3, 2, 1), (5, 32, 24, 37, 35, 3, 1, 1), (4, 16, 16, 40, 40, 1, 1, 0), (6, 32, 16, 36, 38, 3, 2, 1),
