@@ -7,7 +7,7 @@
 // pixel row (1 KiB contiguous when C >= 512 bf16) or several adjacent pixels for narrower tensors.
 #include <stdlib.h>
 #include <type_traits>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 // tensors beyond this many MiB are streamed with non-temporal loads / stores by the forward pass (tools/gpu: variant builds with
@@ -391,14 +391,6 @@ Geo geometry(long pixels, int C, int ve, int kind /*0 fwd, 1 bwd reduce, 2 bwd a
   return g;
 }
 
-int check_view(const char* who, const void* p, long ld, int C, int dtype) {
-  const int ve = dtype == DY_F32 ? 4 : 8, es = dtype == DY_F32 ? 4 : 2;
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(C > 0 && C % ve == 0, "%s: C=%d must be a multiple of %d", who, C, ve);
-  DY_CHECK(ld >= C && (ld * es) % 16 == 0 && ((uintptr_t)p) % 16 == 0, "%s: view not 16-byte aligned (ld=%ld)", who, ld);
-  return 0;
-}
-
 }  // namespace
 
 // The *_valid entries take the layer's real channel count C_valid <= C (include/dedark_yolo.h: channel padding); the entries
@@ -440,22 +432,21 @@ extern "C" int dy_bn_fold_eval(const float* gamma, const float* beta, const floa
 extern "C" int dy_bn_act_fwd(const void* z, int64_t z_ld, const float* scale, const float* shift, int act,
                              const void* residual, int64_t res_ld, void* y, int64_t y_ld, int64_t pixels, int C, int dtype,
                              void* stream) {
-  if (int e = check_view("dy_bn_act_fwd(z)", z, z_ld, C, dtype)) return e;
-  if (int e = check_view("dy_bn_act_fwd(y)", y, y_ld, C, dtype)) return e;
-  if (residual) if (int e = check_view("dy_bn_act_fwd(res)", residual, res_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_fwd(z)", z, z_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_fwd(y)", y, y_ld, C, dtype)) return e;
+  if (residual) if (int e = dy_check_view("dy_bn_act_fwd(res)", residual, res_ld, C, dtype)) return e;
   if (pixels <= 0) return 0;
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const Geo g = geometry(pixels, C, ve, 0);
   const size_t shm = 2 * (size_t)g.cgb * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  const bool big = pixels * C * (dtype == DY_F32 ? 4 : 2) > ((long)DY_BN_NT_FWD_MB << 20);
+  const bool big = pixels * C * dy_elem_size(dtype) > ((long)DY_BN_NT_FWD_MB << 20);
   dy_note_kernel("bn_act_fwd_kernel");
-#define FWD(T_, U_) bn_act_fwd_kernel<T_, U_, (U_ == 4)><<<g.grid, NT, shm, st>>>((const T_*)z, z_ld, scale, shift, act, (const T_*)residual, res_ld, \
-                                                                    (T_*)y, y_ld, pixels, C, g.cgb, g.rows)
-  if (dtype == DY_F32) { if (big) FWD(float, 4); else FWD(float, 2); }
-  else if ((dtype) == DY_F16) { if (big) FWD(f16_t, 4); else FWD(f16_t, 2); }
-  else { if (big) FWD(bf16_t, 4); else FWD(bf16_t, 2); }
-#undef FWD
+  DY_DISPATCH_DTYPE("dy_bn_act_fwd", dtype, {
+    auto kernel = big ? bn_act_fwd_kernel<T, 4, true> : bn_act_fwd_kernel<T, 2, false>;
+    kernel<<<g.grid, NT, shm, st>>>((const T*)z, z_ld, scale, shift, act, (const T*)residual, res_ld, (T*)y, y_ld, pixels, C, g.cgb,
+                                    g.rows);
+  });
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -463,22 +454,21 @@ extern "C" int dy_bn_act_fwd(const void* z, int64_t z_ld, const float* scale, co
 extern "C" int dy_bn_act_bwd_reduce(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale,
                                     const float* shift, const float* mean, const float* invstd, int act, int has_bn,
                                     double* sums, int64_t pixels, int C, int dtype, void* stream) {
-  if (int e = check_view("dy_bn_act_bwd_reduce(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check_view("dy_bn_act_bwd_reduce(z)", z, z_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_bwd_reduce(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_bwd_reduce(z)", z, z_ld, C, dtype)) return e;
   DY_CHECK(sums && (!has_bn || (mean && invstd)), "dy_bn_act_bwd_reduce: null stats");
   if (pixels <= 0) return 0;
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const Geo g = geometry(pixels, C, ve, 1);
   size_t shm = (4 + 2 * (size_t)g.rows) * g.cgb * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("bn_act_bwd_reduce_kernel");
-  const bool big = pixels * C * (dtype == DY_F32 ? 4 : 2) > (128L << 20);
-#define REDUCE(T_, N_) bn_act_bwd_reduce_kernel<T_, 2, N_><<<g.grid, NT, shm, st>>>((const T_*)dy, dy_ld, (const T_*)z, z_ld, scale, shift, mean, invstd, \
-                                                                                   act, has_bn, sums, pixels, C, g.cgb, g.rows)
-  if (dtype == DY_F32) { if (big) REDUCE(float, true); else REDUCE(float, false); }
-  else if (dtype == DY_F16) { if (big) REDUCE(f16_t, true); else REDUCE(f16_t, false); }
-  else { if (big) REDUCE(bf16_t, true); else REDUCE(bf16_t, false); }
-#undef REDUCE
+  const bool big = pixels * C * dy_elem_size(dtype) > (128L << 20);
+  DY_DISPATCH_DTYPE("dy_bn_act_bwd_reduce", dtype, {
+    auto kernel = big ? bn_act_bwd_reduce_kernel<T, 2, true> : bn_act_bwd_reduce_kernel<T, 2, false>;
+    kernel<<<g.grid, NT, shm, st>>>((const T*)dy, dy_ld, (const T*)z, z_ld, scale, shift, mean, invstd, act, has_bn, sums, pixels, C,
+                                    g.cgb, g.rows);
+  });
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -487,25 +477,23 @@ extern "C" int dy_bn_act_bwd_apply_valid(const void* dy, int64_t dy_ld, const vo
                                          const float* shift, const float* mean, const float* invstd, const float* gamma, int act,
                                          int has_bn, const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta,
                                          int64_t pixels, int C, int C_valid, int dtype, void* stream) {
-  if (int e = check_view("dy_bn_act_bwd_apply(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check_view("dy_bn_act_bwd_apply(z)", z, z_ld, C, dtype)) return e;
-  if (int e = check_view("dy_bn_act_bwd_apply(dz)", dz, dz_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_bwd_apply(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_bwd_apply(z)", z, z_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_bn_act_bwd_apply(dz)", dz, dz_ld, C, dtype)) return e;
   DY_CHECK(sums && (!has_bn || (mean && invstd)), "dy_bn_act_bwd_apply: null stats");
   DY_CHECK(C_valid > 0 && C_valid <= C, "dy_bn_act_bwd_apply: C_valid=%d outside 1..C=%d", C_valid, C);
   // pixels == 0: only the parameter gradients (dgamma / dbeta) are written
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const Geo g = geometry(pixels > 0 ? pixels : 1, C, ve, 2);
   const size_t shm = 7 * (size_t)g.cgb * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  const bool big = pixels * C * (dtype == DY_F32 ? 4 : 2) > (128L << 20);
+  const bool big = pixels * C * dy_elem_size(dtype) > (128L << 20);
   dy_note_kernel("bn_act_bwd_apply_kernel");
-#define APPLY(T_, U_) bn_act_bwd_apply_kernel<T_, U_, (U_ == 1)><<<g.grid, NT, shm, st>>>((const T_*)dy, dy_ld, (const T_*)z, z_ld, scale, shift, mean, invstd, \
-                                                                            gamma, act, has_bn, sums, (T_*)dz, dz_ld, dgamma, dbeta, pixels, \
-                                                                            pixels > 0 ? pixels : 1, C, C_valid, g.cgb, g.rows)
-  if (dtype == DY_F32) { if (big) APPLY(float, 1); else APPLY(float, 2); }
-  else if ((dtype) == DY_F16) { if (big) APPLY(f16_t, 1); else APPLY(f16_t, 2); }
-  else { if (big) APPLY(bf16_t, 1); else APPLY(bf16_t, 2); }
-#undef APPLY
+  DY_DISPATCH_DTYPE("dy_bn_act_bwd_apply", dtype, {
+    auto kernel = big ? bn_act_bwd_apply_kernel<T, 1, true> : bn_act_bwd_apply_kernel<T, 2, false>;
+    kernel<<<g.grid, NT, shm, st>>>((const T*)dy, dy_ld, (const T*)z, z_ld, scale, shift, mean, invstd, gamma, act, has_bn, sums, (T*)dz,
+                                    dz_ld, dgamma, dbeta, pixels, pixels > 0 ? pixels : 1, C, C_valid, g.cgb, g.rows);
+  });
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -8,7 +8,7 @@
 //   soft-max statistics in ONE read of the row: every lane keeps a running maximum m and the sum s of exp(z - m), rescaled when m
 //   grows; lanes merge pairwise, (m, s) + (m', s') = (M, s exp(m - M) + s' exp(m' - M)), M = max(m, m'), in the fixed butterfly order.
 // No float atomics anywhere: the loss is summed by one block in a strided-then-tree order, so two runs give identical bytes.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 #include <math.h>
@@ -19,8 +19,6 @@ constexpr int NT = 256;                 // threads per block
 constexpr int ROWS = NT / 64;           // rows (waves) per block
 constexpr int TOPK_MAX = 8;
 constexpr float XENT_DIV = 64.f;        // the reference divides by the constant 64, not by the batch size
-
-inline bool aligned16(const void* p, long ld, int elem) { return ((uintptr_t)p % 16) == 0 && (ld * elem) % 16 == 0; }
 
 // ---- global average pool -------------------------------------------------------------------------------------------------------
 // thread = one 16-byte channel group (or one tail channel) of one image; the HW loop stays inside the thread
@@ -291,121 +289,98 @@ __global__ __launch_bounds__(NT) void metrics_kernel(const int32_t* __restrict__
   if (threadIdx.x < 3 && red[threadIdx.x][0]) atomicAdd(counts + threadIdx.x, (unsigned long long)red[threadIdx.x][0]);
 }
 
-int check_dtype(int dtype, const char* who) {
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "%s: bad dtype %d", who, dtype);
-  return 0;
-}
-
 }  // namespace
 
-#define CP(T, p) reinterpret_cast<const T*>(p)
-#define MP(T, p) reinterpret_cast<T*>(p)
-
 extern "C" int dy_gap_fwd(const void* x, int64_t x_ld, int N, int HW, int C, int dtype, void* y, int64_t y_ld, void* stream) {
-  if (int e = check_dtype(dtype, "dy_gap_fwd")) return e;
+  if (int e = dy_check_dtype("dy_gap_fwd", dtype)) return e;
   DY_CHECK(x && y && N > 0 && HW > 0 && C > 0 && x_ld >= C && y_ld >= C, "dy_gap_fwd: bad arguments (N %d HW %d C %d x_ld %ld y_ld %ld)", N,
            HW, C, (long)x_ld, (long)y_ld);
   DY_CHECK(N <= 65535, "dy_gap_fwd: N %d above 65535", N);
-  const int es = dtype == DY_F32 ? 4 : 2, ve = 16 / es;
-  const int nv = aligned16(x, x_ld, es) ? C / ve : 0;
-  const bool y_vec = aligned16(y, y_ld, es);
+  const int es = dy_elem_size(dtype), ve = dy_vec_elems(dtype);
+  const int nv = dy_aligned16(x, x_ld, es) ? C / ve : 0;
+  const bool y_vec = dy_aligned16(y, y_ld, es);
   dim3 grid(dy_cdiv(nv + (C - nv * ve), NT), N);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("gap_fwd_kernel");
-  if (dtype == DY_F32) gap_fwd_kernel<float><<<grid, NT, 0, st>>>(CP(float, x), x_ld, HW, C, nv, MP(float, y), y_ld, y_vec);
-  else if (dtype == DY_F16) gap_fwd_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, x), x_ld, HW, C, nv, MP(f16_t, y), y_ld, y_vec);
-  else gap_fwd_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, x), x_ld, HW, C, nv, MP(bf16_t, y), y_ld, y_vec);
+  DY_DISPATCH_DTYPE("dy_gap_fwd", dtype, gap_fwd_kernel<T><<<grid, NT, 0, st>>>((const T*)x, x_ld, HW, C, nv, (T*)y, y_ld, y_vec));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_gap_bwd(const void* dy, int64_t dy_ld, int N, int HW, int C, int dtype, void* dx, int64_t dx_ld, void* stream) {
-  if (int e = check_dtype(dtype, "dy_gap_bwd")) return e;
+  if (int e = dy_check_dtype("dy_gap_bwd", dtype)) return e;
   DY_CHECK(dy && dx && N > 0 && HW > 0 && C > 0 && dy_ld >= C && dx_ld >= C, "dy_gap_bwd: bad arguments (N %d HW %d C %d dy_ld %ld dx_ld %ld)",
            N, HW, C, (long)dy_ld, (long)dx_ld);
   DY_CHECK(N <= 65535, "dy_gap_bwd: N %d above 65535", N);
-  const int es = dtype == DY_F32 ? 4 : 2, ve = 16 / es;
-  const int nv = aligned16(dx, dx_ld, es) ? C / ve : 0;
-  const bool dy_vec = aligned16(dy, dy_ld, es);
+  const int es = dy_elem_size(dtype), ve = dy_vec_elems(dtype);
+  const int nv = dy_aligned16(dx, dx_ld, es) ? C / ve : 0;
+  const bool dy_vec = dy_aligned16(dy, dy_ld, es);
   dim3 grid(dy_cdiv(nv + (C - nv * ve), NT), N);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("gap_bwd_kernel");
-  if (dtype == DY_F32) gap_bwd_kernel<float><<<grid, NT, 0, st>>>(CP(float, dy), dy_ld, dy_vec, HW, C, nv, MP(float, dx), dx_ld);
-  else if (dtype == DY_F16) gap_bwd_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, dy), dy_ld, dy_vec, HW, C, nv, MP(f16_t, dx), dx_ld);
-  else gap_bwd_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, dy), dy_ld, dy_vec, HW, C, nv, MP(bf16_t, dx), dx_ld);
+  DY_DISPATCH_DTYPE("dy_gap_bwd", dtype, gap_bwd_kernel<T><<<grid, NT, 0, st>>>((const T*)dy, dy_ld, dy_vec, HW, C, nv, (T*)dx, dx_ld));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cls_xent_fwd(const void* logits, int64_t ld, int dtype, const int64_t* cls, int B, int nc, float* row_lse, float* loss,
                                void* stream) {
-  if (int e = check_dtype(dtype, "dy_cls_xent_fwd")) return e;
+  if (int e = dy_check_dtype("dy_cls_xent_fwd", dtype)) return e;
   DY_CHECK(logits && cls && row_lse && loss && B > 0 && nc > 0 && ld >= nc, "dy_cls_xent_fwd: bad arguments (B %d nc %d ld %ld)", B, nc, (long)ld);
-  const int es = dtype == DY_F32 ? 4 : 2;
-  const bool vec = aligned16(logits, ld, es);
+  const int es = dy_elem_size(dtype);
+  const bool vec = dy_aligned16(logits, ld, es);
   const int grid = dy_cdiv(B, ROWS);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("xent_lse_kernel");
-  if (dtype == DY_F32) xent_lse_kernel<float><<<grid, NT, 0, st>>>(CP(float, logits), ld, vec, B, nc, row_lse);
-  else if (dtype == DY_F16) xent_lse_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, logits), ld, vec, B, nc, row_lse);
-  else xent_lse_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, logits), ld, vec, B, nc, row_lse);
+  DY_DISPATCH_DTYPE("dy_cls_xent_fwd", dtype, xent_lse_kernel<T><<<grid, NT, 0, st>>>((const T*)logits, ld, vec, B, nc, row_lse));
   DY_LAUNCH_CHECK();
   dy_note_kernel("xent_sum_kernel");
-  if (dtype == DY_F32) xent_sum_kernel<float><<<1, NT, 0, st>>>(CP(float, logits), ld, cls, B, nc, row_lse, loss);
-  else if (dtype == DY_F16) xent_sum_kernel<f16_t><<<1, NT, 0, st>>>(CP(f16_t, logits), ld, cls, B, nc, row_lse, loss);
-  else xent_sum_kernel<bf16_t><<<1, NT, 0, st>>>(CP(bf16_t, logits), ld, cls, B, nc, row_lse, loss);
+  DY_DISPATCH_DTYPE("dy_cls_xent_fwd", dtype, xent_sum_kernel<T><<<1, NT, 0, st>>>((const T*)logits, ld, cls, B, nc, row_lse, loss));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cls_xent_bwd(const void* logits, int64_t ld, int dtype, const int64_t* cls, const float* row_lse, const float* grad_out,
                                int B, int nc, void* dlogits, int64_t dld, void* stream) {
-  if (int e = check_dtype(dtype, "dy_cls_xent_bwd")) return e;
+  if (int e = dy_check_dtype("dy_cls_xent_bwd", dtype)) return e;
   DY_CHECK(logits && cls && row_lse && grad_out && dlogits && B > 0 && nc > 0 && ld >= nc && dld >= nc,
            "dy_cls_xent_bwd: bad arguments (B %d nc %d ld %ld dld %ld)", B, nc, (long)ld, (long)dld);
-  const int es = dtype == DY_F32 ? 4 : 2;
-  const bool vec = aligned16(logits, ld, es), dvec = aligned16(dlogits, dld, es);
+  const int es = dy_elem_size(dtype);
+  const bool vec = dy_aligned16(logits, ld, es), dvec = dy_aligned16(dlogits, dld, es);
   const int grid = dy_cdiv(B, ROWS);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("xent_bwd_kernel");
-  if (dtype == DY_F32)
-    xent_bwd_kernel<float><<<grid, NT, 0, st>>>(CP(float, logits), ld, vec, cls, row_lse, grad_out, B, nc, MP(float, dlogits), dld, dvec);
-  else if (dtype == DY_F16)
-    xent_bwd_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, logits), ld, vec, cls, row_lse, grad_out, B, nc, MP(f16_t, dlogits), dld, dvec);
-  else
-    xent_bwd_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, logits), ld, vec, cls, row_lse, grad_out, B, nc, MP(bf16_t, dlogits), dld, dvec);
+  DY_DISPATCH_DTYPE("dy_cls_xent_bwd", dtype,
+                    xent_bwd_kernel<T><<<grid, NT, 0, st>>>((const T*)logits, ld, vec, cls, row_lse, grad_out, B, nc, (T*)dlogits, dld,
+                                                            dvec));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cls_softmax(const void* logits, int64_t ld, int dtype, int B, int nc, float* probs, void* stream) {
-  if (int e = check_dtype(dtype, "dy_cls_softmax")) return e;
+  if (int e = dy_check_dtype("dy_cls_softmax", dtype)) return e;
   DY_CHECK(logits && probs && B > 0 && nc > 0 && ld >= nc, "dy_cls_softmax: bad arguments (B %d nc %d ld %ld)", B, nc, (long)ld);
-  const int es = dtype == DY_F32 ? 4 : 2;
-  const bool vec = aligned16(logits, ld, es);
+  const int es = dy_elem_size(dtype);
+  const bool vec = dy_aligned16(logits, ld, es);
   const int grid = dy_cdiv(B, ROWS);
   hipStream_t st = (hipStream_t)stream;
-  const bool pvec = aligned16(probs, nc, 4);
+  const bool pvec = dy_aligned16(probs, nc, 4);
   dy_note_kernel("softmax_kernel");
-  if (dtype == DY_F32) softmax_kernel<float><<<grid, NT, 0, st>>>(CP(float, logits), ld, vec, B, nc, probs, pvec);
-  else if (dtype == DY_F16) softmax_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, logits), ld, vec, B, nc, probs, pvec);
-  else softmax_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, logits), ld, vec, B, nc, probs, pvec);
+  DY_DISPATCH_DTYPE("dy_cls_softmax", dtype, softmax_kernel<T><<<grid, NT, 0, st>>>((const T*)logits, ld, vec, B, nc, probs, pvec));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cls_topk(const void* scores, int64_t ld, int dtype, int B, int nc, int k, int32_t* idx, void* stream) {
-  if (int e = check_dtype(dtype, "dy_cls_topk")) return e;
+  if (int e = dy_check_dtype("dy_cls_topk", dtype)) return e;
   DY_CHECK(scores && idx && B > 0 && nc > 0 && ld >= nc, "dy_cls_topk: bad arguments (B %d nc %d ld %ld)", B, nc, (long)ld);
   DY_CHECK(k >= 1 && k <= nc && k <= TOPK_MAX, "dy_cls_topk: k %d outside [1, min(nc, %d)]", k, TOPK_MAX);
-  const int es = dtype == DY_F32 ? 4 : 2;
-  const bool vec = aligned16(scores, ld, es);
+  const int es = dy_elem_size(dtype);
+  const bool vec = dy_aligned16(scores, ld, es);
   const int grid = dy_cdiv(B, ROWS);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("topk_kernel");
-  if (dtype == DY_F32) topk_kernel<float><<<grid, NT, 0, st>>>(CP(float, scores), ld, vec, B, nc, k, idx);
-  else if (dtype == DY_F16) topk_kernel<f16_t><<<grid, NT, 0, st>>>(CP(f16_t, scores), ld, vec, B, nc, k, idx);
-  else topk_kernel<bf16_t><<<grid, NT, 0, st>>>(CP(bf16_t, scores), ld, vec, B, nc, k, idx);
+  DY_DISPATCH_DTYPE("dy_cls_topk", dtype, topk_kernel<T><<<grid, NT, 0, st>>>((const T*)scores, ld, vec, B, nc, k, idx));
   DY_LAUNCH_CHECK();
   return 0;
 }

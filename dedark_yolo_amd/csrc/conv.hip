@@ -12,7 +12,7 @@
 // Block ids are remapped so that each XCD (private L2) owns a contiguous range of output tiles (3x3 halo rows and the
 // weight panel stay L2-resident).
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
@@ -1135,9 +1135,8 @@ extern "C" int dy_pack_weight(const float* w, void* packed, int Cout, int Cout_p
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DY_F32) pack_weight_kernel<float><<<blocks, 256, 0, st>>>(w, (float*)packed, Cout, Cout_pad, Cin, Cin_pad, KH, KW, transposed);
-  else if (dtype == DY_F16) pack_weight_kernel<f16_t><<<blocks, 256, 0, st>>>(w, (f16_t*)packed, Cout, Cout_pad, Cin, Cin_pad, KH, KW, transposed);
-  else pack_weight_kernel<bf16_t><<<blocks, 256, 0, st>>>(w, (bf16_t*)packed, Cout, Cout_pad, Cin, Cin_pad, KH, KW, transposed);
+  DY_DISPATCH_DTYPE("dy_pack_weight", dtype,
+                    pack_weight_kernel<T><<<blocks, 256, 0, st>>>(w, (T*)packed, Cout, Cout_pad, Cin, Cin_pad, KH, KW, transposed));
   DY_LAUNCH_CHECK();
   return 0;
 }

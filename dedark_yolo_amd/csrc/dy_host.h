@@ -1,0 +1,54 @@
+// Host-side helpers shared by the C-ABI launchers of the element-wise, BatchNorm, loss and task files: the dtype dispatch, the
+// NHWC view check and the small grid / alignment helpers.  Nothing here is device code.
+#pragma once
+#include "dy_common.h"
+
+static inline int dy_elem_size(int dtype) { return dtype == DY_F32 ? 4 : 2; }   // bytes per element
+static inline int dy_vec_elems(int dtype) { return dtype == DY_F32 ? 4 : 8; }   // elements per 16-byte vector (DT<T>::VE)
+
+static inline int dy_check_dtype(const char* who, int dtype) {
+  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "%s: bad dtype %d", who, dtype);
+  return 0;
+}
+
+// The dtype is a launch parameter, the kernels want it as a type (the idea of bnact.hip's with_act): f is a generic lambda, called
+// once with a tag whose ::type is float, f16_t or bf16_t.  Any other dtype value calls nothing, sets "<who>: bad dtype %d" and
+// returns 1.
+template <typename T> struct DyType { using type = T; };
+template <typename F> inline int dy_dispatch_dtype(const char* who, int dtype, F&& f) {
+  if (dtype == DY_F32) f(DyType<float>{});
+  else if (dtype == DY_F16) f(DyType<f16_t>{});
+  else if (dtype == DY_BF16) f(DyType<bf16_t>{});
+  else return dy_check_dtype(who, dtype);
+  return 0;
+}
+// The form the entries use: the statement sees the element type as T, a bad dtype returns from the entry.
+//   DY_DISPATCH_DTYPE("dy_entry", dtype, kernel<T><<<grid, block, shm, st>>>((const T*)x, x_ld, (T*)y, y_ld, n));
+//   DY_LAUNCH_CHECK();
+#define DY_DISPATCH_DTYPE(who, dtype, ...)                                                      \
+  do {                                                                                          \
+    if (int e__ = dy_dispatch_dtype(who, dtype, [&](auto tag__) {                               \
+          using T = typename decltype(tag__)::type;                                             \
+          __VA_ARGS__;                                                                          \
+        }))                                                                                     \
+      return e__;                                                                               \
+  } while (0)
+
+// the NHWC view (pointer + pixel stride ld, C channels) every vectorised kernel takes: whole 16-byte vectors, 16-byte aligned rows
+static inline int dy_check_view(const char* who, const void* p, long ld, int C, int dtype) {
+  DY_CHECK(p != nullptr, "%s: null pointer", who);
+  if (int e = dy_check_dtype(who, dtype)) return e;
+  const int ve = dy_vec_elems(dtype);
+  DY_CHECK(C > 0 && C % ve == 0, "%s: C=%d must be a multiple of %d", who, C, ve);
+  DY_CHECK(ld >= C && (ld * dy_elem_size(dtype)) % 16 == 0 && ((uintptr_t)p) % 16 == 0, "%s: view not 16-byte aligned (ld=%ld)", who, ld);
+  return 0;
+}
+
+// rows of ld elements can be read with 16-byte vectors
+static inline bool dy_aligned16(const void* p, long ld, int elem_size) { return ((uintptr_t)p % 16) == 0 && (ld * elem_size) % 16 == 0; }
+
+// blocks of 256 threads for a grid-stride loop over `total` items, at most `cap`
+static inline int dy_ew_blocks(long total, int cap) {
+  const long b = (total + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}

@@ -6,7 +6,7 @@
 // The reference launches ~12 full-image passes (clone x2, pad, 3 dense 625-tap conv2d, cat, ...); here: one pointwise
 // kernel (1R+1W), one USM kernel (1R + 1W f32 + optional NHWC8 copy for the stem conv).  Must-reproduce quirk: `lum` of the contrast filter is a per-(b,c,row) scalar taken from
 // pixel columns 0,1,2 of the gamma-filtered image.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -282,26 +282,22 @@ __global__ __launch_bounds__(256) void pointwise_bwd_kernel(const float* __restr
   }
 }
 
-inline int ew_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+constexpr int EW_CAP = 4096;   // blocks of an element-wise launch
 
 }  // namespace
 
 extern "C" int dy_image_to_nhwc8(const float* x, int B, int H, int W, void* y, int Ho, int Wo, int dtype, void* stream) {
   DY_CHECK(x && y && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "dy_image_to_nhwc8: bad args");
-  const int blocks = ew_blocks((long)B * Ho * Wo);
-  if (dtype == DY_F32) image_to_nhwc8_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(x, B, H, W, (float*)y, Ho, Wo);
-  else if ((dtype) == DY_F16) image_to_nhwc8_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(x, B, H, W, (f16_t*)y, Ho, Wo);
-  else image_to_nhwc8_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(x, B, H, W, (bf16_t*)y, Ho, Wo);
+  const int blocks = dy_ew_blocks((long)B * Ho * Wo, EW_CAP);
+  DY_DISPATCH_DTYPE("dy_image_to_nhwc8", dtype,
+                    image_to_nhwc8_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(x, B, H, W, (T*)y, Ho, Wo));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_resize_bwd(const float* dy, int dy_ld, int B, int H, int W, int Ho, int Wo, float* dx, void* stream) {
   DY_CHECK(dy && dx && dy_ld >= 3, "dy_resize_bwd: bad args");
-  resize_bwd_kernel<<<ew_blocks((long)B * Ho * Wo), 256, 0, (hipStream_t)stream>>>(dy, dy_ld, B, H, W, Ho, Wo, dx);
+  resize_bwd_kernel<<<dy_ew_blocks((long)B * Ho * Wo, EW_CAP), 256, 0, (hipStream_t)stream>>>(dy, dy_ld, B, H, W, Ho, Wo, dx);
   DY_LAUNCH_CHECK();
   return 0;
 }

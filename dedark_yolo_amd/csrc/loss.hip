@@ -7,7 +7,7 @@
 // The Detect maps are NHWC, i.e. already [B, anchors, 64+nc] per level: the reference's cat/split/permute copies vanish.
 // Integer outputs (target_gt_idx, fg_mask) follow the CPU reference's tie-breaking: argmax = first maximum; top-10 =
 // libstdc++ std::partial_sort (heap-select) as torch.topk uses on CPU for dim >= 64*k, emulated exactly by one wave.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "dy_lossmath.h"
 #include "../../include/dedark_yolo.h"
 
@@ -656,7 +656,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
 // d points at a dy_det_maps4 when d->n_levels == 4 (its tail is read only then)
 int make_maps(const dy_det_maps* d, Maps& m, const char* who) {
   DY_CHECK(d && d->n_levels >= 1 && d->n_levels <= DY_DET_MAX_LEVELS, "%s: bad maps", who);
-  DY_CHECK(d->dtype == DY_F32 || d->dtype == DY_BF16 || d->dtype == DY_F16, "%s: bad dtype", who);
+  if (int e = dy_check_dtype(who, d->dtype)) return e;
   m.B = d->B; m.nc = d->nc; m.nl = d->n_levels;
   m.dec_scores = nullptr; m.dec_anchors = nullptr;
   const dy_det_maps4* d4 = d->n_levels == 4 ? reinterpret_cast<const dy_det_maps4*>(d) : nullptr;
@@ -696,9 +696,7 @@ extern "C" int dy_loss_decode(const dy_det_maps* d, float* pred_boxes, void* str
   if (int e = make_maps(d, m, "dy_loss_decode")) return e;
   DY_CHECK(pred_boxes, "dy_loss_decode: null");
   int blocks = dy_cdiv((long)m.B * m.A, 256);
-  if (d->dtype == DY_F32) decode_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes);
-  else if ((d->dtype) == DY_F16) decode_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes);
-  else decode_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes);
+  DY_DISPATCH_DTYPE("dy_loss_decode", d->dtype, decode_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -724,9 +722,8 @@ int run_assigner(const Maps& m, int dtype, const float* pred_boxes, const float*
   (void)hipMemsetAsync(work_b, 0, R, st);
   (void)hipMemsetAsync(work_f, 0, (2 * R + 2L * m.B * n_max) * sizeof(float), st);
   dim3 grid(n_max, m.B);
-  if (dtype == DY_F32) tal_metrics_kernel<float><<<grid, 256, 0, st>>>(m, pred_boxes, gt, n_max, align, overl, work_i, work_b);
-  else if ((dtype) == DY_F16) tal_metrics_kernel<f16_t><<<grid, 256, 0, st>>>(m, pred_boxes, gt, n_max, align, overl, work_i, work_b);
-  else tal_metrics_kernel<bf16_t><<<grid, 256, 0, st>>>(m, pred_boxes, gt, n_max, align, overl, work_i, work_b);
+  DY_DISPATCH_DTYPE("dy_tal_assign", dtype,
+                    tal_metrics_kernel<T><<<grid, 256, 0, st>>>(m, pred_boxes, gt, n_max, align, overl, work_i, work_b));
   DY_LAUNCH_CHECK();
   int blocks = dy_cdiv(BA, 256);
   tal_resolve_kernel<<<blocks, 256, 0, st>>>(m.B, m.A, n_max, counts, overl, work_b, target_gt_idx, fg_mask);
@@ -773,9 +770,9 @@ extern "C" int dy_loss_fwd(const dy_det_maps* d, const float* pred_boxes, const 
   DY_CHECK(pred_boxes && fg_mask && norm && target_label && target_box && acc, "dy_loss_fwd: null");
   int blocks = dy_cdiv((long)m.B * m.A, 256);
   if (blocks > 256) blocks = 256;
-  if (d->dtype == DY_F32) loss_fwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes, fg_mask, norm, target_label, target_box, acc);
-  else if ((d->dtype) == DY_F16) loss_fwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes, fg_mask, norm, target_label, target_box, acc);
-  else loss_fwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes, fg_mask, norm, target_label, target_box, acc);
+  DY_DISPATCH_DTYPE("dy_loss_fwd", d->dtype,
+                    loss_fwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(m, pred_boxes, fg_mask, norm, target_label, target_box,
+                                                                                acc));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -804,18 +801,10 @@ extern "C" int dy_loss_bwd(const dy_det_maps* d, void* const* dmap, const int64_
     if (dmap_ld[l] < pad_to) pad_to = (int)dmap_ld[l];
   }
   int blocks = dy_cdiv((long)m.B * m.A, 256);
-  if (d->dtype == DY_F32)
-    loss_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
-                                                                    norm, target_label, target_box, acc, grad_out, hyp_box, hyp_cls,
-                                                                    hyp_dfl, pad_to);
-  else if ((d->dtype) == DY_F16)
-    loss_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
-                                                                     norm, target_label, target_box, acc, grad_out, hyp_box,
-                                                                     hyp_cls, hyp_dfl, pad_to);
-  else
-    loss_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3], pred_boxes, fg_mask,
-                                                                     norm, target_label, target_box, acc, grad_out, hyp_box,
-                                                                     hyp_cls, hyp_dfl, pad_to);
+  DY_DISPATCH_DTYPE("dy_loss_bwd", d->dtype,
+                    loss_bwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(m, dp[0], dp[1], dp[2], dp[3], dl[0], dl[1], dl[2], dl[3],
+                                                                                pred_boxes, fg_mask, norm, target_label, target_box, acc,
+                                                                                grad_out, hyp_box, hyp_cls, hyp_dfl, pad_to));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -908,9 +897,7 @@ extern "C" int dy_detect_decode_rows(const dy_det_maps* d, float* y, int rows, v
   if (int e = make_maps(d, m, "dy_detect_decode")) return e;
   DY_CHECK(y && rows >= 4 + m.nc, "dy_detect_decode: null output or rows < 4 + nc");
   int blocks = dy_cdiv((long)m.B * m.A, 256);
-  if (d->dtype == DY_F32) detect_decode_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
-  else if ((d->dtype) == DY_F16) detect_decode_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
-  else detect_decode_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows);
+  DY_DISPATCH_DTYPE("dy_detect_decode_rows", d->dtype, detect_decode_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, rows));
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,7 @@
 // per-element parameter-group hyper-parameters and the EMA lerp in one pass (reference: BaseTrainer.optimizer_step
 // ultralytics/engine/trainer.py:459-467, build_optimizer :611-665, ModelEMA.update ultralytics/utils/torch_utils.py:360-371).
 // Pure HBM streaming: 4-5 reads + 3 writes per element instead of ~230 x (5-8) small launches.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -115,17 +115,14 @@ __global__ void ema_lerp_kernel(float* __restrict__ ema, const float* __restrict
     ema[i] = d * ema[i] + (1.f - d) * src[i];
 }
 
-inline int ew_blocks(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+constexpr int EW_CAP = 2048;   // blocks of an element-wise launch
 
 }  // namespace
 
 extern "C" int dy_sumsq(const float* g, int64_t n, double* acc, void* stream) {
   DY_CHECK(g && acc && n >= 0 && ((uintptr_t)g) % 16 == 0, "dy_sumsq: bad args");
   // every block ends with ONE f64 atomic on the same address (~8 ns each, serialised): 256 blocks, not 2048 (30 -> ~8 us at 3 M)
-  int blocks = ew_blocks(n / 4 + 1);
+  int blocks = dy_ew_blocks(n / 4 + 1, EW_CAP);
   if (blocks > 256) blocks = 256;
   sumsq_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(g, n, acc);
   DY_LAUNCH_CHECK();
@@ -139,7 +136,7 @@ extern "C" int dy_sgd_step_scaled(float* p, const float* g, float* mom_buf, floa
   DY_CHECK(p && g && mom_buf && n >= 0 && (!loss_scale || sumsq), "dy_sgd_step: bad args");
   if (n == 0) return 0;
   Hyp h = {{lr0, lr1, lr2, lr2}, {wd0, wd1, wd2, wd2}};
-  sgd_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(p, g, mom_buf, ema, group_id, h, momentum, nesterov, ema_decay, sumsq,
+  sgd_kernel<<<dy_ew_blocks(n, EW_CAP), 256, 0, (hipStream_t)stream>>>(p, g, mom_buf, ema, group_id, h, momentum, nesterov, ema_decay, sumsq,
                                                             max_norm, grad_scale, loss_scale, n);
   DY_LAUNCH_CHECK();
   return 0;
@@ -159,7 +156,7 @@ extern "C" int dy_adamw_step_scaled(float* p, const float* g, float* exp_avg, fl
   DY_CHECK(p && g && exp_avg && exp_avg_sq && n >= 0 && step >= 1 && (!loss_scale || sumsq), "dy_adamw_step: bad args");
   if (n == 0) return 0;
   Hyp h = {{lr0, lr1, lr2, lr2}, {wd0, wd1, wd2, wd2}};
-  adamw_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(p, g, exp_avg, exp_avg_sq, ema, group_id, h, beta1, beta2, eps, step,
+  adamw_kernel<<<dy_ew_blocks(n, EW_CAP), 256, 0, (hipStream_t)stream>>>(p, g, exp_avg, exp_avg_sq, ema, group_id, h, beta1, beta2, eps, step,
                                                               ema_decay, sumsq, max_norm, grad_scale, loss_scale, n);
   DY_LAUNCH_CHECK();
   return 0;
@@ -193,7 +190,7 @@ __global__ void grad_accumulate_kernel(float* __restrict__ acc, const float* __r
 extern "C" int dy_grad_accumulate(float* acc, const float* g, int64_t n, void* stream) {
   DY_CHECK(acc && g && n >= 0 && ((uintptr_t)acc % 16 == 0) && ((uintptr_t)g % 16 == 0), "dy_grad_accumulate: bad args");
   if (n == 0) return 0;
-  grad_accumulate_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(acc, g, n);
+  grad_accumulate_kernel<<<dy_ew_blocks(n, EW_CAP), 256, 0, (hipStream_t)stream>>>(acc, g, n);
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -201,7 +198,7 @@ extern "C" int dy_grad_accumulate(float* acc, const float* g, int64_t n, void* s
 extern "C" int dy_ema_lerp(float* ema, const float* src, float decay, int64_t n, void* stream) {
   DY_CHECK(ema && src && n >= 0, "dy_ema_lerp: bad args");
   if (n == 0) return 0;
-  ema_lerp_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)stream>>>(ema, src, decay, n);
+  ema_lerp_kernel<<<dy_ew_blocks(n, EW_CAP), 256, 0, (hipStream_t)stream>>>(ema, src, decay, n);
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -16,7 +16,7 @@
 // broadcast).  Wider c3 splits the output channels over blockIdx.y so that the slab stays <= 64 KiB.
 #include <hip/hip_runtime.h>
 
-#include "dy_common.h"
+#include "dy_host.h"
 
 namespace {
 
@@ -312,14 +312,13 @@ __global__ __launch_bounds__(PC_THREADS) void pconv_mfma_kernel(const T* __restr
   }
 }
 
-bool aligned16(const void* p, long ld) { return p == nullptr || (((uintptr_t)p) % 16 == 0 && ld % 8 == 0); }
-
 template <typename T>
 int launch_mfma(const void* src, long src_ld, void* dst, long dst_ld, const void* wp, int N, int H, int W, int C, int c3,
                 int accumulate, const void* add, long add_ld, hipStream_t st) {
   const int KC = (c3 + 31) / 32, NT = (c3 + 15) / 16;
-  const int vec_in = c3 % 8 == 0 && aligned16(src, src_ld);
-  const int vec_pass = c3 % 8 == 0 && (C - c3) % 8 == 0 && aligned16(src, src_ld) && aligned16(dst, dst_ld) && aligned16(add, add_ld);
+  const int vec_in = c3 % 8 == 0 && dy_aligned16(src, src_ld, sizeof(T));
+  const int vec_pass = c3 % 8 == 0 && (C - c3) % 8 == 0 && vec_in && dy_aligned16(dst, dst_ld, sizeof(T)) &&
+                       (add == nullptr || dy_aligned16(add, add_ld, sizeof(T)));
   // 32-column tiles unless 16-column ones waste fewer pixel slots at the right edge (W = 40: 48 vs 64 columns)
   const int MT = ((W + 15) / 16 * 16 - W) < ((W + 31) / 32 * 32 - W) ? 1 : 2, TW = 16 * MT;
   dim3 grid((unsigned)((W + TW - 1) / TW), (unsigned)((H + MF_TH - 1) / MF_TH), (unsigned)N);
@@ -350,10 +349,9 @@ int pconv_cob(int c3) {                     // output channels per block: the sm
 }
 
 int check_pview(const char* who, const void* p, long ld, int C, int dtype) {
-  const int es = dtype == DY_F32 ? 4 : 2;
   DY_CHECK(p != nullptr, "%s: null pointer", who);
   DY_CHECK(ld >= C, "%s: pixel stride %ld < C=%d", who, ld, C);
-  DY_CHECK(((uintptr_t)p) % es == 0, "%s: misaligned pointer", who);
+  DY_CHECK(((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: misaligned pointer", who);
   return 0;
 }
 
@@ -403,19 +401,16 @@ int launch_wgrad(const void* x, long x_ld, const void* dy, long dy_ld, float* dw
 int check_common(const char* who, int N, int H, int W, int C, int c3, int dtype) {
   DY_CHECK(N > 0 && H > 0 && W > 0, "%s: bad shape %dx%dx%d", who, N, H, W);
   DY_CHECK(c3 >= 1 && c3 <= 128 && c3 <= C, "%s: c3=%d must be in [1, min(C=%d, 128)]", who, c3, C);
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "%s: bad dtype %d", who, dtype);
-  return 0;
+  return dy_check_dtype(who, dtype);
 }
 
 }  // namespace
 
-#define PC_DISPATCH(dtype, FN, ...) \
-  ((dtype) == DY_F32 ? FN<float>(__VA_ARGS__) : ((dtype) == DY_BF16 ? FN<bf16_t>(__VA_ARGS__) : FN<f16_t>(__VA_ARGS__)))
-
 static bool use_mfma(int c3, int dtype) { return dtype != DY_F32 && c3 >= 16; }
 
 extern "C" int dy_pconv_pack(const float* w, void* wp, int c3, int transposed, int dtype, void* stream) {
-  DY_CHECK(w && wp && c3 >= 16 && c3 <= 128 && dtype != DY_F32, "dy_pconv_pack: bad args (16-bit weights for c3 in [16, 128])");
+  DY_CHECK(w && wp && c3 >= 16 && c3 <= 128 && (dtype == DY_BF16 || dtype == DY_F16),
+           "dy_pconv_pack: bad args (16-bit weights for c3 in [16, 128])");
   const int KC = (c3 + 31) / 32, NT = (c3 + 15) / 16;
   const long total = 9L * KC * NT * 512;
   const unsigned blocks = (unsigned)((total + PC_THREADS - 1) / PC_THREADS);
@@ -439,7 +434,10 @@ extern "C" int dy_pconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, 
     return dtype == DY_BF16 ? launch_mfma<bf16_t>(x, x_ld, y, y_ld, wp, N, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream)
                             : launch_mfma<f16_t>(x, x_ld, y, y_ld, wp, N, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream);
   }
-  return PC_DISPATCH(dtype, launch_conv, x, x_ld, y, y_ld, w, 0, (long)N * H * W, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream);
+  int r = 0;
+  DY_DISPATCH_DTYPE("dy_pconv_fwd", dtype,
+                    r = launch_conv<T>(x, x_ld, y, y_ld, w, 0, (long)N * H * W, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream));
+  return r;
 }
 
 extern "C" int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, const float* w, const void* wp, int N, int H,
@@ -455,8 +453,11 @@ extern "C" int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t d
     return dtype == DY_BF16 ? launch_mfma<bf16_t>(dy, dy_ld, dx, dx_ld, wp, N, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld, (hipStream_t)stream)
                             : launch_mfma<f16_t>(dy, dy_ld, dx, dx_ld, wp, N, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld, (hipStream_t)stream);
   }
-  return PC_DISPATCH(dtype, launch_conv, dy, dy_ld, dx, dx_ld, w, 1, (long)N * H * W, H, W, C, c3, accumulate ? 1 : 0, add_src,
-                     add_ld, (hipStream_t)stream);
+  int r = 0;
+  DY_DISPATCH_DTYPE("dy_pconv_dgrad", dtype,
+                    r = launch_conv<T>(dy, dy_ld, dx, dx_ld, w, 1, (long)N * H * W, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld,
+                                       (hipStream_t)stream));
+  return r;
 }
 
 extern "C" int dy_pconv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw, int N, int H, int W, int c3,
@@ -465,6 +466,8 @@ extern "C" int dy_pconv_wgrad(const void* x, int64_t x_ld, const void* dy, int64
   if (int e = check_pview("dy_pconv_wgrad(x)", x, x_ld, c3, dtype)) return e;
   if (int e = check_pview("dy_pconv_wgrad(dy)", dy, dy_ld, c3, dtype)) return e;
   DY_CHECK(dw != nullptr && scratch != nullptr, "dy_pconv_wgrad: null dw / scratch");
-  return PC_DISPATCH(dtype, launch_wgrad, x, x_ld, dy, dy_ld, dw, (long)N * H * W, H, W, c3, scratch, scratch_elems,
-                     (hipStream_t)stream);
+  int r = 0;
+  DY_DISPATCH_DTYPE("dy_pconv_wgrad", dtype,
+                    r = launch_wgrad<T>(x, x_ld, dy, dy_ld, dw, (long)N * H * W, H, W, c3, scratch, scratch_elems, (hipStream_t)stream));
+  return r;
 }

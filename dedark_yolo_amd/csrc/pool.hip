@@ -2,15 +2,12 @@
 // Replaces MaxPool2d in SPPF (reference ultralytics/nn/modules/block.py:331-338) and ASFF (block.py:58,85-86),
 // nn.Upsample / F.interpolate(nearest) (yolov8.yaml head; block.py:91,97,99), torch.cat / chunk (conv.py:473,
 // block.py:385-387), the ASFF softmax blend (block.py:103-111).
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
 
-inline int ew_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+constexpr int EW_CAP = 4096;   // blocks of an element-wise launch
 
 // ---- max pool: first maximum in (kh, kw) scan order wins (ATen max_pool2d semantics); arg = kh*k + kw ---------------
 template <typename T>
@@ -266,41 +263,18 @@ __global__ void asff_bwd_kernel(const T* __restrict__ dout, long lddo, const T* 
   }
 }
 
-int check_view(const char* who, const void* p, long ld, int C, int dtype) {
-  const int ve = dtype == DY_F32 ? 4 : 8, es = dtype == DY_F32 ? 4 : 2;
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(C > 0 && C % ve == 0, "%s: C=%d must be a multiple of %d", who, C, ve);
-  DY_CHECK(ld >= C && (ld * es) % 16 == 0 && ((uintptr_t)p) % 16 == 0, "%s: view not 16-byte aligned (ld=%ld)", who, ld);
-  return 0;
-}
-
 }  // namespace
-
-#define DISPATCH(dtype, KERNEL, grid, ...)                                              \
-  do {                                                                                  \
-    if ((dtype) == DY_F32) KERNEL<float><<<grid, 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); \
-    else if ((dtype) == DY_F16) KERNEL<f16_t><<<grid, 256, 0, (hipStream_t)stream>>>(__VA_ARGS__);\
-    else KERNEL<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>(__VA_ARGS__);                  \
-    DY_LAUNCH_CHECK();                                                                  \
-  } while (0)
 
 extern "C" int dy_maxpool_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, uint8_t* argmax, int N, int H, int W, int C,
                               int k, int stride, int pad, int Ho, int Wo, int dtype, void* stream) {
-  if (int e = check_view("dy_maxpool_fwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check_view("dy_maxpool_fwd(y)", y, y_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_maxpool_fwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_maxpool_fwd(y)", y, y_ld, C, dtype)) return e;
   DY_CHECK(k >= 1 && k <= 15 && stride >= 1 && pad >= 0 && 2 * pad <= k, "dy_maxpool_fwd: bad window");
   DY_CHECK(Ho == (H + 2 * pad - k) / stride + 1 && Wo == (W + 2 * pad - k) / stride + 1, "dy_maxpool_fwd: bad output size");
-  const int ve = dtype == DY_F32 ? 4 : 8;
-  const int blocks = ew_blocks((long)N * Ho * Wo * (C / ve));
-  if (dtype == DY_F32)
-    maxpool_fwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)x, x_ld, (float*)y, y_ld, argmax, N, H, W, C,
-                                                                       k, stride, pad, Ho, Wo);
-  else if ((dtype) == DY_F16)
-    maxpool_fwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)x, x_ld, (f16_t*)y, y_ld, argmax, N, H, W,
-                                                                        C, k, stride, pad, Ho, Wo);
-  else
-    maxpool_fwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, x_ld, (bf16_t*)y, y_ld, argmax, N, H, W,
-                                                                        C, k, stride, pad, Ho, Wo);
+  const int blocks = dy_ew_blocks((long)N * Ho * Wo * (C / dy_vec_elems(dtype)), EW_CAP);
+  DY_DISPATCH_DTYPE("dy_maxpool_fwd", dtype,
+                    maxpool_fwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)x, x_ld, (T*)y, y_ld, argmax, N, H, W, C, k,
+                                                                                   stride, pad, Ho, Wo));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -308,81 +282,59 @@ extern "C" int dy_maxpool_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld
 extern "C" int dy_maxpool_bwd(const void* dy, int64_t dy_ld, const uint8_t* argmax, void* dx, int64_t dx_ld, int N, int H,
                               int W, int C, int k, int stride, int pad, int Ho, int Wo, int accumulate, int dtype,
                               void* stream) {
-  if (int e = check_view("dy_maxpool_bwd(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check_view("dy_maxpool_bwd(dx)", dx, dx_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_maxpool_bwd(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_maxpool_bwd(dx)", dx, dx_ld, C, dtype)) return e;
   DY_CHECK(argmax != nullptr, "dy_maxpool_bwd: null argmax");
-  const int ve = dtype == DY_F32 ? 4 : 8;
-  const int blocks = ew_blocks((long)N * H * W * (C / ve));
-  if (dtype == DY_F32)
-    maxpool_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)dy, dy_ld, argmax, (float*)dx, dx_ld, N, H, W,
-                                                                       C, k, stride, pad, Ho, Wo, accumulate);
-  else if ((dtype) == DY_F16)
-    maxpool_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)dy, dy_ld, argmax, (f16_t*)dx, dx_ld, N, H,
-                                                                        W, C, k, stride, pad, Ho, Wo, accumulate);
-  else
-    maxpool_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)dy, dy_ld, argmax, (bf16_t*)dx, dx_ld, N, H,
-                                                                        W, C, k, stride, pad, Ho, Wo, accumulate);
+  const int blocks = dy_ew_blocks((long)N * H * W * (C / dy_vec_elems(dtype)), EW_CAP);
+  DY_DISPATCH_DTYPE("dy_maxpool_bwd", dtype,
+                    maxpool_bwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)dy, dy_ld, argmax, (T*)dx, dx_ld, N, H, W, C,
+                                                                                   k, stride, pad, Ho, Wo, accumulate));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_upsample_nearest_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, int N, int H, int W, int C, int scale,
                                        int dtype, void* stream) {
-  if (int e = check_view("dy_upsample_nearest_fwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check_view("dy_upsample_nearest_fwd(y)", y, y_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_upsample_nearest_fwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_upsample_nearest_fwd(y)", y, y_ld, C, dtype)) return e;
   DY_CHECK(scale >= 1, "dy_upsample_nearest_fwd: bad scale");
-  const int ve = dtype == DY_F32 ? 4 : 8;
-  const int blocks = ew_blocks((long)N * H * scale * W * scale * (C / ve));
-  if (dtype == DY_F32)
-    upsample_fwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)x, x_ld, (float*)y, y_ld, N, H, W, C, scale);
-  else if ((dtype) == DY_F16)
-    upsample_fwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)x, x_ld, (f16_t*)y, y_ld, N, H, W, C, scale);
-  else
-    upsample_fwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, x_ld, (bf16_t*)y, y_ld, N, H, W, C, scale);
+  const int blocks = dy_ew_blocks((long)N * H * scale * W * scale * (C / dy_vec_elems(dtype)), EW_CAP);
+  DY_DISPATCH_DTYPE("dy_upsample_nearest_fwd", dtype,
+                    upsample_fwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)x, x_ld, (T*)y, y_ld, N, H, W, C, scale));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_upsample_nearest_bwd(const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, int N, int H, int W, int C,
                                        int scale, int accumulate, int dtype, void* stream) {
-  if (int e = check_view("dy_upsample_nearest_bwd(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check_view("dy_upsample_nearest_bwd(dx)", dx, dx_ld, C, dtype)) return e;
-  const int ve = dtype == DY_F32 ? 4 : 8;
-  const int blocks = ew_blocks((long)N * H * W * (C / ve));
-  if (dtype == DY_F32)
-    upsample_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)dy, dy_ld, (float*)dx, dx_ld, N, H, W, C, scale,
-                                                                        accumulate);
-  else if ((dtype) == DY_F16)
-    upsample_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)dy, dy_ld, (f16_t*)dx, dx_ld, N, H, W, C,
-                                                                         scale, accumulate);
-  else
-    upsample_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)dy, dy_ld, (bf16_t*)dx, dx_ld, N, H, W, C,
-                                                                         scale, accumulate);
+  if (int e = dy_check_view("dy_upsample_nearest_bwd(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_upsample_nearest_bwd(dx)", dx, dx_ld, C, dtype)) return e;
+  const int blocks = dy_ew_blocks((long)N * H * W * (C / dy_vec_elems(dtype)), EW_CAP);
+  DY_DISPATCH_DTYPE("dy_upsample_nearest_bwd", dtype,
+                    upsample_bwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)dy, dy_ld, (T*)dx, dx_ld, N, H, W, C, scale,
+                                                                                    accumulate));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_copy2d(const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int64_t pixels, int C, int accumulate,
                          int dtype, void* stream) {
-  if (int e = check_view("dy_copy2d(src)", src, src_ld, C, dtype)) return e;
-  if (int e = check_view("dy_copy2d(dst)", dst, dst_ld, C, dtype)) return e;
-  const int ve = dtype == DY_F32 ? 4 : 8;
-  const int blocks = ew_blocks(pixels * (C / ve));
-  if (dtype == DY_F32)
-    copy2d_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)src, src_ld, (float*)dst, dst_ld, pixels, C, accumulate);
-  else if ((dtype) == DY_F16)
-    copy2d_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)src, src_ld, (f16_t*)dst, dst_ld, pixels, C,
-                                                                   accumulate);
-  else
-    copy2d_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)src, src_ld, (bf16_t*)dst, dst_ld, pixels, C,
-                                                                   accumulate);
+  if (int e = dy_check_view("dy_copy2d(src)", src, src_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_copy2d(dst)", dst, dst_ld, C, dtype)) return e;
+  const int blocks = dy_ew_blocks(pixels * (C / dy_vec_elems(dtype)), EW_CAP);
+  DY_DISPATCH_DTYPE("dy_copy2d", dtype,
+                    copy2d_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)src, src_ld, (T*)dst, dst_ld, pixels, C,
+                                                                              accumulate));
   DY_LAUNCH_CHECK();
   return 0;
 }
 
+// an explicit table: bf16 <-> f16 kernels are not instantiated
 extern "C" int dy_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream) {
   DY_CHECK(src && dst && n >= 0, "dy_cast: bad args");
-  const int blocks = ew_blocks(n);
+  if (int e = dy_check_dtype("dy_cast(src)", src_dtype)) return e;
+  if (int e = dy_check_dtype("dy_cast(dst)", dst_dtype)) return e;
+  const int blocks = dy_ew_blocks(n, EW_CAP);
   hipStream_t st = (hipStream_t)stream;
   DY_CHECK(src_dtype == dst_dtype || src_dtype == DY_F32 || dst_dtype == DY_F32, "dy_cast: bf16 <-> f16 goes through f32");
   if (src_dtype == DY_F32 && dst_dtype == DY_BF16) cast_kernel<float, bf16_t><<<blocks, 256, 0, st>>>((const float*)src, (bf16_t*)dst, n);
@@ -398,27 +350,19 @@ extern "C" int dy_cast(const void* src, int src_dtype, void* dst, int dst_dtype,
 extern "C" int dy_asff_fuse_fwd(const void* x0, int64_t ld0, const void* x1, int64_t ld1, const void* x2, int64_t ld2,
                                 const void* logits, int64_t ldl, void* out, int64_t ldo, int64_t pixels, int C, int dtype,
                                 void* stream) {
-  if (int e = check_view("dy_asff_fuse_fwd(x0)", x0, ld0, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_fwd(x1)", x1, ld1, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_fwd(x0)", x0, ld0, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_fwd(x1)", x1, ld1, C, dtype)) return e;
   if (x2)
-    if (int e = check_view("dy_asff_fuse_fwd(x2)", x2, ld2, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_fwd(out)", out, ldo, C, dtype)) return e;
+    if (int e = dy_check_view("dy_asff_fuse_fwd(x2)", x2, ld2, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_fwd(out)", out, ldo, C, dtype)) return e;
   DY_CHECK(logits && ldl >= (x2 ? 3 : 2), "dy_asff_fuse_fwd: bad logits");
   long waves = pixels;
   int blocks = (int)((waves + 3) / 4);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  if (dtype == DY_F32)
-    asff_fwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)x0, ld0, (const float*)x1, ld1, (const float*)x2, ld2,
-                                                                    (const float*)logits, ldl, (float*)out, ldo, pixels, C);
-  else if ((dtype) == DY_F16)
-    asff_fwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)x0, ld0, (const f16_t*)x1, ld1,
-                                                                     (const f16_t*)x2, ld2, (const f16_t*)logits, ldl,
-                                                                     (f16_t*)out, ldo, pixels, C);
-  else
-    asff_fwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x0, ld0, (const bf16_t*)x1, ld1,
-                                                                     (const bf16_t*)x2, ld2, (const bf16_t*)logits, ldl,
-                                                                     (bf16_t*)out, ldo, pixels, C);
+  DY_DISPATCH_DTYPE("dy_asff_fuse_fwd", dtype,
+                    asff_fwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)x0, ld0, (const T*)x1, ld1, (const T*)x2, ld2,
+                                                                                (const T*)logits, ldl, (T*)out, ldo, pixels, C));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -427,32 +371,25 @@ extern "C" int dy_asff_fuse_bwd(const void* dout, int64_t lddo, const void* x0, 
                                 const void* x2, int64_t ld2, const void* logits, int64_t ldl, void* dx0, int64_t ldd0, void* dx1,
                                 int64_t ldd1, void* dx2, int64_t ldd2, void* dlogits, int64_t lddl, int64_t pixels, int C,
                                 int acc0, int acc1, int acc2, int dtype, void* stream) {
-  if (int e = check_view("dy_asff_fuse_bwd(dout)", dout, lddo, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_bwd(x0)", x0, ld0, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_bwd(x1)", x1, ld1, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_bwd(dout)", dout, lddo, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_bwd(x0)", x0, ld0, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_bwd(x1)", x1, ld1, C, dtype)) return e;
   if (x2)
-    if (int e = check_view("dy_asff_fuse_bwd(x2)", x2, ld2, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_bwd(dx0)", dx0, ldd0, C, dtype)) return e;
-  if (int e = check_view("dy_asff_fuse_bwd(dx1)", dx1, ldd1, C, dtype)) return e;
+    if (int e = dy_check_view("dy_asff_fuse_bwd(x2)", x2, ld2, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_bwd(dx0)", dx0, ldd0, C, dtype)) return e;
+  if (int e = dy_check_view("dy_asff_fuse_bwd(dx1)", dx1, ldd1, C, dtype)) return e;
   if (x2)
-    if (int e = check_view("dy_asff_fuse_bwd(dx2)", dx2, ldd2, C, dtype)) return e;
+    if (int e = dy_check_view("dy_asff_fuse_bwd(dx2)", dx2, ldd2, C, dtype)) return e;
   DY_CHECK(logits && dlogits && ldl >= (x2 ? 3 : 2) && lddl >= (x2 ? 3 : 2), "dy_asff_fuse_bwd: bad logits");
   int blocks = (int)((pixels + 3) / 4);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   const int lgw = (int)(lddl < 8 ? lddl : 8);
-  if (dtype == DY_F32)
-    asff_bwd_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(
-        (const float*)dout, lddo, (const float*)x0, ld0, (const float*)x1, ld1, (const float*)x2, ld2, (const float*)logits, ldl,
-        (float*)dx0, ldd0, (float*)dx1, ldd1, (float*)dx2, ldd2, (float*)dlogits, lddl, pixels, C, acc0, acc1, acc2, lgw);
-  else if ((dtype) == DY_F16)
-    asff_bwd_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(
-        (const f16_t*)dout, lddo, (const f16_t*)x0, ld0, (const f16_t*)x1, ld1, (const f16_t*)x2, ld2, (const f16_t*)logits,
-        ldl, (f16_t*)dx0, ldd0, (f16_t*)dx1, ldd1, (f16_t*)dx2, ldd2, (f16_t*)dlogits, lddl, pixels, C, acc0, acc1, acc2, lgw);
-  else
-    asff_bwd_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>(
-        (const bf16_t*)dout, lddo, (const bf16_t*)x0, ld0, (const bf16_t*)x1, ld1, (const bf16_t*)x2, ld2, (const bf16_t*)logits,
-        ldl, (bf16_t*)dx0, ldd0, (bf16_t*)dx1, ldd1, (bf16_t*)dx2, ldd2, (bf16_t*)dlogits, lddl, pixels, C, acc0, acc1, acc2, lgw);
+  DY_DISPATCH_DTYPE("dy_asff_fuse_bwd", dtype,
+                    asff_bwd_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>((const T*)dout, lddo, (const T*)x0, ld0, (const T*)x1, ld1,
+                                                                                (const T*)x2, ld2, (const T*)logits, ldl, (T*)dx0, ldd0,
+                                                                                (T*)dx1, ldd1, (T*)dx2, ldd2, (T*)dlogits, lddl, pixels, C,
+                                                                                acc0, acc1, acc2, lgw));
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -13,7 +13,7 @@
 // Sums run in a fixed order: one thread sums the K keypoints of a positive, one block per image sums its positives in a
 // strided-then-tree order, one thread sums the images.  No float atomics (two runs agree bit for bit) and no host
 // synchronisation: the positive counts stay on the device.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(NT) void kpt_oks_kernel(const float* __restrict__ g
 // d points at the caller's descriptor; which fields are needed depends on the entry (decode: maps only)
 int make_pose(const dy_pose_desc* d, Pose& p, bool loss, const char* who) {
   DY_CHECK(d && d->n_levels >= 1 && d->n_levels <= DY_POSE_MAX_LEVELS, "%s: bad descriptor / level count", who);
-  DY_CHECK(d->dtype == DY_F32 || d->dtype == DY_BF16 || d->dtype == DY_F16, "%s: bad dtype %d", who, d->dtype);
+  if (int e = dy_check_dtype(who, d->dtype)) return e;
   DY_CHECK(d->B > 0 && d->K > 0 && (d->ndim == 2 || d->ndim == 3), "%s: bad B / K / ndim (%d, %d, %d)", who, d->B, d->K, d->ndim);
   p.nl = d->n_levels; p.B = d->B; p.K = d->K; p.ndim = d->ndim;
   int off = 0;
@@ -287,9 +287,7 @@ extern "C" int dy_pose_loss_fwd(const dy_pose_desc* d, float hyp_pose, float hyp
   DY_CHECK(work && det_out && out, "dy_pose_loss_fwd: null output");
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("pose_pos_kernel");
-  if (d->dtype == DY_F32) launch_pos<float>(p, work, st);
-  else if (d->dtype == DY_F16) launch_pos<f16_t>(p, work, st);
-  else launch_pos<bf16_t>(p, work, st);
+  DY_DISPATCH_DTYPE("dy_pose_loss_fwd", d->dtype, launch_pos<T>(p, work, st));
   DY_LAUNCH_CHECK();
   float* img = work + 3L * p.B * p.A;
   dy_note_kernel("pose_image_kernel");
@@ -306,7 +304,7 @@ extern "C" int dy_pose_loss_bwd(const dy_pose_desc* d, const float* work, const 
   Pose p;
   if (int e = make_pose(d, p, true, "dy_pose_loss_bwd")) return e;
   DY_CHECK(work && grad_out && dkpt, "dy_pose_loss_bwd: null argument");
-  const int ve = d->dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(d->dtype);
   DY_CHECK(dk_ld >= ((long)d->K * d->ndim + ve - 1) / ve * ve, "dy_pose_loss_bwd: dk_ld %ld below the padded keypoint width",
            (long)dk_ld);
   DyPoseGrad g;
@@ -318,9 +316,8 @@ extern "C" int dy_pose_loss_bwd(const dy_pose_desc* d, const float* work, const 
   const int blocks = dy_cdiv((long)p.B * p.A * dk_ld, NT);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("pose_bwd_kernel");
-  if (d->dtype == DY_F32) pose_bwd_kernel<float><<<blocks, NT, 0, st>>>(p, img, grad_out, hyp_pose, hyp_kobj, g, dk_ld);
-  else if (d->dtype == DY_F16) pose_bwd_kernel<f16_t><<<blocks, NT, 0, st>>>(p, img, grad_out, hyp_pose, hyp_kobj, g, dk_ld);
-  else pose_bwd_kernel<bf16_t><<<blocks, NT, 0, st>>>(p, img, grad_out, hyp_pose, hyp_kobj, g, dk_ld);
+  DY_DISPATCH_DTYPE("dy_pose_loss_bwd", d->dtype,
+                    pose_bwd_kernel<T><<<blocks, NT, 0, st>>>(p, img, grad_out, hyp_pose, hyp_kobj, g, dk_ld));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -332,9 +329,7 @@ extern "C" int dy_pose_kpt_decode(const dy_pose_desc* d, int nc, float* y, void*
   dim3 grid(dy_cdiv(p.A, NT), p.K * p.ndim, p.B);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("pose_decode_kernel");
-  if (d->dtype == DY_F32) pose_decode_kernel<float><<<grid, NT, 0, st>>>(p, nc, y);
-  else if (d->dtype == DY_F16) pose_decode_kernel<f16_t><<<grid, NT, 0, st>>>(p, nc, y);
-  else pose_decode_kernel<bf16_t><<<grid, NT, 0, st>>>(p, nc, y);
+  DY_DISPATCH_DTYPE("dy_pose_kpt_decode", d->dtype, pose_decode_kernel<T><<<grid, NT, 0, st>>>(p, nc, y));
   DY_LAUNCH_CHECK();
   return 0;
 }

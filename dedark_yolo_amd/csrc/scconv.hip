@@ -6,7 +6,7 @@
 // and their backward passes.  Layout NHWC views (pointer + pixel stride), f32 / bf16 / f16; all sums in f32 per thread, a fixed-order
 // LDS reduction over the rows of a block and f64 atomics across blocks.  One block = pixels of ONE image (blockIdx.y), so every sum
 // is keyed (image, channel).  These kernels are HBM-bound elementwise / reduction passes (2 reads + 1 write or 2 reads).
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -386,15 +386,6 @@ __global__ __launch_bounds__(NT) void cru_fuse_bwd_apply_kernel(const T* __restr
   }
 }
 
-int check(const char* who, const void* p, long ld, int C, int dtype) {
-  const int ve = dtype == DY_F32 ? 4 : 8, es = dtype == DY_F32 ? 4 : 2;
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "%s: bad dtype", who);
-  DY_CHECK(C > 0 && C % ve == 0, "%s: C=%d must be a multiple of %d", who, C, ve);
-  DY_CHECK(ld >= C && (ld * es) % 16 == 0 && ((uintptr_t)p) % 16 == 0, "%s: view not 16-byte aligned (ld=%ld)", who, ld);
-  return 0;
-}
-
 inline dim3 grid_for(long HW, int N, int vectors_per_pixel) {
   long work = HW * vectors_per_pixel;
   long bx = (work + NT * 4 - 1) / (NT * 4);
@@ -403,82 +394,86 @@ inline dim3 grid_for(long HW, int N, int vectors_per_pixel) {
   return dim3((unsigned)bx, (unsigned)N);
 }
 
-#define DY_SC_DISPATCH(dtype, ...)                                      \
-  do {                                                                  \
-    if ((dtype) == DY_F32) { using T = float; __VA_ARGS__; }            \
-    else if ((dtype) == DY_F16) { using T = f16_t; __VA_ARGS__; }       \
-    else { using T = bf16_t; __VA_ARGS__; }                             \
-    DY_LAUNCH_CHECK();                                                  \
-  } while (0)
-
 }  // namespace
 
 extern "C" int dy_chan_moments(const void* x, int64_t ld, int N, int64_t HW, int C, double* out, int dtype, void* stream) {
-  if (int e = check("dy_chan_moments", x, ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_chan_moments", x, ld, C, dtype)) return e;
   DY_CHECK(out && N > 0 && HW > 0, "dy_chan_moments: bad args");
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const dim3 g = grid_for(HW, N, C / ve);
   const size_t shm = (size_t)NT * 2 * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  DY_SC_DISPATCH(dtype, chan_moments_kernel<T><<<g, NT, shm, st>>>((const T*)x, ld, HW, C, out));
+  DY_DISPATCH_DTYPE("dy_chan_moments", dtype, chan_moments_kernel<T><<<g, NT, shm, st>>>((const T*)x, ld, HW, C, out));
+  DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_sru_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, int N, int64_t HW, int C, int groups, const double* moments,
                           const float* gamma, const float* beta, float eps, int dtype, void* stream) {
-  if (int e = check("dy_sru_fwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check("dy_sru_fwd(y)", y, y_ld, C, dtype)) return e;
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  if (int e = dy_check_view("dy_sru_fwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_sru_fwd(y)", y, y_ld, C, dtype)) return e;
+  const int ve = dy_vec_elems(dtype);
   DY_CHECK(moments && gamma && beta && groups > 0 && groups <= 64 && C % groups == 0 && (C / 2) % ve == 0 && HW * (C / groups) > 1,
            "dy_sru_fwd: bad group layout");
   const dim3 g = grid_for(HW, N, C / 2 / ve);
   hipStream_t st = (hipStream_t)stream;
-  DY_SC_DISPATCH(dtype, sru_fwd_kernel<T><<<g, NT, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, HW, C, groups, moments, gamma, beta, eps));
+  DY_DISPATCH_DTYPE("dy_sru_fwd", dtype,
+                    sru_fwd_kernel<T><<<g, NT, 0, st>>>((const T*)x, x_ld, (T*)y, y_ld, HW, C, groups, moments, gamma, beta, eps));
+  DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_sru_bwd(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, int N, int64_t HW, int C,
                           int groups, const double* moments, const float* gamma, const float* beta, float eps, double* red, int dtype,
                           void* stream) {
-  if (int e = check("dy_sru_bwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check("dy_sru_bwd(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check("dy_sru_bwd(dx)", dx, dx_ld, C, dtype)) return e;
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  if (int e = dy_check_view("dy_sru_bwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_sru_bwd(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_sru_bwd(dx)", dx, dx_ld, C, dtype)) return e;
+  const int ve = dy_vec_elems(dtype);
   DY_CHECK(moments && gamma && beta && red && groups > 0 && groups <= 64 && C % groups == 0 && (C / 2) % ve == 0, "dy_sru_bwd: bad args");
   const dim3 g = grid_for(HW, N, C / 2 / ve);
   const size_t shm = (size_t)NT * 2 * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  DY_SC_DISPATCH(dtype, sru_bwd_reduce_kernel<T><<<g, NT, shm, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, HW, C, groups, moments, gamma,
-                                                                    beta, eps, red));
-  DY_SC_DISPATCH(dtype, sru_bwd_apply_kernel<T><<<g, NT, 0, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, (T*)dx, dx_ld, HW, C, groups, moments,
-                                                                  gamma, beta, eps, red));
+  DY_DISPATCH_DTYPE("dy_sru_bwd", dtype,
+                    sru_bwd_reduce_kernel<T><<<g, NT, shm, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, HW, C, groups, moments, gamma,
+                                                                 beta, eps, red));
+  DY_LAUNCH_CHECK();
+  DY_DISPATCH_DTYPE("dy_sru_bwd", dtype,
+                    sru_bwd_apply_kernel<T><<<g, NT, 0, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, (T*)dx, dx_ld, HW, C, groups,
+                                                              moments, gamma, beta, eps, red));
+  DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cru_fuse_fwd(const void* o, int64_t o_ld, void* res, int64_t r_ld, int N, int64_t HW, int C, const double* moments, int dtype,
                                void* stream) {
-  if (int e = check("dy_cru_fuse_fwd(o)", o, o_ld, 2 * C, dtype)) return e;
-  if (int e = check("dy_cru_fuse_fwd(res)", res, r_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_cru_fuse_fwd(o)", o, o_ld, 2 * C, dtype)) return e;
+  if (int e = dy_check_view("dy_cru_fuse_fwd(res)", res, r_ld, C, dtype)) return e;
   DY_CHECK(moments && C <= 2048, "dy_cru_fuse_fwd: bad args");
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const dim3 g = grid_for(HW, N, C / ve);
   const size_t shm = (size_t)2 * C * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  DY_SC_DISPATCH(dtype, cru_fuse_fwd_kernel<T><<<g, NT, shm, st>>>((const T*)o, o_ld, (T*)res, r_ld, HW, C, moments));
+  DY_DISPATCH_DTYPE("dy_cru_fuse_fwd", dtype, cru_fuse_fwd_kernel<T><<<g, NT, shm, st>>>((const T*)o, o_ld, (T*)res, r_ld, HW, C, moments));
+  DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_cru_fuse_bwd(const void* o, int64_t o_ld, const void* dres, int64_t d_ld, void* dout, int64_t do_ld, int N, int64_t HW, int C,
                                const double* moments, double* ds, int dtype, void* stream) {
-  if (int e = check("dy_cru_fuse_bwd(o)", o, o_ld, 2 * C, dtype)) return e;
-  if (int e = check("dy_cru_fuse_bwd(dres)", dres, d_ld, C, dtype)) return e;
-  if (int e = check("dy_cru_fuse_bwd(dout)", dout, do_ld, 2 * C, dtype)) return e;
+  if (int e = dy_check_view("dy_cru_fuse_bwd(o)", o, o_ld, 2 * C, dtype)) return e;
+  if (int e = dy_check_view("dy_cru_fuse_bwd(dres)", dres, d_ld, C, dtype)) return e;
+  if (int e = dy_check_view("dy_cru_fuse_bwd(dout)", dout, do_ld, 2 * C, dtype)) return e;
   DY_CHECK(moments && ds && C <= 2048, "dy_cru_fuse_bwd: bad args");
-  const int ve = dtype == DY_F32 ? 4 : 8;
+  const int ve = dy_vec_elems(dtype);
   const dim3 g = grid_for(HW, N, C / ve);
   hipStream_t st = (hipStream_t)stream;
   const size_t shm_r = (size_t)NT * 2 * ve * sizeof(float), shm_a = (size_t)4 * C * sizeof(float);
-  DY_SC_DISPATCH(dtype, cru_fuse_bwd_reduce_kernel<T><<<g, NT, shm_r, st>>>((const T*)o, o_ld, (const T*)dres, d_ld, HW, C, ds));
-  DY_SC_DISPATCH(dtype, cru_fuse_bwd_apply_kernel<T><<<g, NT, shm_a, st>>>((const T*)dres, d_ld, (T*)dout, do_ld, HW, C, moments, ds));
+  DY_DISPATCH_DTYPE("dy_cru_fuse_bwd", dtype,
+                    cru_fuse_bwd_reduce_kernel<T><<<g, NT, shm_r, st>>>((const T*)o, o_ld, (const T*)dres, d_ld, HW, C, ds));
+  DY_LAUNCH_CHECK();
+  DY_DISPATCH_DTYPE("dy_cru_fuse_bwd", dtype,
+                    cru_fuse_bwd_apply_kernel<T><<<g, NT, shm_a, st>>>((const T*)dres, d_ld, (T*)dout, do_ld, HW, C, moments, ds));
+  DY_LAUNCH_CHECK();
   return 0;
 }

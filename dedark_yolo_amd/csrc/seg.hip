@@ -8,7 +8,7 @@
 //   item    = hyp_box / B * sum_i mean_{p in i} l_p
 // Every sum has a fixed order (in-block trees, per-image sequential sums): no float atomics, two runs agree bit for bit.  The
 // positive counts stay on the device; nothing here synchronises with the host.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -466,13 +466,12 @@ __global__ __launch_bounds__(NT) void seg_mask_iou_kernel(const void* __restrict
 
 int check_seg(const dy_seg_desc* d, const char* who) {
   DY_CHECK(d && d->mc && d->proto && d->target_gt_idx && d->fg_mask && d->target_box && d->pos && d->npos, "%s: null pointer", who);
-  DY_CHECK(d->dtype == DY_F32 || d->dtype == DY_BF16 || d->dtype == DY_F16, "%s: bad dtype %d", who, d->dtype);
+  if (int e = dy_check_dtype(who, d->dtype)) return e;
   DY_CHECK(d->nm == NM, "%s: nm=%d (the kernels are built for %d mask coefficients)", who, d->nm, NM);
   DY_CHECK(d->B > 0 && d->A > 0 && d->mh > 0 && d->mw > 0, "%s: empty geometry", who);
   DY_CHECK(d->mc_ld >= NM && d->proto_ld >= NM, "%s: mc_ld / proto_ld below nm", who);
-  const int es = d->dtype == DY_F32 ? 4 : 2;
-  DY_CHECK((d->mc_ld * es) % 16 == 0 && (d->proto_ld * es) % 16 == 0 && ((uintptr_t)d->mc) % 16 == 0 && ((uintptr_t)d->proto) % 16 == 0,
-           "%s: mc / proto rows must be 16-byte aligned", who);
+  const int es = dy_elem_size(d->dtype);
+  DY_CHECK(dy_aligned16(d->mc, d->mc_ld, es) && dy_aligned16(d->proto, d->proto_ld, es), "%s: mc / proto rows must be 16-byte aligned", who);
   DY_CHECK(d->img_h > 0.f && d->img_w > 0.f, "%s: bad image size", who);
   DY_CHECK(d->masks != nullptr && d->mask_h > 0 && d->mask_w > 0 && (d->mask_dtype == 0 || d->mask_dtype == 1), "%s: bad gt masks", who);
   DY_CHECK(d->overlap || (d->gt_rows && d->n_max > 0), "%s: per-instance masks need gt_rows", who);
@@ -511,9 +510,7 @@ extern "C" int dy_seg_loss_fwd(const dy_seg_desc* d, float hyp_box, float* lossp
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(seg_grid_x(d), d->B);
   dy_note_kernel("seg_loss_fwd_kernel");
-  if (d->dtype == DY_F32) seg_loss_fwd_kernel<float><<<grid, NT, 0, st>>>(s, lossp);
-  else if (d->dtype == DY_F16) seg_loss_fwd_kernel<f16_t><<<grid, NT, 0, st>>>(s, lossp);
-  else seg_loss_fwd_kernel<bf16_t><<<grid, NT, 0, st>>>(s, lossp);
+  DY_DISPATCH_DTYPE("dy_seg_loss_fwd", d->dtype, seg_loss_fwd_kernel<T><<<grid, NT, 0, st>>>(s, lossp));
   DY_LAUNCH_CHECK();
   float* means = lossp + (long)d->B * d->A;
   seg_image_mean_kernel<<<d->B, NT, 0, st>>>(lossp, d->npos, d->A, means);
@@ -527,37 +524,29 @@ extern "C" int dy_seg_loss_bwd(const dy_seg_desc* d, const float* grad_out, floa
                                int64_t dproto_ld, void* stream) {
   if (int e = check_seg(d, "dy_seg_loss_bwd")) return e;
   DY_CHECK(grad_out && dmc && dproto, "dy_seg_loss_bwd: null output");
-  const int es = d->dtype == DY_F32 ? 4 : 2;
-  DY_CHECK(dmc_ld >= NM && dproto_ld >= NM && (dproto_ld * es) % 16 == 0 && ((uintptr_t)dproto) % 16 == 0,
+  const int es = dy_elem_size(d->dtype);
+  DY_CHECK(dmc_ld >= NM && dproto_ld >= NM && dy_aligned16(dproto, dproto_ld, es),
            "dy_seg_loss_bwd: dmc_ld / dproto_ld below nm or d proto rows not 16-byte aligned");
   const Seg s = seg_of(d);
   hipStream_t st = (hipStream_t)stream;
   dim3 g1(seg_grid_x(d), d->B), g2(dy_cdiv((long)d->mh * d->mw, NT), d->B);
   dy_note_kernel("seg_loss_dproto_kernel");
-  if (d->dtype == DY_F32) {
-    seg_loss_dmc_kernel<float><<<g1, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dmc, dmc_ld);
-    seg_loss_dproto_kernel<float><<<g2, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dproto, dproto_ld);
-  } else if (d->dtype == DY_F16) {
-    seg_loss_dmc_kernel<f16_t><<<g1, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dmc, dmc_ld);
-    seg_loss_dproto_kernel<f16_t><<<g2, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dproto, dproto_ld);
-  } else {
-    seg_loss_dmc_kernel<bf16_t><<<g1, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dmc, dmc_ld);
-    seg_loss_dproto_kernel<bf16_t><<<g2, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dproto, dproto_ld);
-  }
+  DY_DISPATCH_DTYPE("dy_seg_loss_bwd", d->dtype, {
+    seg_loss_dmc_kernel<T><<<g1, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dmc, dmc_ld);
+    seg_loss_dproto_kernel<T><<<g2, NT, 0, st>>>(s, grad_out, hyp_box, (char*)dproto, dproto_ld);
+  });
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int dy_bias_add(void* x, int64_t ld, const float* bias, int64_t pixels, int C, int dtype, void* stream) {
   DY_CHECK(x && bias && ld >= C && C > 0 && pixels >= 0, "dy_bias_add: bad args");
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "dy_bias_add: bad dtype %d", dtype);
+  if (int e = dy_check_dtype("dy_bias_add", dtype)) return e;
   if (pixels == 0) return 0;
   const int blocks = dy_cdiv(pixels * C, NT);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("seg_bias_add_kernel");
-  if (dtype == DY_F32) seg_bias_add_kernel<float><<<blocks, NT, 0, st>>>((float*)x, ld, bias, pixels, C);
-  else if (dtype == DY_F16) seg_bias_add_kernel<f16_t><<<blocks, NT, 0, st>>>((f16_t*)x, ld, bias, pixels, C);
-  else seg_bias_add_kernel<bf16_t><<<blocks, NT, 0, st>>>((bf16_t*)x, ld, bias, pixels, C);
+  DY_DISPATCH_DTYPE("dy_bias_add", dtype, seg_bias_add_kernel<T><<<blocks, NT, 0, st>>>((T*)x, ld, bias, pixels, C));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -565,14 +554,12 @@ extern "C" int dy_bias_add(void* x, int64_t ld, const float* bias, int64_t pixel
 extern "C" int dy_bias_grad(const void* dy, int64_t ld, int64_t pixels, int C, int dtype, float* scratch, int64_t scratch_elems, float* db,
                             void* stream) {
   DY_CHECK(dy && db && scratch && ld >= C && C > 0 && pixels >= 0, "dy_bias_grad: bad args");
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "dy_bias_grad: bad dtype %d", dtype);
+  if (int e = dy_check_dtype("dy_bias_grad", dtype)) return e;
   DY_CHECK(scratch_elems >= (int64_t)BG_CHUNKS * C, "dy_bias_grad: scratch needs %ld floats", (long)BG_CHUNKS * C);
   hipStream_t st = (hipStream_t)stream;
   dim3 g1(BG_CHUNKS, dy_cdiv(C, NT));
   dy_note_kernel("seg_bias_grad_final_kernel");
-  if (dtype == DY_F32) seg_bias_grad_partial_kernel<float><<<g1, NT, 0, st>>>((const float*)dy, ld, pixels, C, scratch);
-  else if (dtype == DY_F16) seg_bias_grad_partial_kernel<f16_t><<<g1, NT, 0, st>>>((const f16_t*)dy, ld, pixels, C, scratch);
-  else seg_bias_grad_partial_kernel<bf16_t><<<g1, NT, 0, st>>>((const bf16_t*)dy, ld, pixels, C, scratch);
+  DY_DISPATCH_DTYPE("dy_bias_grad", dtype, seg_bias_grad_partial_kernel<T><<<g1, NT, 0, st>>>((const T*)dy, ld, pixels, C, scratch));
   DY_LAUNCH_CHECK();
   seg_bias_grad_final_kernel<<<dy_cdiv(C, NT), NT, 0, st>>>(scratch, C, db);
   DY_LAUNCH_CHECK();
@@ -585,15 +572,14 @@ extern "C" int dy_seg_mask_decode(const void* proto, int64_t proto_ld, int nm, i
   DY_CHECK(n >= 0 && mh > 0 && mw > 0 && det_ld >= 6 + NM && proto_ld >= NM, "dy_seg_mask_decode: bad geometry");
   if (n == 0) return 0;
   DY_CHECK(proto && det && det_img && out, "dy_seg_mask_decode: null pointer");
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "dy_seg_mask_decode: bad dtype %d", dtype);
-  const int es = dtype == DY_F32 ? 4 : 2;
-  DY_CHECK((proto_ld * es) % 16 == 0 && ((uintptr_t)proto) % 16 == 0, "dy_seg_mask_decode: proto rows must be 16-byte aligned");
+  if (int e = dy_check_dtype("dy_seg_mask_decode", dtype)) return e;
+  DY_CHECK(dy_aligned16(proto, proto_ld, dy_elem_size(dtype)), "dy_seg_mask_decode: proto rows must be 16-byte aligned");
   const int blocks = dy_cdiv((long)n * mh * mw, NT);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("seg_mask_decode_kernel");
-  if (dtype == DY_F32) seg_mask_decode_kernel<float><<<blocks, NT, 0, st>>>((const float*)proto, proto_ld, mh, mw, det, det_ld, det_img, n, sx, sy, out);
-  else if (dtype == DY_F16) seg_mask_decode_kernel<f16_t><<<blocks, NT, 0, st>>>((const f16_t*)proto, proto_ld, mh, mw, det, det_ld, det_img, n, sx, sy, out);
-  else seg_mask_decode_kernel<bf16_t><<<blocks, NT, 0, st>>>((const bf16_t*)proto, proto_ld, mh, mw, det, det_ld, det_img, n, sx, sy, out);
+  DY_DISPATCH_DTYPE("dy_seg_mask_decode", dtype,
+                    seg_mask_decode_kernel<T><<<blocks, NT, 0, st>>>((const T*)proto, proto_ld, mh, mw, det, det_ld, det_img, n, sx, sy,
+                                                                     out));
   DY_LAUNCH_CHECK();
   return 0;
 }

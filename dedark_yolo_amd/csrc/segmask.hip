@@ -17,7 +17,7 @@
 // src = scale * (dst + 0.5) - 0.5 clamped at 0, i0 = (int)src, i1 = min(i0 + 1, in - 1), w1 = src - i0, and the value
 // wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d).  The file is built with -ffp-contract=off so that the index arithmetic
 // and the weights round as written, on the device and in the launcher's region bound alike; the dot product uses fmaf explicitly.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -260,10 +260,9 @@ extern "C" int dy_seg_mask_upsample(const void* proto, int64_t proto_ld, int nm,
   if (int e = check_window("dy_seg_mask_upsample", mh, mw, top, left, bottom, right, oh, ow)) return e;
   if (n_groups == 0 || max_group == 0) return 0;
   DY_CHECK(proto && det && img_off && img_ids && out, "dy_seg_mask_upsample: null pointer");
-  DY_CHECK(dtype == DY_F32 || dtype == DY_BF16 || dtype == DY_F16, "dy_seg_mask_upsample: bad dtype %d", dtype);
+  if (int e = dy_check_dtype("dy_seg_mask_upsample", dtype)) return e;
   DY_CHECK(det_chunk > 0, "dy_seg_mask_upsample: det_chunk must be positive");
-  const int es = dtype == DY_F32 ? 4 : 2;
-  DY_CHECK((proto_ld * es) % 16 == 0 && ((uintptr_t)proto) % 16 == 0, "dy_seg_mask_upsample: proto rows must be 16-byte aligned");
+  DY_CHECK(dy_aligned16(proto, proto_ld, dy_elem_size(dtype)), "dy_seg_mask_upsample: proto rows must be 16-byte aligned");
   DY_CHECK(((uintptr_t)out) % 16 == 0, "dy_seg_mask_upsample: out must be 16-byte aligned");
   Up u;
   u.proto_ld = proto_ld; u.mh = mh; u.mw = mw;
@@ -288,9 +287,7 @@ extern "C" int dy_seg_mask_upsample(const void* proto, int64_t proto_ld, int nm,
   dim3 grid(u.tiles_x * dy_cdiv(oh, th), (unsigned)gy);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("seg_mask_upsample_kernel");
-  if (dtype == DY_F32) seg_mask_upsample_kernel<float><<<grid, NT, 0, st>>>(u, (const float*)proto, det, out);
-  else if (dtype == DY_F16) seg_mask_upsample_kernel<f16_t><<<grid, NT, 0, st>>>(u, (const f16_t*)proto, det, out);
-  else seg_mask_upsample_kernel<bf16_t><<<grid, NT, 0, st>>>(u, (const bf16_t*)proto, det, out);
+  DY_DISPATCH_DTYPE("dy_seg_mask_upsample", dtype, seg_mask_upsample_kernel<T><<<grid, NT, 0, st>>>(u, (const T*)proto, det, out));
   DY_LAUNCH_CHECK();
   return 0;
 }

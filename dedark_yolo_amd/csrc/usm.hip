@@ -12,7 +12,7 @@
 // (the mirrored copies of g that reflect padding adds are the adjoint's fold-back terms except for the edge sample itself).
 // So the backward pass is the forward machinery plus a wave-uniform correction on the 13 border rows / columns; the first
 // version of this kernel evaluated per-lane adjoint weights and took 1.3 ms against 0.33 ms for the forward pass.
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 
 namespace {
@@ -360,11 +360,11 @@ extern "C" int dy_usm_fwd(const float* s4, const float* params, float* out_nchw,
                           int dtype, void* stream) {
   DY_CHECK(s4 && params && B > 0, "dy_usm_fwd: bad args");
   DY_CHECK(H > R && W > R, "dy_usm_fwd: reflect padding needs H, W > %d", R);
+  if (int e = dy_check_dtype("dy_usm_fwd", dtype)) return e;
   if (int e = ensure_taps()) return e;
   dim3 grid(dy_cdiv(W, TW), dy_cdiv(H, TH), B);
-  if (dtype == DY_F32) usm_fwd_kernel<float><<<grid, NTH, 0, (hipStream_t)stream>>>(s4, params, out_nchw, (float*)out_nhwc8, hp, B, H, W);
-  else if ((dtype) == DY_F16) usm_fwd_kernel<f16_t><<<grid, NTH, 0, (hipStream_t)stream>>>(s4, params, out_nchw, (f16_t*)out_nhwc8, hp, B, H, W);
-  else usm_fwd_kernel<bf16_t><<<grid, NTH, 0, (hipStream_t)stream>>>(s4, params, out_nchw, (bf16_t*)out_nhwc8, hp, B, H, W);
+  DY_DISPATCH_DTYPE("dy_usm_fwd", dtype,
+                    usm_fwd_kernel<T><<<grid, NTH, 0, (hipStream_t)stream>>>(s4, params, out_nchw, (T*)out_nhwc8, hp, B, H, W));
   DY_LAUNCH_CHECK();
   return 0;
 }
@@ -374,14 +374,12 @@ extern "C" int dy_usm_bwd(const float* dout_nchw, const void* dout_nhwc8, int do
   DY_CHECK(dout_nhwc8 == nullptr || dout_ld >= 3 || dout_ld == 0, "dy_usm_bwd: bad dout_ld");
   DY_CHECK((dout_nchw != nullptr) != (dout_nhwc8 != nullptr), "dy_usm_bwd: exactly one of dout_nchw / dout_nhwc8");
   DY_CHECK(hp && params && ds4 && dparams && B > 0 && H > R && W > R, "dy_usm_bwd: bad args");
+  if (int e = dy_check_dtype("dy_usm_bwd", dtype)) return e;
   if (int e = ensure_taps()) return e;
   dim3 grid(dy_cdiv(W, TW), dy_cdiv(H, TH), B);
-  if (dtype == DY_F32)
-    usm_bwd_kernel<float><<<grid, NTH, 0, (hipStream_t)stream>>>(dout_nchw, (const float*)dout_nhwc8, dout_ld, hp, params, ds4, dparams, B, H, W);
-  else if ((dtype) == DY_F16)
-    usm_bwd_kernel<f16_t><<<grid, NTH, 0, (hipStream_t)stream>>>(dout_nchw, (const f16_t*)dout_nhwc8, dout_ld, hp, params, ds4, dparams, B, H, W);
-  else
-    usm_bwd_kernel<bf16_t><<<grid, NTH, 0, (hipStream_t)stream>>>(dout_nchw, (const bf16_t*)dout_nhwc8, dout_ld, hp, params, ds4, dparams, B, H, W);
+  DY_DISPATCH_DTYPE("dy_usm_bwd", dtype,
+                    usm_bwd_kernel<T><<<grid, NTH, 0, (hipStream_t)stream>>>(dout_nchw, (const T*)dout_nhwc8, dout_ld, hp, params, ds4,
+                                                                             dparams, B, H, W));
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -10,6 +10,7 @@
  * `ld` is the pixel stride in ELEMENTS, so a channel slice of a wider concat buffer is a view with ld = total width.
  * dtype: DY_F32 (parity path, exact-f32 MFMA 32x32x2), DY_BF16 (throughput path, MFMA 32x32x16 / 16x16x32, f32 accumulate) or
  * DY_F16 (IEEE half: the same kernels on the f16 MFMA; the reference's AMP dtype, BASELINE configs[4]).
+ * Any other dtype value is an error: the entry launches nothing and returns 1 with "<entry>: bad dtype <value>".
  * Weights: f32 OIHW master (the reference state_dict layout) is packed per step into [Cout][KH][KW][Cin] ("KRSC").
  */
 #ifndef DEDARK_YOLO_H
