@@ -137,6 +137,8 @@ _SIGS = {
     "dy_loss_bwd": [C.POINTER(DetMaps), C.POINTER(vp), C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp],
     "dy_detect_decode": [C.POINTER(DetMaps), vp, vp],
     "dy_detect_decode_rows": [C.POINTER(DetMaps), vp, i32, vp],
+    "dy_detect_decode_tta": [C.POINTER(DetMaps), vp, i64, i32, i32, i32, f32, i32, f32, f32, vp],
+    "dy_tta_scale_img": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "dy_nms_candidates": [vp, i32, i32, i32, f32, i32, vp, vp, i64, vp],
     "dy_nms_sort": [vp, vp, vp, i32, i64, vp, vp, vp],
     "dy_nms_greedy": [vp, vp, vp, i32, i32, i32, i64, C.c_double, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp],

@@ -153,15 +153,26 @@ DY_HD inline float dy_box_iou_any(const float* b1, const float* b2, int xywh, in
 }
 
 // softmax over n logits -> probabilities p, returns expectation sum_i i*p_i
-DY_HD inline float dy_softmax_expect(const float* x, int n, float* p) {
+DY_HD inline float dy_softmax_expect_impl(const float* x, int n, float* p, int fma) {
   float mx = x[0];
   for (int i = 1; i < n; ++i) mx = dy_fmaxf(mx, x[i]);
   float s = 0.f;
   for (int i = 0; i < n; ++i) { p[i] = expf(x[i] - mx); s += p[i]; }
   float inv = 1.f / s, e = 0.f;
-  for (int i = 0; i < n; ++i) { p[i] *= inv; e += p[i] * (float)i; }
+  for (int i = 0; i < n; ++i) {
+    p[i] *= inv;
+    if (fma) e = fmaf(p[i], (float)i, e);
+    else e += p[i] * (float)i;
+  }
   return e;
 }
+
+DY_HD inline float dy_softmax_expect(const float* x, int n, float* p) { return dy_softmax_expect_impl(x, n, p, 0); }
+
+// The same with the multiply-add written out instead of left to contraction, for the eval decodes: a kernel in which the
+// vectoriser pairs the box sides rounds p[i] * i on its own, and dy_detect_decode and dy_detect_decode_tta must give the same bits
+// for the same map whatever the optimiser makes of the code around the decode.
+DY_HD inline float dy_softmax_expect_fma(const float* x, int n, float* p) { return dy_softmax_expect_impl(x, n, p, 1); }
 
 // DFL for one side: CE at floor(t) and floor(t)+1 (reference ultralytics/utils/loss.py:75-84), logits x[16]
 DY_HD inline float dy_dfl_side(const float* x, float t, float* wl_out, int* tl_out) {

@@ -583,11 +583,11 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Maps m, char* d0, char* d
 
 // ---- Detect eval decode ----------------------------------------------------------------------------------------------------------
 // y [B][rows][A] f32 with rows >= 4 + nc (the Pose head's buffer also holds its keypoint rows after the class rows)
+// one anchor of one image: box = (cx, cy, w, h) * stride; returns the anchor's map row (the class logits start at 4 * REG).  No
+// product feeds a sum here and dy_softmax_expect_fma writes its multiply-adds out, so the decode kernels that share this give the same
+// bits whatever the optimiser does with the code around it.
 template <typename T>
-__global__ void detect_decode_kernel(Maps m, float* __restrict__ y, int rows) {
-  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)m.B * m.A) return;
-  int b = (int)(i / m.A), a = (int)(i - (long)b * m.A);
+__device__ inline const T* detect_decode_anchor(const Maps& m, int b, int a, float box[4]) {
   int lvl, cell;
   float ax, ay;
   anchor_of(m, a, lvl, cell, ax, ay);
@@ -597,16 +597,52 @@ __global__ void detect_decode_kernel(Maps m, float* __restrict__ y, int rows) {
   for (int s = 0; s < 4; ++s) {
     float x[REG], p[REG];
     load_run<T>(r, s * REG, REG, m.ld[lvl], x);
-    d[s] = dy_softmax_expect(x, REG, p);
+    d[s] = dy_softmax_expect_fma(x, REG, p);
   }
   const float st = m.stride[lvl];
   float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
+  box[0] = (x1 + x2) / 2 * st;
+  box[1] = (y1 + y2) / 2 * st;
+  box[2] = (x2 - x1) * st;
+  box[3] = (y2 - y1) * st;
+  return r;
+}
+
+template <typename T>
+__global__ void detect_decode_kernel(Maps m, float* __restrict__ y, int rows) {
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)m.B * m.A) return;
+  int b = (int)(i / m.A), a = (int)(i - (long)b * m.A);
+  float box[4];
+  const T* r = detect_decode_anchor<T>(m, b, a, box);
   float* o = y + (long)b * rows * m.A + a;
-  o[0] = (x1 + x2) / 2 * st;
-  o[(long)m.A] = (y1 + y2) / 2 * st;
-  o[2L * m.A] = (x2 - x1) * st;
-  o[3L * m.A] = (y2 - y1) * st;
+  o[0] = box[0];
+  o[(long)m.A] = box[1];
+  o[2L * m.A] = box[2];
+  o[3L * m.A] = box[3];
   for (int c = 0; c < m.nc; ++c) o[(long)(4 + c) * m.A] = dy_sigmoid(DT<T>::ld(r + 4 * REG + c));
+}
+
+// Test-time augmentation (reference tasks.py:303-340): the decode of one pass written into its column window of the merged
+// y [B][4 + nc][A_total]: anchors [a_lo, a_hi) of the pass (_clip_augmented) go to columns col0 .. col0 + (a_hi - a_lo); box rows
+// divided by the pass's scale, then mirrored about the ORIGINAL image's width / height for a flipped pass (_descale_pred).
+template <typename T>
+__global__ void detect_decode_tta_kernel(Maps m, float* __restrict__ y, long a_total, int col0, int a_lo, int a_hi, float scale, int flip,
+                                         float img_h, float img_w) {
+  const int keep = a_hi - a_lo;
+  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)m.B * keep) return;
+  int b = (int)(i / keep), k = (int)(i - (long)b * keep);
+  float box[4];
+  const T* r = detect_decode_anchor<T>(m, b, a_lo + k, box);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) box[s] = box[s] / scale;
+  if (flip == 3) box[0] = img_w - box[0];
+  else if (flip == 2) box[1] = img_h - box[1];
+  float* o = y + (long)b * (4 + m.nc) * a_total + col0 + k;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) o[s * a_total] = box[s];
+  for (int c = 0; c < m.nc; ++c) o[(long)(4 + c) * a_total] = dy_sigmoid(DT<T>::ld(r + 4 * REG + c));
 }
 
 // uint8 pixels take 256 values: every block tabulates clean = v/255 and img = clean^gamma once (the exact libm powf of the
@@ -904,6 +940,24 @@ extern "C" int dy_detect_decode_rows(const dy_det_maps* d, float* y, int rows, v
 
 extern "C" int dy_detect_decode(const dy_det_maps* d, float* y, void* stream) {
   return dy_detect_decode_rows(d, y, d ? 4 + d->nc : 0, stream);
+}
+
+extern "C" int dy_detect_decode_tta(const dy_det_maps* d, float* y, int64_t a_total, int col0, int a_lo, int a_hi, float scale, int flip,
+                                    float img_h, float img_w, void* stream) {
+  Maps m;
+  if (int e = make_maps(d, m, "dy_detect_decode_tta")) return e;
+  DY_CHECK(y, "dy_detect_decode_tta: null output");
+  DY_CHECK(a_lo >= 0 && a_lo <= a_hi && a_hi <= m.A, "dy_detect_decode_tta: anchors [%d, %d) outside the pass's %d", a_lo, a_hi, m.A);
+  DY_CHECK(col0 >= 0 && (int64_t)col0 + (a_hi - a_lo) <= a_total, "dy_detect_decode_tta: columns [%d, %d) outside the merged %ld", col0,
+           col0 + (a_hi - a_lo), (long)a_total);
+  DY_CHECK(scale > 0.f && (flip == 0 || flip == 2 || flip == 3), "dy_detect_decode_tta: scale %g, flip %d (0 none, 2 up-down, 3 left-right)",
+           (double)scale, flip);
+  if (a_hi == a_lo) return 0;
+  int blocks = dy_cdiv((long)m.B * (a_hi - a_lo), 256);
+  DY_DISPATCH_DTYPE("dy_detect_decode_tta", d->dtype,
+                    detect_decode_tta_kernel<T><<<blocks, 256, 0, (hipStream_t)stream>>>(m, y, a_total, col0, a_lo, a_hi, scale, flip, img_h, img_w));
+  DY_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int dy_preprocess_batch(const uint8_t* img, float* img_out, float* clean_out, float dark_param, int lowlight,

@@ -19,6 +19,7 @@
 // and the weights round as written, on the device and in the launcher's region bound alike; the dot product uses fmaf explicitly.
 #include "dy_host.h"
 #include "../../include/dedark_yolo.h"
+#include "dy_bilinear.h"          // Tap, tap_of, bilerp
 
 namespace {
 
@@ -28,25 +29,6 @@ constexpr int PPT = 2;            // proto pixels a thread keeps in registers
 constexpr int RCAP = NT * PPT;    // proto pixels under one output tile, halo included
 constexpr int SEG = 16;           // output pixels per lane = one 16-byte store
 constexpr int TILE_MAX = 64;      // output tile edge: (64 / SEG) lanes per row x 64 rows = NT lanes
-
-struct Tap { int i0, i1; float w1; };
-
-__host__ __device__ inline Tap tap_of(int dst, float scale, int in) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  int i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  float l = src - (float)i0;
-  l = l < 0.f ? 0.f : (l > 1.f ? 1.f : l);
-  Tap t;
-  t.i0 = i0; t.i1 = i0 < in - 1 ? i0 + 1 : i0; t.w1 = l;
-  return t;
-}
-
-__device__ inline float bilerp(float a, float b, float c, float d, float wx1, float wy1) {
-  const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-  return wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d);
-}
 
 struct Up {
   long proto_ld; int mh, mw;

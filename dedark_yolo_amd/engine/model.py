@@ -119,13 +119,14 @@ class YOLO:
         return all_tasks()[self.task][2](get_cfg(ov))(self.model, loader)
 
     @torch.no_grad()
-    def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, **kw):
+    def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, augment=False,
+                **kw):
         """reference engine/predictor.py stream_inference + DetectionPredictor.postprocess (models/yolo/detect/predict.py:12-38)
         for an already letter-boxed batch: `source` is a uint8 [B,3,H,W] RGB tensor (or float in [0,1]); returns one `Results`
         per image with boxes scaled back to `orig_shapes[i]` (default: the network input shape).  A segment model also fills
         `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Image decoding / letter-boxing (cv2), plotting
         and the mask contours (`Masks.xy`) are outside the hot path.  A classify model returns `Results.probs` (the eval soft-max row
-        of each image; classify/predict.py:23-31) and no boxes."""
+        of each image; classify/predict.py:23-31) and no boxes.  `augment=True`: multi-scale, flipped inference (DetectionModel._predict_augment) before the NMS."""
         from ..utils import ops as uops
         from .results import Results
         from .validator import DetectionValidator
@@ -140,7 +141,7 @@ class YOLO:
             img = v.preprocess(dict(img=source))["img"]
         else:
             img = source.to(dev).float()
-        preds = self.model(img)
+        preds = self.model(img, augment=bool(augment))        # engine/predictor.py:167 (detect models only; the others warn)
         if self.task == "classify":
             H, W = img.shape[2:]
             out = [Results(tuple(orig_shapes[i]) if orig_shapes is not None else (H, W), names=self.model.names, probs=p)

@@ -154,7 +154,8 @@ class DetectionValidator:
         self.init_metrics(model)
         for batch in loader:
             batch = self.preprocess(dict(batch))
-            preds = model(batch["img"])
+            # engine/validator.py:99,170: augmented inference only outside the trainer's own validation
+            preds = model(batch["img"], augment=bool(getattr(self.args, "augment", False)) and not self.training)
             preds = self.postprocess(preds)
             self.update_metrics(preds, batch)
         stats = self.get_stats()
@@ -302,7 +303,7 @@ class ClassificationValidator:
         self.init_metrics(model)
         for batch in loader:
             batch = self.preprocess(dict(batch))
-            self.update_metrics(model(batch["img"]), batch)
+            self.update_metrics(model(batch["img"], augment=bool(getattr(self.args, "augment", False)) and not self.training), batch)
         stats = self.get_stats()
         model.train(was_training)
         return {k: float(v) for k, v in stats.items()}

@@ -959,7 +959,21 @@ class Detect(DyModule):
             tape.push(subs)
         if self.training:
             return maps
+        win = self.__dict__.get("_tta_window")
+        if win is not None:                              # a pass of DetectionModel._predict_augment: no plain decode as well
+            return (self._decode_into(maps, **win), *maps)
         return (self._decode(maps), *maps)
+
+    def _decode_into(self, maps, y, col0, a_lo, a_hi, scale, flip, img_h, img_w):
+        """The eval decode of one augmented pass written into columns [col0, col0 + a_hi - a_lo) of the merged y [B, 4 + nc, A_total]
+        f32, de-scaled, de-flipped and clipped (dy_detect_decode_tta; reference tasks.py:320-340)."""
+        if not (y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 3 and y.shape[0] == maps[0].shape[0]
+                and y.shape[1] == 4 + self.nc and y.device == maps[0].device):
+            raise ValueError(f"Detect._decode_into: y {tuple(y.shape)} {y.dtype} is not the merged [B, {4 + self.nc}, A] f32 buffer")
+        m = ops.det_maps(maps, self.strides_as_floats(), self.nc)
+        call("dy_detect_decode_tta", C.byref(m), ptr(y), y.shape[2], col0, a_lo, a_hi, float(scale), int(flip or 0), float(img_h),
+             float(img_w), stream())
+        return y
 
     def _decode(self, maps):
         """The eval output y [B, 4 + nc, A] f32 of the level maps (dy_detect_decode)."""

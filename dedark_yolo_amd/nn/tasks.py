@@ -7,6 +7,7 @@ import contextlib
 import math
 import os
 import re
+import warnings
 from copy import deepcopy
 from pathlib import Path
 
@@ -355,6 +356,38 @@ def initialize_weights(model):
             m.momentum = 0.03
 
 
+# Test-time augmentation of DetectionModel._predict_augment (reference tasks.py:303-340): the passes' scales and flips (:306-307;
+# 2 = up-down, 3 = left-right) and `e`, the number of levels _clip_augmented cuts off the first and the last pass (:335).
+TTA = dict(scales=(1, 0.83, 0.67), flips=(None, 3, None), e=1)
+
+
+def tta_plan(H, W, strides, nl):
+    """Host-side geometry of the augmented passes for an H x W input: (passes, A_total) with one
+    (scale, flip, hs, ws, Hp, Wp, A_i, a_lo, a_hi, col0) per pass -- the resized size (hs, ws) and the padded size (Hp, Wp) as
+    scale_img computes them (torch_utils.py:270-279: Python int() and math.ceil on doubles; scale 1 keeps the image), the pass's
+    anchor count A_i, the anchors [a_lo, a_hi) that _clip_augmented keeps (tasks.py:331-340, its integer formula) and the column
+    col0 of the merged output where they start."""
+    strides = [int(s) for s in strides]
+    if len(strides) != nl:
+        raise ValueError(f"tta_plan: {len(strides)} strides for {nl} levels")
+    gs = max(strides)
+    g = sum(4 ** k for k in range(nl))
+    e = TTA["e"]
+    n = len(TTA["scales"])
+    passes, col0 = [], 0
+    for i, (s, f) in enumerate(zip(TTA["scales"], TTA["flips"])):
+        hs, ws, Hp, Wp = ops.scale_img_sizes(H, W, s, gs)
+        A = sum(math.ceil(Hp / st) * math.ceil(Wp / st) for st in strides)
+        a_lo, a_hi = 0, A
+        if i == 0:
+            a_hi = A - (A // g) * sum(4 ** k for k in range(e))
+        if i == n - 1:
+            a_lo = (A // g) * sum(4 ** (nl - 1 - k) for k in range(e))
+        passes.append((s, f, hs, ws, Hp, Wp, A, a_lo, a_hi, col0))
+        col0 += a_hi - a_lo
+    return passes, col0
+
+
 class BaseModel(nn.Module):
     """reference tasks.py:29-253."""
 
@@ -369,6 +402,16 @@ class BaseModel(nn.Module):
         return self.predict(x, *args, **kwargs)
 
     def predict(self, x, profile=False, visualize=False, augment=False):
+        """reference tasks.py:56-72; training mode never augments."""
+        if augment and isinstance(x, dict):
+            raise ValueError("predict(augment=True) takes an image tensor, not a batch dict")
+        if augment and not self.training:
+            return self._predict_augment(x)
+        return self._predict_once(x)
+
+    def _predict_augment(self, x):
+        """reference tasks.py:121-127 (and :358-363, :381-386 for segment and pose): only the detection model augments."""
+        warnings.warn(f"{type(self).__name__} has not supported augment inference yet! Now using single-scale inference instead.")
         return self._predict_once(x)
 
     def _predict_once(self, x, profile=False, visualize=False):
@@ -564,6 +607,29 @@ class DetectionModel(BaseModel):
                 s.append(prev if f == -1 else s[f])
         raise RuntimeError("no Detect layer")
 
+    def _predict_augment(self, x):
+        """Multi-scale, flipped inference (reference tasks.py:303-340): three eval passes (TTA), each on an image one kernel prepares
+        (dy_tta_scale_img; the first pass reads x itself) and each decoded straight into its column window of the merged
+        y [B, 4 + nc, A_total], de-scaled, de-flipped and clipped (dy_detect_decode_tta).  Returns (y, None).  The boxes of a flipped
+        pass are mirrored about the ORIGINAL width, also where the pass was padded, as in the reference."""
+        head = self.model[-1]
+        if not (torch.is_tensor(x) and x.dim() == 4):
+            raise ValueError("predict(augment=True) takes an image tensor [B, C, H, W]")
+        self._check_imgsz(x)
+        x = x.float().contiguous()
+        H, W = x.shape[2:]
+        strides = head.strides_as_floats()
+        passes, a_total = tta_plan(H, W, strides, head.nl)
+        y = torch.empty((x.shape[0], 4 + head.nc, a_total), dtype=torch.float32, device=x.device)
+        try:
+            for s, f, _, _, _, _, _, a_lo, a_hi, col0 in passes:
+                xi = x if (s == 1.0 and not f) else ops.tta_scale_img(x, s, int(max(strides)), f)
+                head.__dict__["_tta_window"] = dict(y=y, col0=col0, a_lo=a_lo, a_hi=a_hi, scale=s, flip=f, img_h=H, img_w=W)
+                self._predict_once(xi)
+        finally:
+            head.__dict__.pop("_tta_window", None)
+        return y, None
+
     def init_criterion(self):
         from ..utils.loss import RcoveryDetectionLoss
         return RcoveryDetectionLoss(self)
@@ -577,6 +643,8 @@ class SegmentationModel(DetectionModel):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
         if not isinstance(self.model[-1], Segment):
             raise ValueError("SegmentationModel: the yaml's last layer is not a Segment head")
+
+    _predict_augment = BaseModel._predict_augment          # reference tasks.py:358-363: warns, single-scale
 
     def init_criterion(self):
         from ..utils.loss import v8SegmentationLoss
@@ -596,6 +664,8 @@ class PoseModel(DetectionModel):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
         if not isinstance(self.model[-1], Pose):
             raise ValueError("PoseModel: the yaml's last layer is not a Pose head")
+
+    _predict_augment = BaseModel._predict_augment          # reference tasks.py:381-386: warns, single-scale
 
     def init_criterion(self):
         from ..utils.loss import v8PoseLoss

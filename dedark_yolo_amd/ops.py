@@ -5,6 +5,7 @@ Tensor convention between modules: logical shape [B, C, H, W] (the reference's m
 legal input/output ("view" = pointer + pixel stride), which is how C2f / SPPF / Detect concats cost nothing.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -880,6 +881,27 @@ def det_maps(maps, strides, nc):
         t = maps[3]
         m.map3, m.map_ld3, m.h3, m.w3, m.stride3 = t.data_ptr(), ld_of(t), t.shape[2], t.shape[3], float(strides[3])
     return m
+
+
+def scale_img_sizes(H, W, ratio, gs):
+    """(hs, ws, Hp, Wp) of scale_img (reference torch_utils.py:270-279): the resized size int(H * ratio), int(W * ratio) and the
+    padded one ceil(H * ratio / gs) * gs, ceil(W * ratio / gs) * gs, in Python doubles as the reference computes them; ratio 1.0 keeps
+    the image."""
+    if ratio == 1.0:
+        return H, W, H, W
+    return (int(H * ratio), int(W * ratio), *(math.ceil(v * ratio / gs) * gs for v in (H, W)))
+
+
+def tta_scale_img(x, ratio, gs, flip=None):
+    """scale_img(x.flip(flip), ratio, gs=gs) of one augmented pass in one kernel (dy_tta_scale_img) for x f32 NCHW on the GPU: flip
+    None / 0, 2 (up-down) or 3 (left-right); bilinear resize by `ratio`, right / bottom padding with 0.447 to the multiple of gs."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("tta_scale_img: expected a contiguous f32 NCHW tensor on the GPU")
+    B, Cc, H, W = x.shape
+    hs, ws, Hp, Wp = scale_img_sizes(H, W, ratio, gs)
+    out = torch.empty((B, Cc, Hp, Wp), dtype=torch.float32, device=x.device)
+    call("dy_tta_scale_img", ptr(x), B, Cc, H, W, hs, ws, Hp, Wp, int(flip or 0), ptr(out), stream())
+    return out
 
 
 def pose_desc(kpts, strides, kpt_shape):

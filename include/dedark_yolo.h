@@ -319,6 +319,22 @@ int dy_loss_bwd(const dy_det_maps* m, void* const* dmap, const int64_t* dmap_ld,
 int dy_detect_decode(const dy_det_maps* m, float* y, void* stream);
 /* the same into y[B, rows, A] f32, rows >= 4+nc (rows past 4+nc are not written: the Pose head's keypoint rows, dy_pose_kpt_decode) */
 int dy_detect_decode_rows(const dy_det_maps* m, float* y, int rows, void* stream);
+/* ---- test-time augmentation for detect (U/nn/tasks.py:303-340 DetectionModel._predict_augment; csrc/tta.hip, csrc/loss.hip) ----------
+ * dy_tta_scale_img: the input of one augmented pass, scale_img(x.flip(flip), ratio, gs) (tasks.py:310, U/utils/torch_utils.py:270-279), in
+ * one pass over the output: x f32 NCHW [B][C][H][W] -> out f32 NCHW [B][C][Hp][Wp].  flip 0 none, 2 up-down, 3 left-right (folded into
+ * the source index).  Pixels inside (hs, ws) are the bilinear resize of the flipped image with the arithmetic documented at
+ * dy_seg_mask_upsample (scale = in / out in f32, src = scale * (dst + 0.5) - 0.5 clamped at 0, upper tap clamped to the last row /
+ * column, wy0 * (wx0 * a + wx1 * b) + wy1 * (wx0 * c + wx1 * d)); the others (right, bottom) are 0.447.  The caller computes
+ * hs = int(H * ratio), ws = int(W * ratio), Hp = ceil(H * ratio / gs) * gs, Wp likewise (in doubles, as the reference does) and passes
+ * them in.  (hs, ws) == (H, W): the mirrored pixels themselves, bit for bit.  out 16-byte aligned, not x.  No atomics. */
+int dy_tta_scale_img(const float* x, int B, int C, int H, int W, int hs, int ws, int Hp, int Wp, int flip, float* out, void* stream);
+/* dy_detect_decode of one augmented pass written into its column window of the merged y [B][4+nc][a_total] f32, with _descale_pred
+ * (tasks.py:320-329) and _clip_augmented (:331-340) applied: anchor a in [a_lo, a_hi) of the pass goes to column col0 + a - a_lo; box
+ * rows = (decoded * stride) / scale in f32 (a division, as the reference's `p[:, :4] /= scale`), then row 0 = img_w - x for flip 3 or
+ * row 1 = img_h - y for flip 2, img_h / img_w being those of the ORIGINAL image (not of the padded pass); class rows = sigmoid,
+ * unchanged.  Anchors outside [a_lo, a_hi) are not computed; columns outside the window are not written. */
+int dy_detect_decode_tta(const dy_det_maps* m, float* y, int64_t a_total, int col0, int a_lo, int a_hi, float scale, int flip,
+                         float img_h, float img_w, void* stream);
 /* ------------------------------------------------------------------------------------------------ NMS
  * non_max_suppression (U/utils/ops.py:144-278; called from U/models/yolo/detect/val.py:62-70) for the whole batch.
  * pred [B, 4+nc, A] f32 = Detect's eval output (xywh px + class scores).  Three stages:
