@@ -49,6 +49,11 @@ class AugSample(C.Structure):
                 ("lut", (C.c_uint8 * 256) * 3)]
 
 
+class AugMixSample(C.Structure):
+    """dy_aug_mix_sample (include/dedark_yolo.h), 2088 bytes: two dy_aug_sample of 1032 bytes, r, r1 = 1.0 - r, mix"""
+    _fields_ = [("a", AugSample), ("b", AugSample), ("r", C.c_double), ("r1", C.c_double), ("mix", i32)]
+
+
 class SegDesc(C.Structure):
     """dy_seg_desc (include/dedark_yolo.h)"""
     _fields_ = [("mc", vp), ("mc_ld", i64), ("proto", vp), ("proto_ld", i64), ("B", i32), ("A", i32), ("nm", i32), ("mh", i32),
@@ -130,6 +135,7 @@ _SIGS = {
     "dy_aug_resize_u8": [vp, i32, i32, i64, vp, i32, i32, i64, vp],
     "dy_aug_letterbox": [vp, i32, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp],
     "dy_aug_mosaic_warp": [vp, i32, i32, i32, vp, vp],
+    "dy_aug_mosaic_warp_mix": [vp, i32, i32, i32, vp, vp],
     "dy_dark_channel_prior": [vp, i32, i32, i32, vp, vp, vp],
     "dy_dfl_loss": [vp, vp, i64, vp, vp, vp],
     "dy_loss_fwd": [C.POINTER(DetMaps), vp, vp, vp, vp, vp, vp, vp],

@@ -6,7 +6,7 @@
 // LetterBox :559-591 (cv2.resize + cv2.copyMakeBorder); trainer: DarkChannel / AtmLight / DarkIcA (models/yolo/detect/train.py:42-68,
 // a Python loop per image behind a device->host copy).
 //
-// Here: dy_aug_mosaic_warp renders a whole batch in ONE launch -- a thread per output pixel walks flips -> warpAffine's fixed-point
+// Here: dy_aug_mosaic_warp (dy_aug_mosaic_warp_mix with MixUp: a second warped image blended in before the HSV gains) renders a whole batch in ONE launch -- a thread per output pixel walks flips -> warpAffine's fixed-point
 // inverse map (AB_BITS 10, INTER_BITS 5, 15-bit bilinear weights) -> the four mosaic placement rectangles (the 2s x 2s canvas is
 // never materialised: each tap is looked up in the source image that owns that canvas pixel, else grey 114) -> cv2's 8-bit BGR->HSV,
 // the three lookup tables, HSV->BGR -> planar RGB.  All arithmetic is integer / explicitly rounded f32, bit-identical to
@@ -123,20 +123,9 @@ __device__ inline void canvas_px(const dy_aug_sample& a, int cx, int cy, int* bg
   }
 }
 
-__global__ __launch_bounds__(256) void mosaic_warp_kernel(const dy_aug_sample* __restrict__ samples, int oh, int ow, uint8_t* __restrict__ out) {
-  __shared__ int sdiv[256], hdiv[256];
-  __shared__ uint8_t lut[3][256];
-  const dy_aug_sample& a = samples[blockIdx.z];
-  {
-    const int i = threadIdx.x;
-    sdiv[i] = i ? rint_i((double)(255 << 12) / (1.0 * i)) : 0;
-    hdiv[i] = i ? rint_i((double)(180 << 12) / (6.0 * i)) : 0;
-    lut[0][i] = a.lut[0][i]; lut[1][i] = a.lut[1][i]; lut[2][i] = a.lut[2][i];
-  }
-  __syncthreads();
-  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (ox >= ow || oy >= oh) return;
-  const int wx = a.fliplr ? ow - 1 - ox : ox, wy = a.flipud ? oh - 1 - oy : oy;        // np.flipud then np.fliplr of the warped image
+// warped BGR of descriptor `a` at coordinate (wx, wy) of the warped image: warpAffine's fixed-point inverse map, four canvas taps,
+// 15-bit bilinear weights.  Shared by both render kernels, so an un-mixed sample has the same bits through either entry point.
+__device__ inline void warp_px(const dy_aug_sample& a, int wx, int wy, int* bgr) {
   // inverse map in fixed point: X = (round(m0 x 1024) + round((m1 y + m2) 1024) + 16) >> 5
   const int X = (rint_i(__dmul_rn(__dmul_rn(a.minv[0], (double)wx), 1024.0)) +
                  rint_i(__dmul_rn(__dadd_rn(__dmul_rn(a.minv[1], (double)wy), a.minv[2]), 1024.0)) + 16) >> 5;
@@ -150,12 +139,24 @@ __global__ __launch_bounds__(256) void mosaic_warp_kernel(const dy_aug_sample* _
   canvas_px(a, sx + 1, sy, p01);
   canvas_px(a, sx, sy + 1, p10);
   canvas_px(a, sx + 1, sy + 1, p11);
-  int bgr[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int v = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + (1 << 14)) >> 15;
     bgr[c] = min(max(v, 0), 255);
   }
+}
+
+// the division tables of bgr2hsv and the three tables of the block's sample, one entry per thread (256 threads)
+__device__ inline void load_hsv_tables(const dy_aug_sample& a, int* sdiv, int* hdiv, uint8_t (*lut)[256]) {
+  const int i = threadIdx.x;
+  sdiv[i] = i ? rint_i((double)(255 << 12) / (1.0 * i)) : 0;
+  hdiv[i] = i ? rint_i((double)(180 << 12) / (6.0 * i)) : 0;
+  lut[0][i] = a.lut[0][i]; lut[1][i] = a.lut[1][i]; lut[2][i] = a.lut[2][i];
+}
+
+// RandomHSV (when the sample has gains) and the planar RGB store of Format
+__device__ inline void hsv_store(const dy_aug_sample& a, int* bgr, const int* sdiv, const int* hdiv, const uint8_t (*lut)[256], int oh, int ow,
+                                 int ox, int oy, uint8_t* __restrict__ out) {
   if (a.hsv) {
     int h, s, v;
     bgr2hsv(bgr[0], bgr[1], bgr[2], sdiv, hdiv, h, s, v);
@@ -166,6 +167,46 @@ __global__ __launch_bounds__(256) void mosaic_warp_kernel(const dy_aug_sample* _
   o[0] = (uint8_t)bgr[2];
   o[plane] = (uint8_t)bgr[1];
   o[2 * plane] = (uint8_t)bgr[0];
+}
+
+__global__ __launch_bounds__(256) void mosaic_warp_kernel(const dy_aug_sample* __restrict__ samples, int oh, int ow, uint8_t* __restrict__ out) {
+  __shared__ int sdiv[256], hdiv[256];
+  __shared__ uint8_t lut[3][256];
+  const dy_aug_sample& a = samples[blockIdx.z];
+  load_hsv_tables(a, sdiv, hdiv, lut);
+  __syncthreads();
+  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (ox >= ow || oy >= oh) return;
+  const int wx = a.fliplr ? ow - 1 - ox : ox, wy = a.flipud ? oh - 1 - oy : oy;        // np.flipud then np.fliplr of the warped image
+  int bgr[3];
+  warp_px(a, wx, wy, bgr);
+  hsv_store(a, bgr, sdiv, hdiv, lut, oh, ow, ox, oy, out);
+}
+
+// MixUp (augment.py:272-288) in the same launch shape: the partner `b` is warped at the same coordinate of the warped image and blended
+// as numpy does `(img1 * r + img2 * (1 - r)).astype(np.uint8)`: two float64 products, one float64 sum (each rounded once: the file is
+// built without contraction), truncation.  HSV gains and flips are the primary's and act on the blend.  `mix` is uniform per block.
+__global__ __launch_bounds__(256) void mosaic_warp_mix_kernel(const dy_aug_mix_sample* __restrict__ samples, int oh, int ow,
+                                                              uint8_t* __restrict__ out) {
+  __shared__ int sdiv[256], hdiv[256];
+  __shared__ uint8_t lut[3][256];
+  const dy_aug_mix_sample& m = samples[blockIdx.z];
+  const dy_aug_sample& a = m.a;
+  load_hsv_tables(a, sdiv, hdiv, lut);
+  __syncthreads();
+  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (ox >= ow || oy >= oh) return;
+  const int wx = a.fliplr ? ow - 1 - ox : ox, wy = a.flipud ? oh - 1 - oy : oy;
+  int bgr[3];
+  warp_px(a, wx, wy, bgr);
+  if (m.mix) {
+    int pb[3];
+    warp_px(m.b, wx, wy, pb);
+    const double r = m.r, r1 = m.r1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bgr[c] = (int)(uint8_t)(__dadd_rn(__dmul_rn((double)bgr[c], r), __dmul_rn((double)pb[c], r1)));
+  }
+  hsv_store(a, bgr, sdiv, hdiv, lut, oh, ow, ox, oy, out);
 }
 
 // ---- dark-channel prior of the trainer (models/yolo/detect/train.py:42-68), deterministic -----------------------------------------------
@@ -286,6 +327,17 @@ extern "C" int dy_aug_mosaic_warp(const dy_aug_sample* samples, int B, int out_h
   DY_CHECK(B <= 65535, "dy_aug_mosaic_warp: at most 65535 samples per launch");
   if (B == 0) return 0;
   mosaic_warp_kernel<<<dim3(dy_cdiv(out_w, 64), dy_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream>>>(samples, out_h, out_w, out);
+  DY_LAUNCH_CHECK();
+  return 0;
+}
+
+static_assert(sizeof(dy_aug_sample) == 1032 && sizeof(dy_aug_mix_sample) == 2088, "descriptor layout: _C.AugSample / _C.AugMixSample");
+
+extern "C" int dy_aug_mosaic_warp_mix(const dy_aug_mix_sample* samples, int B, int out_h, int out_w, uint8_t* out, void* stream) {
+  DY_CHECK(B >= 0 && out_h > 0 && out_w > 0 && (B == 0 || (samples && out)), "dy_aug_mosaic_warp_mix: bad arguments");
+  DY_CHECK(B <= 65535, "dy_aug_mosaic_warp_mix: at most 65535 samples per launch");
+  if (B == 0) return 0;
+  mosaic_warp_mix_kernel<<<dim3(dy_cdiv(out_w, 64), dy_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream>>>(samples, out_h, out_w, out);
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,7 @@
 
 Reference (host, per sample, cv2 + numpy in dataloader workers): ultralytics/data/base.py:142-169 load_image (resize so that the long
 side is imgsz), ultralytics/data/augment.py `v8_transforms` :753-783 = Mosaic :118-216 -> CopyPaste(p=0) -> RandomPerspective :292-478 ->
-MixUp(p=0) -> Albumentations (package absent: bookkeeping only) -> RandomHSV :480-499 -> RandomFlip x2 :502-537, then Format :697-751 and
+MixUp :272-288 -> Albumentations (package absent: bookkeeping only) -> RandomHSV :480-499 -> RandomFlip x2 :502-537, then Format :697-751 and
 YOLODataset.collate_fn (dataset.py:172-188).  Validation: LetterBox(scaleup=False) :540-603 + Format.
 
 Here the split is:
@@ -12,7 +12,8 @@ Here the split is:
   * `train_labels` / `val_labels` move the boxes through the same float32 steps as the reference's Instances bookkeeping (a few dozen
     numbers per image: host numpy, like the reference);
   * the pixels never exist on the host in augmented form: `DeviceAugmenter` keeps the decoded uint8 images in HBM (or uploads them) and
-    ONE kernel per batch (dy_aug_mosaic_warp) samples mosaic canvas -> affine warp (cv2.warpAffine's fixed-point bilinear) -> HSV
+    ONE kernel per batch (dy_aug_mosaic_warp; dy_aug_mosaic_warp_mix when hyp.mixup > 0: the partner's warped image is blended in before
+    the HSV gains) samples mosaic canvas -> affine warp (cv2.warpAffine's fixed-point bilinear) -> HSV
     gains (cv2's 8-bit BGR<->HSV + the three lookup tables) -> flips -> CHW RGB uint8, i.e. batch['img'] of the reference's batch dict.
     The 2s x 2s mosaic canvas is never materialised: every bilinear tap is resolved through the four placement rectangles.
 There is no CPU pixel path: without the library the augmenter raises.
@@ -36,21 +37,14 @@ def AugmentHyp(**kw):
 
 
 def _check_hyp(hyp):
-    if hyp.mixup or hyp.copy_paste or hyp.perspective:
-        raise NotImplementedError("mixup / copy_paste / perspective are 0 in the reference's configuration and are not implemented")
+    if hyp.copy_paste or hyp.perspective:
+        raise NotImplementedError("copy_paste / perspective are 0 in the reference's configuration and are not implemented")
 
 
-def plan_train_sample(index, shapes, buffer, imgsz, hyp, rnd=_random, nprnd=np.random):
-    """Random draws of ONE training sample, in the call order of the reference's transform chain:
-      Mosaic.__call__ (augment.py:86-104): uniform(0, 1) against p; 3 partners with random.choices(buffer, k=3) (:145-150);
-        centre yc, xc = int(uniform(-x, 2 s + x)) for x in border = (-s // 2, -s // 2) (:161);
-      RandomPerspective.affine_transform (:317-339): 2 perspective, rotation, scale, 2 shear, 2 translation draws;
-      MixUp.__call__: uniform(0, 1) against p = 0 (still one draw);
-      RandomHSV (:490): numpy.random.uniform(-1, 1, 3) when any gain is non-zero;
-      RandomFlip vertical (:527): random.random(); RandomFlip horizontal (:530): random.random().
-    `shapes[i]` = (h, w) of dataset image i at its load_image size.  Returns a SimpleNamespace plan."""
-    _check_hyp(hyp)
-    s = int(imgsz)
+def _plan_geometry(index, shapes, buffer, s, hyp, rnd):
+    """The draws of the reference's `pre_transform` = [Mosaic, CopyPaste(p=0), RandomPerspective] for dataset image `index`: mosaic coin,
+    three partners, centre (or the LetterBox geometry), eight affine draws.  The primary of a sample and the partner of a MixUp both go
+    through it (BaseMixTransform.__call__ :97-101 applies MixUp's pre_transform to the partner)."""
     p = SimpleNamespace(index=int(index), imgsz=s)
     p.mosaic = not (rnd.uniform(0, 1) > hyp.mosaic)
     if p.mosaic:
@@ -75,7 +69,31 @@ def plan_train_sample(index, shapes, buffer, imgsz, hyp, rnd=_random, nprnd=np.r
              rnd.uniform(-hyp.shear, hyp.shear), rnd.uniform(-hyp.shear, hyp.shear),
              rnd.uniform(0.5 - hyp.translate, 0.5 + hyp.translate), rnd.uniform(0.5 - hyp.translate, 0.5 + hyp.translate)]
     p.M, p.scale, p.size = affine_matrix(draws, p.canvas_hw, p.border)
-    rnd.uniform(0, 1)                                          # MixUp's own coin (p = 0: never taken)
+    return p
+
+
+def plan_train_sample(index, shapes, buffer, imgsz, hyp, rnd=_random, nprnd=np.random):
+    """Random draws of ONE training sample, in the call order of the reference's transform chain:
+      Mosaic.__call__ (augment.py:86-104): uniform(0, 1) against p; 3 partners with random.choices(buffer, k=3) (:145-150);
+        centre yc, xc = int(uniform(-x, 2 s + x)) for x in border = (-s // 2, -s // 2) (:161);
+      RandomPerspective.affine_transform (:317-339): 2 perspective, rotation, scale, 2 shear, 2 translation draws;
+      MixUp.__call__ (:86-107, 272-288): uniform(0, 1) against hyp.mixup (always one draw); only when taken: the partner image
+        random.randint(0, len(dataset) - 1), the partner's own Mosaic / RandomPerspective draws as above (it may fall onto the
+        letterbox path when mosaic < 1), then r = numpy.random.beta(32, 32);
+      RandomHSV (:490): numpy.random.uniform(-1, 1, 3) when any gain is non-zero;
+      RandomFlip vertical (:527): random.random(); RandomFlip horizontal (:530): random.random().
+    `shapes[i]` = (h, w) of dataset image i at its load_image size: the non-mosaic (letterbox) path -- the primary's or a MixUp
+    partner's when hyp.mosaic < 1, every sample after close_mosaic -- needs images at that size and raises NotImplementedError otherwise.
+    Returns a SimpleNamespace plan; `plan.mix` is the partner's plan (sources, rects, canvas_hw, M, scale, size, border / letterbox)
+    and `plan.mix_r` the blend ratio (Python float) when MixUp was taken, else plan.mix is None."""
+    _check_hyp(hyp)
+    s = int(imgsz)
+    p = _plan_geometry(index, shapes, buffer, s, hyp, rnd)
+    p.mix, p.mix_r = None, None
+    taken = not (rnd.uniform(0, 1) > hyp.mixup)               # MixUp's own coin (drawn whatever p is)
+    if taken and hyp.mixup > 0:                               # (p = 0: never, also not on a draw of exactly 0.0 -- the un-mixed kernel renders)
+        p.mix = _plan_geometry(rnd.randint(0, len(shapes) - 1), shapes, buffer, s, hyp, rnd)
+        p.mix_r = float(nprnd.beta(32.0, 32.0))
     p.hsv_gains = None
     if hyp.hsv_h or hyp.hsv_s or hyp.hsv_v:
         p.hsv_gains = nprnd.uniform(-1, 1, 3) * [hyp.hsv_h, hyp.hsv_s, hyp.hsv_v] + 1
@@ -267,29 +285,11 @@ def check_flip_idx(hyp, flip_idx, n_kpt):
     return hyp, (flip_idx or None)
 
 
-def train_labels(plan, labels, shapes, segments=None, keypoints=None, flip_idx=None):
-    """The boxes of one planned sample through the reference's bookkeeping: per source xywhn -> xyxy pixels + mosaic offset
-    (Mosaic._update_labels :262-268), concatenation, clip to the canvas and zero-area removal (_cat_labels :270-288), affine + clip
-    + box_candidates against the scaled originals (RandomPerspective.__call__ :432-468), xywh-normalised (Albumentations' bookkeeping
-    :681-692), flips on normalised centres (RandomFlip :521-534), Format's denormalise / normalise round trip (:719-733).
-    labels[i] = dict(cls [n,1] float32, bboxes [n,4] normalised xywh float32).  Returns (cls [m,1], bboxes [m,4]) float32.
-
-    `segments[i]` (float32 [n_i, 1000, 2], normalised, resample_segments of image i's polygons) or `keypoints[i]` (float32 [n_i, K, 3],
-    normalised x, y + visibility) move through the same steps (Instances.denormalize / add_padding / clip :229-329,
-    RandomPerspective.apply_segments / apply_keypoints :375-421, Instances.flipud / fliplr, `flip_idx` on a horizontal flip :533-534) and a
-    third value is returned: the int32 [m, 1000, 2] pixel polygons exactly as polygon2mask hands them to cv2.fillPoly
-    (data/utils.py:146-147, astype(np.int32) of Format's denormalised segments), or the normalised keypoints [m, K, 3] of
-    Format(return_keypoint=True).  Rows are in LABEL order; the area order of Format._format_segments is applied on the device.
-    Reference quirks reproduced (the g20 fixtures decide):
-      * every Instances construction resamples non-empty segments again (_reresample): Instances.concatenate in Mosaic._cat_labels,
-        RandomPerspective's new_instances and its new_instances[i] -- three times on the mosaic path, twice on the letterbox path;
-      * with segments the boxes become segment2box of the transformed polygons (zeros when no inside point has a non-zero x) and
-        box_candidates uses area_thr 0.01 instead of 0.10 (:464-466);
-      * keypoints outside [0, w] x [0, h] after the affine map get visibility 0 and are then clipped like the rest (:419-420, :459);
-      * Albumentations' normalisation divides segments / keypoints by w, h while the boxes are multiplied by 1 / w, 1 / h."""
+def _stage_labels(plan, labels, shapes, segments, keypoints):
+    """train_labels up to and including box_candidates for ONE side of a sample (the primary, or the partner of a MixUp: a plan's
+    geometry part): (cls [m, 1], pixel xyxy boxes [m, 4], segments [m, 1000, 2] or None, keypoints [m, K, 3] or None) as
+    RandomPerspective.__call__ leaves them (:464-468)"""
     seg_on, kp_on = segments is not None, keypoints is not None
-    if seg_on and kp_on:
-        raise ValueError("Can not use both segments and keypoints.")
     cls, boxes, segs, kps = [], [], [], []
     for src, rect in zip(plan.sources, plan.rects):
         h, w = shapes[src]
@@ -358,6 +358,45 @@ def train_labels(plan, labels, shapes, segments=None, keypoints=None, flip_idx=N
         sg = _reresample(sg[keep])                                    # new_instances[i]
     if kp_on:
         kp = kp[keep]
+    return c, nb, sg, kp
+
+
+def train_labels(plan, labels, shapes, segments=None, keypoints=None, flip_idx=None):
+    """The boxes of one planned sample through the reference's bookkeeping: per source xywhn -> xyxy pixels + mosaic offset
+    (Mosaic._update_labels :262-268), concatenation, clip to the canvas and zero-area removal (_cat_labels :270-288), affine + clip
+    + box_candidates against the scaled originals (RandomPerspective.__call__ :432-468), xywh-normalised (Albumentations' bookkeeping
+    :681-692), flips on normalised centres (RandomFlip :521-534), Format's denormalise / normalise round trip (:719-733).
+    labels[i] = dict(cls [n,1] float32, bboxes [n,4] normalised xywh float32).  Returns (cls [m,1], bboxes [m,4]) float32.
+
+    `segments[i]` (float32 [n_i, 1000, 2], normalised, resample_segments of image i's polygons) or `keypoints[i]` (float32 [n_i, K, 3],
+    normalised x, y + visibility) move through the same steps (Instances.denormalize / add_padding / clip :229-329,
+    RandomPerspective.apply_segments / apply_keypoints :375-421, Instances.flipud / fliplr, `flip_idx` on a horizontal flip :533-534) and a
+    third value is returned: the int32 [m, 1000, 2] pixel polygons exactly as polygon2mask hands them to cv2.fillPoly
+    (data/utils.py:146-147, astype(np.int32) of Format's denormalised segments), or the normalised keypoints [m, K, 3] of
+    Format(return_keypoint=True).  Rows are in LABEL order; the area order of Format._format_segments is applied on the device.
+    Reference quirks reproduced (the g20 fixtures decide):
+      * every Instances construction resamples non-empty segments again (_reresample): Instances.concatenate in Mosaic._cat_labels,
+        RandomPerspective's new_instances and its new_instances[i] -- three times on the mosaic path, twice on the letterbox path;
+      * with segments the boxes become segment2box of the transformed polygons (zeros when no inside point has a non-zero x) and
+        box_candidates uses area_thr 0.01 instead of 0.10 (:464-466);
+      * keypoints outside [0, w] x [0, h] after the affine map get visibility 0 and are then clipped like the rest (:419-420, :459);
+      * a MixUp (plan.mix set) concatenates the partner's rows after the primary's at this point -- pixel xyxy boxes already filtered by
+        box_candidates on each side, Instances.concatenate (:286): one more re-resampling of the segments; normalisation, flips
+        (flip_idx on all rows) and Format then see the merged set, so the polygons reach polygon2mask in primary-then-partner order
+        and the area ranking is over the merged set;
+      * Albumentations' normalisation divides segments / keypoints by w, h while the boxes are multiplied by 1 / w, 1 / h."""
+    seg_on, kp_on = segments is not None, keypoints is not None
+    if seg_on and kp_on:
+        raise ValueError("Can not use both segments and keypoints.")
+    c, nb, sg, kp = _stage_labels(plan, labels, shapes, segments, keypoints)
+    if getattr(plan, "mix", None) is not None:                # MixUp._mix_transform (:286-287)
+        c2, nb2, sg2, kp2 = _stage_labels(plan.mix, labels, shapes, segments, keypoints)
+        c, nb = np.concatenate((c, c2), 0), np.concatenate((nb, nb2), 0)
+        if seg_on:
+            sg = _reresample(np.concatenate((sg, sg2), 0))         # Instances.concatenate constructs a new Instances
+        if kp_on:
+            kp = np.concatenate((kp, kp2), 0)
+    w, h = plan.size
     if len(c):                                                # Albumentations.__call__ touches the boxes only when there are any
         nb = _xyxy2xywh(nb)
         _mul(nb, 1 / w, 1 / h)
@@ -481,17 +520,21 @@ class DeviceAugmenter:
 
     def render(self, plans, staging=None):
         """pixels of a list of plans: uint8 [B, 3, s, s] RGB on the device (one launch on the current stream).  `staging`: optional
-        pinned uint8 host tensor (>= B * sizeof(dy_aug_sample)) the descriptors are written into and copied from asynchronously;
-        without it the copy comes from pageable memory and blocks the host."""
+        pinned uint8 host tensor (>= B * descriptor_bytes(mix)) the descriptors are written into and copied from asynchronously;
+        without it the copy comes from pageable memory and blocks the host.  With hyp.mixup > 0 the launch is dy_aug_mosaic_warp_mix
+        over dy_aug_mix_sample descriptors (mixed and un-mixed samples alike); with mixup == 0 nothing changes."""
         from .._C import call
         from ..ops import ptr, stream
         B, s = len(plans), self.imgsz
-        nbytes = B * descriptor_bytes()
+        mix = self.hyp.mixup > 0
+        nbytes = B * descriptor_bytes(mix)
         host = staging[:nbytes] if staging is not None else torch.empty(nbytes, dtype=torch.uint8)
-        fill_descriptors(plans, self.images, host.data_ptr())
+        if mix and nbytes:
+            host.zero_()                                      # padding and the unread half of un-mixed descriptors: defined bytes
+        fill_descriptors(plans, self.images, host.data_ptr(), mix)
         dev = host.to(self.device, non_blocking=staging is not None)
         out = torch.empty((B, 3, s, s), dtype=torch.uint8, device=self.device)
-        call("dy_aug_mosaic_warp", ptr(dev), B, s, s, ptr(out), stream())
+        call("dy_aug_mosaic_warp_mix" if mix else "dy_aug_mosaic_warp", ptr(dev), B, s, s, ptr(out), stream())
         self._keep = dev                                      # descriptor array stays alive until the next call
         return out
 
@@ -619,29 +662,47 @@ def polygon_masks(polys, offsets, rows, B, h, w, mask_ratio=4, overlap=True):
     return masks, rows_out, perm
 
 
-def descriptor_bytes():
+def descriptor_bytes(mix=False):
+    """sizeof(dy_aug_sample), or of dy_aug_mix_sample (the descriptor of dy_aug_mosaic_warp_mix)"""
     import ctypes as C
-    from .._C import AugSample
-    return C.sizeof(AugSample)
+    from .._C import AugMixSample, AugSample
+    return C.sizeof(AugMixSample if mix else AugSample)
 
 
-def fill_descriptors(plans, images, address):
-    """dy_aug_sample[len(plans)] at `address` (host memory owned by the caller) for plans over `images` (device tensors by dataset index)"""
+def _fill_geometry(a, p, images):
+    """the fields of a dy_aug_sample both sides of a MixUp need: sources, placement rectangles, canvas, inverse matrix"""
+    a.n_src = len(p.sources)
+    for j, (src, r) in enumerate(zip(p.sources, p.rects)):
+        im = images[src]
+        a.src[j], a.sh[j], a.sw[j], a.pitch[j] = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
+        rj = a.rect[j]
+        rj[0], rj[1], rj[2], rj[3], rj[4], rj[5] = int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[5])
+    a.canvas_h, a.canvas_w = p.canvas_hw
+    minv = invert_affine(p.M[:2]).reshape(-1)
+    m = a.minv
+    m[0], m[1], m[2], m[3], m[4], m[5] = (float(v) for v in minv)
+
+
+def fill_descriptors(plans, images, address, mix=False):
+    """dy_aug_sample[len(plans)] (mix: dy_aug_mix_sample[len(plans)]) at `address` (host memory owned by the caller) for plans over
+    `images` (device tensors by dataset index).  Without `mix` a plan that carries a MixUp partner is an error."""
     import ctypes as C
-    from .._C import AugSample
-    arr = (AugSample * len(plans)).from_address(address)
+    from .._C import AugMixSample, AugSample
+    arr = ((AugMixSample if mix else AugSample) * len(plans)).from_address(address)
     for k, p in enumerate(plans):
-        a = arr[k]
-        a.n_src = len(p.sources)
-        for j, (src, r) in enumerate(zip(p.sources, p.rects)):
-            im = images[src]
-            a.src[j], a.sh[j], a.sw[j], a.pitch[j] = im.data_ptr(), im.shape[0], im.shape[1], im.stride(0)
-            rj = a.rect[j]
-            rj[0], rj[1], rj[2], rj[3], rj[4], rj[5] = int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[5])
-        a.canvas_h, a.canvas_w = p.canvas_hw
-        minv = invert_affine(p.M[:2]).reshape(-1)
-        m = a.minv
-        m[0], m[1], m[2], m[3], m[4], m[5] = (float(v) for v in minv)
+        partner = getattr(p, "mix", None)
+        if mix:
+            d = arr[k]
+            a = d.a
+            d.mix = int(partner is not None)
+            if partner is not None:
+                _fill_geometry(d.b, partner, images)
+                d.r, d.r1 = p.mix_r, 1.0 - p.mix_r           # 1 - r in float64 on the host, as Python computes it
+        elif partner is not None:
+            raise ValueError("fill_descriptors: a plan with a MixUp partner needs the mix descriptor")
+        else:
+            a = arr[k]
+        _fill_geometry(a, p, images)
         a.hsv = int(p.hsv_gains is not None)
         if a.hsv:
             for c_ in range(3):

@@ -18,7 +18,13 @@ class DeviceAugmentLoader:
     """task="detect": batches of {img, batch_idx, cls, bboxes, n_max}.  task="segment" (labels carry `segments`): `masks` is added --
     rasterised on the device from the augmented polygons (csrc/polymask.hip) -- and batch_idx / cls / bboxes are the device rows in the
     area order the overlap masks index (`sorted_idx`: the permutation).  task="pose" (labels carry `keypoints`): `keypoints` [N, K, 3]
-    f32 is added.  Everything is uploaded from the pinned ring and issued on the loader's stream."""
+    f32 is added.  Everything is uploaded from the pinned ring and issued on the loader's stream.
+
+    hyp.mixup > 0: MixUp (ultralytics/data/augment.py:272-288) -- a second planned image per mixed sample is warped and blended in by the
+    same launch (dy_aug_mosaic_warp_mix) and its labels are appended to the primary's.  `close_mosaic()` switches mosaic / mixup /
+    copy_paste off from the next epoch on (the reference's trainer does that for the last `close_mosaic` epochs).  The non-mosaic path
+    (hyp.mosaic < 1, and every sample after close_mosaic) pads an image as it is: it needs every image at its load_image size (long
+    side == imgsz) and raises NotImplementedError otherwise."""
 
     def __init__(self, images, labels, imgsz, batch_size, hyp=None, device="cuda", resident=True, seed=0, shuffle=True, drop_last=True,
                  task="detect", flip_idx=None, mask_ratio=4, overlap_mask=True):
@@ -39,6 +45,22 @@ class DeviceAugmentLoader:
             self.host = [(im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))).pin_memory() for im in images]
             self.aug = None
         self.uploaded_bytes = 0
+        self._close = False
+
+    def close_mosaic(self):
+        """BaseTrainer's `close_mosaic` switch (engine/trainer.py:302-308 -> YOLODataset.close_mosaic, data/dataset.py:152-157): from the
+        next __iter__ on, mosaic = mixup = copy_paste = 0 on the loader's OWN copy of the hyper-parameters (the caller's object is left
+        alone).  A batch already prepared keeps its plans."""
+        self._close = True
+
+    def _apply_close(self):
+        import copy
+        hyp = copy.copy(self.hyp)
+        hyp.mosaic = hyp.mixup = hyp.copy_paste = 0.0
+        self.hyp = self.extras.hyp = hyp
+        if self.aug is not None:
+            self.aug.hyp = hyp
+        self._close = False
 
     def __len__(self):
         n = len(self.shapes)
@@ -54,7 +76,7 @@ class DeviceAugmentLoader:
         from .augment import descriptor_bytes
         if getattr(self, "_ring", None) is None:
             cap = 64 * self.bs                                   # label rows per batch the pinned buffer holds (grown on demand)
-            self._ring = [dict(desc=torch.empty(self.bs * descriptor_bytes(), dtype=torch.uint8).pin_memory(),
+            self._ring = [dict(desc=torch.empty(self.bs * descriptor_bytes(self.hyp.mixup > 0), dtype=torch.uint8).pin_memory(),
                                lab=torch.empty((cap, 6), dtype=torch.float32).pin_memory(), ev=torch.cuda.Event()) for _ in range(self.RING)]
             self._turn = 0
             self.stream = torch.cuda.Stream(device=self.device)
@@ -94,7 +116,7 @@ class DeviceAugmentLoader:
             if self.resident:
                 aug = self.aug
             else:
-                need = sorted({s for p in plans for s in p.sources})
+                need = sorted({s for p in plans for q in (p, p.mix) if q is not None for s in q.sources})
                 dev = {s: self.host[s].to(self.device, non_blocking=True) for s in need}
                 self.uploaded_bytes += sum(self.host[s].numel() for s in need)
                 aug = DeviceAugmenter.__new__(DeviceAugmenter)           # a view of the uploaded subset with the full index space
@@ -123,6 +145,8 @@ class DeviceAugmentLoader:
         return batch, slot["ev"], tensors
 
     def __iter__(self):
+        if self._close:
+            self._apply_close()
         order = list(range(len(self.shapes)))
         if self.shuffle:
             self.rnd.shuffle(order)

@@ -596,7 +596,8 @@ class DetectionTrainer:
         (:366-380, 408-433); then the stop flag of EarlyStopping(args.patience) is broadcast from rank 0 (:389-395) -- the
         collective doubles as the epoch-boundary barrier: the other ranks wait HERE, on the host, for rank 0's validation / save,
         not inside the first gradient all-reduce of the next epoch where a long validation would run into the RCCL watchdog.
-        `start_epoch`: resume_training's return value.  Returns the per-epoch loss items; self.metrics / self.fitness /
+        `start_epoch`: resume_training's return value.  args.close_mosaic = N > 0: at the top of epoch `epochs - N` (or of the first
+        epoch when a resumed run starts beyond it) `loader.close_mosaic()` is called if the loader has one.  Returns the per-epoch loss items; self.metrics / self.fitness /
         self.best_fitness / self.stop hold the rest."""
         epochs = epochs or self.args.epochs
         nb = len(loader)
@@ -606,7 +607,11 @@ class DetectionTrainer:
         nbs, bs = float(getattr(self.args, "nbs", 64)), max(int(getattr(self.args, "batch", 64)), 1)
         self.stopper = getattr(self, "stopper", None) or EarlyStopping(getattr(self.args, "patience", 50))
         self.stop = False
+        close = int(getattr(self.args, "close_mosaic", 0) or 0)
         for epoch in range(start_epoch, epochs):
+            # the last `close_mosaic` epochs run without mosaic / mixup (engine/trainer.py:302-308; on resume inside them :604-609)
+            if close > 0 and hasattr(loader, "close_mosaic") and (epoch == epochs - close or (epoch == start_epoch and epoch > epochs - close)):
+                loader.close_mosaic()
             for i, batch in enumerate(self._batches(loader)):
                 ni = i + nb * epoch
                 lr, mom = self.lr_factors(ni, nw, epoch, epochs)

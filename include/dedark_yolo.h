@@ -441,6 +441,17 @@ int dy_aug_letterbox(const uint8_t* src, int sh, int sw, int64_t src_pitch, int 
 /* Mosaic canvas -> cv2.warpAffine(borderValue 114) -> RandomHSV -> RandomFlip x2 -> Format for B samples in one launch (augment.py:158-195,
  * 323-345,486-499,527-532,745-751); samples: DEVICE array of B descriptors; out = uint8 [B, 3, out_h, out_w] RGB = batch['img']. */
 int dy_aug_mosaic_warp(const dy_aug_sample* samples, int B, int out_h, int out_w, uint8_t* out, void* stream);
+/* The same with MixUp (augment.py:272-288) for the samples whose `mix` is set: `b` (the partner after ITS Mosaic / RandomPerspective; only
+ * the geometry fields src, sh, sw, pitch, rect, n_src, canvas_*, minv are read) is warped at the same pixel and blended per channel as
+ * numpy's `(img1 * r + img2 * (1 - r)).astype(np.uint8)` -- float64 products and sum, each rounded once, truncation; r1 = 1.0 - r is
+ * computed by the caller in float64.  HSV gains and flips are `a`'s and act on the blend.  A sample with mix == 0 gives the bits of
+ * dy_aug_mosaic_warp on `a`. */
+typedef struct dy_aug_mix_sample {
+  dy_aug_sample a, b;
+  double r, r1;
+  int32_t mix;
+} dy_aug_mix_sample;
+int dy_aug_mosaic_warp_mix(const dy_aug_mix_sample* samples, int B, int out_h, int out_w, uint8_t* out, void* stream);
 /* DarkChannel / AtmLight / DarkIcA of preprocess_batch (train.py:42-68,81-96) without the device->host copy and the Python loop:
  * img f32 [B,3,H,W] in [0,1] (the darkened batch) -> A [B,3] (0..255 scale, as train.py:95), ica [B,1,H,W].  Deterministic: ties of the
  * reference's unstable argsort go by pixel index, the rows DarkIcA leaves uninitialised use the per-channel formula. */
