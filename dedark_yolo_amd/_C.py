@@ -11,10 +11,11 @@ LIB_PATH = os.path.join(os.environ.get("DY_LIB_DIR") or os.path.join(_HERE, "lib
 
 DY_F32, DY_BF16, DY_F16 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_LEAKY = 0, 1, 2
+OPT_RULES = dict(Adam=0, Adamax=1, NAdam=2, RAdam=3, RMSProp=4)      # DY_OPT_* of include/dedark_yolo.h
 STATS_REPLICAS = 64          # DY_STATS_REPLICAS of include/dedark_yolo.h
 BN_BWD_REPLICAS = 8          # DY_BN_BWD_REPLICAS
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 
 class ConvDesc(C.Structure):
@@ -154,6 +155,7 @@ _SIGS = {
     "dy_sgd_step_scaled": [vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, f32, f32, vp, i64, vp],
     "dy_adamw_step_scaled": [vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, f32, f32, vp, i64, vp],
     "dy_loss_scale_update": [vp, vp, f32, f32, i32, vp],
+    "dy_optim_step": [i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, f64, f64, f64, f64, f32, vp, f32, f32, vp, vp, i64, vp],
     "dy_adamw_step": [vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, f32, f32, i64, vp],
     "dy_ema_lerp": [vp, vp, f32, i64, vp],
     "dy_grad_accumulate": [vp, vp, i64, vp],

@@ -21,7 +21,7 @@ import torch.distributed as dist
 import yaml
 
 from .. import ops
-from .._C import call
+from .._C import OPT_RULES, call
 from ..nn.modules import DyModule
 from ..nn.tasks import DetectionModel, all_tasks, guess_model_task
 from ..ops import ptr, stream
@@ -35,6 +35,58 @@ def get_cfg(overrides=None):
     for k, v in (overrides or {}).items():
         d[k] = v
     return SimpleNamespace(**d)
+
+
+# the reference's `optimizer:` names (build_optimizer, U/engine/trainer.py:648-658; case-sensitive) besides "auto"
+OPTIMIZERS = ("SGD", "Adam", "Adamax", "AdamW", "NAdam", "RAdam", "RMSProp")
+ADAM_FAMILY = ("Adam", "Adamax", "NAdam", "RAdam")          # torch groups with `betas`: the warm-up leaves beta1 alone (trainer.py:326-327)
+# torch's names of FlatState.m / FlatState.m2 in each optimizer's state_dict
+STATE_KEYS = dict(SGD=("momentum_buffer", None), AdamW=("exp_avg", "exp_avg_sq"), Adam=("exp_avg", "exp_avg_sq"),
+                  Adamax=("exp_avg", "exp_inf"), NAdam=("exp_avg", "exp_avg_sq"), RAdam=("exp_avg", "exp_avg_sq"),
+                  RMSProp=("square_avg", "momentum_buffer"))
+
+
+def resolve_optimizer(name, lr0, momentum, nc=10, total_iterations=None):
+    """(optimizer name, lr0, momentum) of build_optimizer (U/engine/trainer.py:632-658): "auto" picks SGD(0.01, 0.9) above 10 000
+    iterations and AdamW(lr_fit, 0.9) below, every other name must be one of the reference's."""
+    if name == "auto":
+        lr_fit = round(0.002 * 5 / (4 + nc), 6)
+        iters = total_iterations if total_iterations is not None else 1e9
+        return ("SGD", 0.01, 0.9) if iters > 10000 else ("AdamW", lr_fit, 0.9)
+    if name not in OPTIMIZERS:
+        raise NotImplementedError(f"Optimizer '{name}' not found in list of available optimizers [{', '.join(OPTIMIZERS)}, auto].")
+    return name, lr0, momentum
+
+
+def optimizer_of_state_dict(opt, opt_name=None):
+    """The names a torch.optim-style state_dict can belong to.  The per-parameter key sets tell SGD, RMSProp, Adamax, NAdam and the
+    {Adam, RAdam, AdamW} family apart; inside the family `opt_name` (dy_state of a checkpoint of this package) decides when given, the
+    group keys otherwise (RAdam has no `amsgrad`, AdamW decouples the weight decay; torch versions that do not write
+    `decoupled_weight_decay` leave Adam / AdamW open).  A state_dict without any state (no step taken) is read by its group keys."""
+    keys = set()
+    for st in opt.get("state", {}).values():
+        keys |= set(st)
+    grp = (opt.get("param_groups") or [{}])[0]
+    if not keys:
+        keys = ({"momentum_buffer"} if "nesterov" in grp else {"square_avg"} if "alpha" in grp else {"mu_product"} if "momentum_decay" in grp
+                else {"exp_avg_sq"} if "amsgrad" in grp or "decoupled_weight_decay" in grp else {"exp_inf"} if "betas" in grp else set())
+        if not keys:
+            return set(OPTIMIZERS)
+    if "exp_inf" in keys:
+        return {"Adamax"}
+    if "mu_product" in keys:
+        return {"NAdam"}
+    if "square_avg" in keys:
+        return {"RMSProp"}
+    if "exp_avg_sq" in keys:
+        if opt_name in ("Adam", "RAdam", "AdamW"):
+            return {opt_name}
+        if "amsgrad" not in grp:
+            return {"RAdam"}
+        if "decoupled_weight_decay" not in grp:
+            return {"Adam", "AdamW"}
+        return {"AdamW"} if grp["decoupled_weight_decay"] else {"Adam"}
+    return {"SGD"} if "momentum_buffer" in keys else set()
 
 
 class FlatState:
@@ -67,6 +119,7 @@ class FlatState:
         self.g = torch.zeros(off, dtype=f32, device=dev)
         self.m = torch.zeros(off, dtype=f32, device=dev)
         self.m2 = None
+        self.opt_state = None
         self.gid = torch.zeros(off, dtype=torch.uint8, device=dev)
         for p, o, n, g in slots:
             self.p[o:o + n].copy_(p.data.reshape(-1))
@@ -90,6 +143,16 @@ class FlatState:
         self.buf_ema = self.buf_flat.clone() if with_ema else None
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         ops.bump_weights_epoch()
+
+    def alloc_optimizer(self, name):
+        """The second per-element buffer of every optimizer that has one (STATE_KEYS) and, for the rules of dy_optim_step, the scalar
+        record dy_optim_state (include/dedark_yolo.h) as 8 doubles: [0] = steps taken, [1] = NAdam's mu_product, the rest is the
+        kernels' own."""
+        if STATE_KEYS[name][1] is not None:
+            self.m2 = torch.zeros_like(self.m)
+        if name in OPT_RULES:
+            self.opt_state = torch.zeros(8, dtype=torch.float64, device=self.m.device)
+            self.opt_state[1] = 1.0
 
     def ema_state_dict(self, model):
         """state_dict of the EMA model (for checkpoints / validation)."""
@@ -256,6 +319,8 @@ class DetectionTrainer:
             model.load(weights)
         return model
 
+    resolve_optimizer = staticmethod(resolve_optimizer)
+
     def setup(self, model=None, nc=None, total_iterations=None):
         torch.cuda.set_device(self.device)
         dt = str(getattr(self.args, "dtype", "fp32"))
@@ -288,18 +353,11 @@ class DetectionTrainer:
         if self.world_size > 1:
             self.buckets = GradBuckets(self.flat, self.model)
         a = self.args
-        name = a.optimizer
-        if name == "auto":                                       # trainer.py:617-623
-            nc_ = getattr(self.model.model[-1], "nc", 10)
-            lr_fit = round(0.002 * 5 / (4 + nc_), 6)
-            iters = total_iterations if total_iterations is not None else 1e9
-            name, self.lr0, self.momentum = ("SGD", 0.01, 0.9) if iters > 10000 else ("AdamW", lr_fit, 0.9)
+        self.opt_name, self.lr0, self.momentum = self.resolve_optimizer(a.optimizer, a.lr0, a.momentum,
+                                                                        getattr(self.model.model[-1], "nc", 10), total_iterations)
+        if a.optimizer == "auto":                                # trainer.py:617-623
             a.warmup_bias_lr = 0.0
-        else:
-            self.lr0, self.momentum = a.lr0, a.momentum
-        self.opt_name = name
-        if name == "AdamW":
-            self.flat.m2 = torch.zeros_like(self.flat.m)
+        self.flat.alloc_optimizer(self.opt_name)
         self.mse_acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         # trainer.py:248-249: accumulate gradients up to the nominal batch size nbs, scale weight_decay accordingly
         nbs, bs = float(getattr(a, "nbs", 64)), max(int(getattr(a, "batch", 64)), 1)
@@ -351,7 +409,9 @@ class DetectionTrainer:
 
     # ---------------------------------------------------------------- step
     def lr_factors(self, ni, nw, epoch, epochs):
-        """warm-up interpolation of trainer.py:318-327 + linear / cosine schedule (:255-259)."""
+        """warm-up interpolation of trainer.py:318-327 + linear / cosine schedule (:255-259).  The reference warms `momentum` only in
+        groups that have that key (:326-327): SGD and RMSProp; torch's Adam-family groups carry `betas`, so beta1 stays args.momentum
+        (AdamW still receives the warmed value here: a known deviation)."""
         a = self.args
         lf = ((1 - math.cos(epoch * math.pi / epochs)) / 2) * (a.lrf - 1) + 1 if a.cos_lr else (1 - epoch / epochs) * (1.0 - a.lrf) + a.lrf
         lr = [self.lr0 * lf] * 3
@@ -359,7 +419,8 @@ class DetectionTrainer:
         if ni <= nw:
             xi = ni / max(nw, 1)
             lr = [self.lr0 * lf * xi, self.lr0 * lf * xi, a.warmup_bias_lr + (self.lr0 * lf - a.warmup_bias_lr) * xi]
-            mom = a.warmup_momentum + (self.momentum - a.warmup_momentum) * xi
+            if getattr(self, "opt_name", None) not in ADAM_FAMILY:
+                mom = a.warmup_momentum + (self.momentum - a.warmup_momentum) * xi
         return lr, mom
 
     def optimizer_step(self, lr, mom):
@@ -379,9 +440,13 @@ class DetectionTrainer:
         if self.opt_name == "AdamW":
             call("dy_adamw_step_scaled", ptr(f.p), ptr(g), ptr(f.m), ptr(f.m2), ptr(f.ema), ptr(f.gid), lr[0], lr[1], lr[2], wd, 0.0, 0.0,
                  mom, 0.999, 1e-8, self.updates, d, ptr(f.sumsq), 10.0, 1.0, ptr(ls), f.n, st)
-        else:
+        elif self.opt_name == "SGD":
             call("dy_sgd_step_scaled", ptr(f.p), ptr(g), ptr(f.m), ptr(f.ema), ptr(f.gid), lr[0], lr[1], lr[2], wd, 0.0, 0.0, mom, 1, d,
                  ptr(f.sumsq), 10.0, 1.0, ptr(ls), f.n, st)
+        else:                                       # beta1 (RMSProp: momentum) = mom, beta2 = 0.999 (RMSProp: alpha = 0.99), eps, NAdam's decay
+            call("dy_optim_step", OPT_RULES[self.opt_name], ptr(f.p), ptr(g), ptr(f.m), ptr(f.m2), ptr(f.ema), ptr(f.gid), lr[0], lr[1],
+                 lr[2], wd, 0.0, 0.0, mom, 0.99 if self.opt_name == "RMSProp" else 0.999, 1e-8, 0.004, d, ptr(f.sumsq), 10.0, 1.0, ptr(ls),
+                 ptr(f.opt_state), f.n, st)
         if ls is not None:
             call("dy_loss_scale_update", ptr(ls), ptr(f.sumsq), 2.0, 0.5, 2000, st)
         if f.buf_ema is not None and f.buf_flat.numel():
@@ -434,52 +499,79 @@ class DetectionTrainer:
 
     def optimizer_state_dict(self):
         """torch.optim-style state_dict of the fused optimizer -- what `optimizer.state_dict()` is in the reference's checkpoint
-        (trainer.py:423) and what its resume hands to `optimizer.load_state_dict` (:591): per-parameter momentum_buffer (SGD) or
-        step / exp_avg / exp_avg_sq (AdamW) + the three param_groups."""
+        (trainer.py:423) and what its resume hands to `optimizer.load_state_dict` (:591): the per-parameter state under torch's own
+        key names and dtypes (STATE_KEYS; `step` and NAdam's `mu_product` are the f32 scalars torch keeps, read from the device
+        record, i.e. the steps really taken) + the three param_groups with the keys and defaults torch writes for that optimizer."""
         f = self.flat
+        name = self.opt_name
         flat, sizes = self._param_order()
         m, m2 = f.m.detach().cpu(), None if f.m2 is None else f.m2.detach().cpu()
+        k1, k2 = STATE_KEYS[name]
+        fused = name in OPT_RULES
+        if fused:
+            step, mu_product = (float(v) for v in f.opt_state[:2].cpu())
+            if name == "RMSProp" and not float(self.momentum) > 0:
+                k2 = None                                     # torch creates momentum_buffer only for momentum > 0
         state = {}
         for i, (o, n, shape) in enumerate(flat):
-            if self.opt_name == "AdamW":
+            if name == "AdamW":
                 state[i] = dict(step=torch.tensor(float(self.updates)), exp_avg=m[o:o + n].view(shape).clone(),
                                 exp_avg_sq=m2[o:o + n].view(shape).clone())
-            else:
+            elif name == "SGD":
                 state[i] = dict(momentum_buffer=m[o:o + n].view(shape).clone())
+            elif step > 0:                                    # torch creates a parameter's state at its first step
+                st = dict(step=torch.tensor(step, dtype=torch.float32))
+                if name == "NAdam":
+                    st["mu_product"] = torch.tensor(mu_product, dtype=torch.float32)
+                st[k1] = m[o:o + n].view(shape).clone()
+                if k2 is not None:
+                    st[k2] = m2[o:o + n].view(shape).clone()
+                state[i] = st
         groups, k = [], 0
+        betas = dict(betas=(float(self.momentum), 0.999), eps=1e-8)
+        extra = dict(SGD=dict(momentum=float(self.momentum), dampening=0, nesterov=True, fused=None),
+                     AdamW=dict(betas, amsgrad=False, capturable=False, fused=None),
+                     Adam=dict(betas, amsgrad=False, capturable=False, fused=None, decoupled_weight_decay=False),
+                     Adamax=dict(betas, capturable=False),
+                     NAdam=dict(betas, momentum_decay=0.004, decoupled_weight_decay=False, capturable=False),
+                     RAdam=dict(betas, capturable=False, decoupled_weight_decay=False),
+                     RMSProp=dict(momentum=float(self.momentum), alpha=0.99, eps=1e-8, centered=False, capturable=False))[name]
         for gi, cnt in enumerate(sizes):
             common = dict(lr=float(self.lr0), initial_lr=float(self.lr0), weight_decay=float(self.weight_decay) if gi == 1 else 0.0,
                           maximize=False, foreach=None, differentiable=False, params=list(range(k, k + cnt)))
-            if self.opt_name == "AdamW":
-                common.update(betas=(float(self.momentum), 0.999), eps=1e-8, amsgrad=False, capturable=False, fused=None)
-            else:
-                common.update(momentum=float(self.momentum), dampening=0, nesterov=True, fused=None)
+            common.update(extra)
             groups.append(common)
             k += cnt
         return dict(state=state, param_groups=groups)
 
-    def load_optimizer_state_dict(self, opt):
-        """Inverse of optimizer_state_dict; also reads the optimizer entry of a checkpoint the REFERENCE wrote."""
+    def load_optimizer_state_dict(self, opt, opt_name=None):
+        """Inverse of optimizer_state_dict; also reads the optimizer entry of a checkpoint the REFERENCE wrote.  `opt_name` is the
+        writer's optimizer name when the checkpoint records one (dy_state)."""
         f = self.flat
         flat, sizes = self._param_order()
         groups = opt.get("param_groups", [])
         if [len(g["params"]) for g in groups] != sizes:
             raise RuntimeError(f"resume: optimizer groups {[len(g['params']) for g in groups]} do not match this model's {sizes}")
-        adam = any("exp_avg" in st for st in opt["state"].values())
-        if adam != (self.opt_name == "AdamW"):
-            raise RuntimeError(f"resume: checkpoint optimizer state does not belong to {self.opt_name}")
+        name = self.opt_name
+        if name not in optimizer_of_state_dict(opt, opt_name):
+            raise RuntimeError(f"resume: checkpoint optimizer state does not belong to {name}")
+        k1, k2 = STATE_KEYS[name]
         f.m.zero_()
         if f.m2 is not None:
             f.m2.zero_()
+        step, mu_product = 0.0, 1.0
         for i, (o, n, shape) in enumerate(flat):
             st = opt["state"].get(i)
             if not st:
                 continue                                      # torch creates state lazily: a parameter that never stepped has none
-            if adam:
-                f.m[o:o + n].copy_(st["exp_avg"].reshape(-1).float())
-                f.m2[o:o + n].copy_(st["exp_avg_sq"].reshape(-1).float())
-            elif st.get("momentum_buffer") is not None:
-                f.m[o:o + n].copy_(st["momentum_buffer"].reshape(-1).float())
+            if st.get(k1) is not None:
+                f.m[o:o + n].copy_(st[k1].reshape(-1).float())
+            if k2 is not None and st.get(k2) is not None:
+                f.m2[o:o + n].copy_(st[k2].reshape(-1).float())
+            step = max(step, float(st.get("step", 0.0)))      # the fused step moves every parameter at once: one count for all
+            mu_product = float(st.get("mu_product", mu_product))
+        if f.opt_state is not None:                           # the first step after a resume takes its bias correction at step + 1
+            f.opt_state.copy_(torch.tensor([step, mu_product] + [0.0] * 6, dtype=torch.float64))
 
     def save_model(self, wdir, epoch=0, fitness=None):
         """trainer.save_model (U/engine/trainer.py:408-433): last.pt always, best.pt when `fitness` is the best so far -- in the
@@ -533,11 +625,11 @@ class DetectionTrainer:
         for k, b in self.model.named_buffers():                     # integer buffers (num_batches_tracked)
             if not b.dtype.is_floating_point and k in msd:
                 b.copy_(msd[k].to(b.device))
+        dy_state = getattr(ck, "dy_state", None) or {}
         if ck.optimizer is not None:
-            self.load_optimizer_state_dict(ck.optimizer)
+            self.load_optimizer_state_dict(ck.optimizer, dy_state.get("opt_name"))
         self.best_fitness = ck.best_fitness
         self.updates = int(ck.updates or 0)
-        dy_state = getattr(ck, "dy_state", None) or {}
         self.step_count = int(dy_state.get("step_count", 0))
         self.last_opt_step = int(dy_state.get("last_opt_step", -1))
         ls = dy_state.get("loss_scale")

@@ -388,6 +388,34 @@ int dy_adamw_step_scaled(float* p, const float* g, float* exp_avg, float* exp_av
                          float ema_decay, const double* sumsq, float max_norm, float grad_scale, const float* loss_scale, int64_t n,
                          void* stream);
 int dy_loss_scale_update(float* state, const double* sumsq, float growth, float backoff, int interval, void* stream);
+/* The other optimizers of build_optimizer (U/engine/trainer.py:648-651): torch.optim.Adam / Adamax / NAdam / RAdam with
+ * betas = (momentum, 0.999), and RMSprop(momentum = momentum); the update rules are torch's _single_tensor_adam / _adamax / _nadam /
+ * _radam / _rmsprop (torch.optim), weight decay as L2 (added to the gradient), no amsgrad, not centered.  One call replaces
+ * clip_grad_norm_ + optimizer.step() + ema.update() like the entries above, with the same group_id / sumsq / grad_scale / loss_scale /
+ * ema contract.  buf1 / buf2 are the two per-element state buffers:
+ *   DY_OPT_ADAM, DY_OPT_NADAM, DY_OPT_RADAM: exp_avg / exp_avg_sq     DY_OPT_ADAMAX: exp_avg / exp_inf
+ *   DY_OPT_RMSPROP: square_avg / momentum_buffer (beta1 = momentum, beta2 = alpha; momentum == 0 leaves buf2 alone)
+ * momentum_decay is NAdam's (0.004), ignored by the other rules.
+ * The scalar state of the optimizer lives on the device in *state (64 bytes, 8-byte aligned; the caller sets step = 0 and
+ * mu_product = 1 before the first step and may read or write both between steps, e.g. for a checkpoint).  A one-thread launch ahead of
+ * the element kernel decides the overflow skip from *sumsq and loss_scale, advances `step` (steps really TAKEN: a skipped step leaves
+ * step, mu_product, the parameters and both buffers untouched, only the EMA moves) and NAdam's running mu_product, and computes the
+ * step's uniform scalars in double precision; the element kernel reads them as floats.  No host synchronisation. */
+enum { DY_OPT_ADAM = 0, DY_OPT_ADAMAX = 1, DY_OPT_NADAM = 2, DY_OPT_RADAM = 3, DY_OPT_RMSPROP = 4 };
+typedef struct dy_optim_state {
+  double step;        /* optimizer steps taken so far (torch's state['step']) */
+  double mu_product;  /* NAdam: product of mu_1 .. mu_step, rounded to f32 after every step as torch's f32 state['mu_product'] is; 1 before the first step */
+  float grad_coef;    /* written every call: clip coefficient * grad_scale / loss scale of this step */
+  int32_t skipped;    /* written every call: 1 = this step found an inf / NaN gradient and was skipped */
+  float c[4];         /* written on a taken step.  Adam: {1 - beta1^t, sqrt(1 - beta2^t)}; Adamax: {1 - beta1^t};
+                         NAdam: {1 - beta2^t, (1 - mu_t) / (1 - mu_product_t), mu_{t+1} / (1 - mu_product_t * mu_{t+1})};
+                         RAdam: {1 - beta1^t, sqrt(1 - beta2^t), rectification r_t, rho_t > 5 ? 1 : 0}; RMSProp: none */
+  float reserved[6];
+} dy_optim_state;
+int dy_optim_step(int rule, float* p, const float* g, float* buf1, float* buf2, float* ema, const uint8_t* group_id, float lr0,
+                  float lr1, float lr2, float wd0, float wd1, float wd2, double beta1, double beta2, double eps,
+                  double momentum_decay, float ema_decay, const double* sumsq, float max_norm, float grad_scale,
+                  const float* loss_scale, dy_optim_state* state, int64_t n, void* stream);
 /* ema = decay*ema + (1-decay)*src (EMA of the BatchNorm running buffers) */
 int dy_ema_lerp(float* ema, const float* src, float decay, int64_t n, void* stream);
 /* acc += g: gradient accumulation over `accumulate` batches (nbs / batch, U/engine/trainer.py:248,340-342) */
