@@ -111,6 +111,10 @@ _SIGS = {
     "dy_pconv_fwd": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "dy_pconv_dgrad": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
     "dy_pconv_wgrad": [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, i64, i32, vp],
+    "dy_dwconv_fwd": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp],
+    "dy_dwconv_dgrad": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
+    "dy_dwconv_wgrad": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
+    "dy_copy2d_exact": [vp, i64, vp, i64, i64, i32, i32, i32, vp],
     "dy_asff_fuse_fwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, i32, vp],
     "dy_asff_fuse_bwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, i32, i32,
                          i32, i32, vp],

@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
@@ -123,12 +123,17 @@ def _act_code(act):
 
 
 class Conv(DyModule):
-    """Conv2d(bias=False) + BatchNorm2d + SiLU (reference ultralytics/nn/modules/conv.py:38-55)."""
+    """Conv2d(bias=False) + BatchNorm2d + SiLU (reference ultralytics/nn/modules/conv.py:38-55).  g == 1 runs the MFMA convolutions;
+    g == c1 == c2 (pure depthwise: odd k <= 7, stride 1 or 2, no dilation) runs the depthwise kernels (ops.dwconv_forward); every other
+    grouping is refused."""
     default_act = nn.SiLU()
+    _dw = False              # True on an instance: pure depthwise, runs ops.dwconv_forward / dwconv_backward
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
         if g != 1:
+            self._dw = True
+        if self._dw and not (g == c1 == c2 and d == 1 and isinstance(k, int) and k % 2 == 1 and 3 <= k <= 7 and s in (1, 2) and p in (None, k // 2)):
             raise NotImplementedError("grouped convolution is outside the Dedark-YOLO hot path")
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p, d), groups=g, dilation=d, bias=False)
         self.bn = nn.BatchNorm2d(c2)
@@ -137,16 +142,111 @@ class Conv(DyModule):
 
     def _fwd(self, tape, x, out=None, residual=None):
         c = self.conv
+        if self._dw:
+            if residual is not None:
+                raise RuntimeError("Conv: the depthwise path takes no residual")
+            return ops.dwconv_forward(tape, x, c.weight, None, self.bn, self._act, c.stride[0], self.training, out=out)
         return conv_forward(tape, x, c.weight, None, self.bn, self._act, c.stride[0], c.padding[0], c.dilation[0],
                             self.training, out=out, residual=residual)
 
     _takes_into = True       # GraphPlan.backward_train: `into[k]` = gradient another consumer of input k already left; add into it
 
     def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False, add_src=None, into=None):
+        bwd = ops.dwconv_backward if self._dw else conv_backward
         if into is not None and into[0] is not None:
-            conv_backward(tape, dy, need_dx=True, dx_out=into[0], accumulate=True)
+            bwd(tape, dy, need_dx=True, dx_out=into[0], accumulate=True)
             return None
-        return conv_backward(tape, dy, need_dx=needs[0], dx_out=dx_out, accumulate=accumulate, add_src=add_src)
+        return bwd(tape, dy, need_dx=needs[0], dx_out=dx_out, accumulate=accumulate, add_src=add_src)
+
+
+class DWConv(Conv):
+    """Depthwise Conv (reference conv.py:95-99): g = gcd(c1, c2); only the pure depthwise case c1 == c2 is implemented."""
+
+    def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
+        g = math.gcd(c1, c2)
+        if not (g == c1 == c2):
+            raise NotImplementedError("grouped convolution is outside the Dedark-YOLO hot path")
+        super().__init__(c1, c2, k, s, g=g, d=d, act=act)
+
+
+class GhostConv(DyModule):
+    """cat(y, cv2(y)), y = cv1(x), cv2 a 5x5 depthwise Conv over the c2 // 2 hidden channels (reference conv.py:142-154).  One
+    buffer: cv1 writes its first half, the depthwise kernel reads that half and writes the second (exact channel bounds: the halves
+    are live neighbours).  A half that is not made of whole 16-byte vectors (4 / 12 / 20 channels in a 16-bit dtype) cannot be the
+    direct target of the MFMA conv or the BatchNorm pass: cv1 then runs into a temporary that ops.copy_exact moves over."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
+        self._c = c_
+
+    def _fwd(self, tape, x, out=None, residual=None):
+        """residual: optional view of the output's shape added to it (GhostBottleneck's identity shortcut).  The first half is the
+        depthwise conv's input, which the tape keeps for the weight gradient: when a residual is going to be added on top of it
+        (training), cv1 keeps its own buffer and the half is copied over."""
+        c_ = self._c
+        B, _, H, W = x.shape
+        c = self.cv1.conv
+        k, st, p = c.kernel_size[0], c.stride[0], c.padding[0]
+        Ho, Wo = (H + 2 * p - k) // st + 1, (W + 2 * p - k) // st + 1
+        Y = out if out is not None else ops._nhwc_like(B, 2 * c_, Ho, Wo, x.dtype, x.device)
+        a, b = Y[:, :c_], Y[:, c_:]
+        whole = ops.vec_ok(a)
+        if whole and not (residual is not None and tape is not None):
+            y1 = self.cv1._fwd(tape, x, out=a)
+        else:
+            y1 = self.cv1._fwd(tape, x)
+            (copy2d if whole else ops.copy_exact)(y1, a)
+        self.cv2._fwd(tape, y1, out=b)
+        if residual is not None:
+            (copy2d if ops.vec_ok(residual) and ops.vec_ok(Y) else ops.copy_exact)(residual, Y, accumulate=True)
+            ops.emu_round(Y)
+        return Y
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False, add_src=None):
+        """d cat(y, cv2(y)): the first half of dy joins cv2's data gradient as its add_src (one launch)."""
+        c_ = self._c
+        da, db = dy[:, :c_], dy[:, c_:]
+        g = self.cv2._bwd(tape, db, add_src=da)
+        return self.cv1._bwd(tape, g, needs=needs, dx_out=dx_out, accumulate=accumulate, add_src=add_src)
+
+
+class GhostBottleneck(DyModule):
+    """conv(x) + shortcut(x), conv = GhostConv -> [DWConv s2] -> GhostConv(act=False) (reference block.py:535-550).  s == 1: the
+    identity shortcut is added into the last GhostConv's buffer by one dy_copy2d(accumulate) (GhostConv's `residual`) and its gradient
+    rides on the first GhostConv's data gradient (add_src).  s == 2: the shortcut's 1x1 Conv adds conv(x) in its BatchNorm pass (residual) and the two
+    input gradients meet in one buffer (dx_out, accumulate)."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1), DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+                                  GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+        self._s2 = s == 2
+        if not self._s2 and c1 != c2:
+            raise ValueError("GhostBottleneck: the identity shortcut needs c1 == c2")
+
+    def _fwd(self, tape, x, out=None):
+        cv = self.conv
+        t = cv[0]._fwd(tape, x)
+        if not self._s2:
+            return cv[2]._fwd(tape, t, out=out, residual=x)
+        u = cv[2]._fwd(tape, cv[1]._fwd(tape, t))
+        return self.shortcut[1]._fwd(tape, self.shortcut[0]._fwd(tape, x), out=out, residual=u)
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        cv = self.conv
+        if not self._s2:
+            dt = cv[2]._bwd(tape, dy)
+            return cv[0]._bwd(tape, dt, needs=needs, dx_out=dx_out, accumulate=accumulate, add_src=dy)
+        dx = self.shortcut[0]._bwd(tape, self.shortcut[1]._bwd(tape, dy), needs=needs, dx_out=dx_out, accumulate=accumulate)
+        dt = cv[1]._bwd(tape, cv[2]._bwd(tape, dy))
+        if not needs[0]:
+            return cv[0]._bwd(tape, dt, needs=needs)
+        return cv[0]._bwd(tape, dt, dx_out=dx, accumulate=True)
 
 
 class AddConv(nn.Module):
@@ -324,6 +424,51 @@ class C2f(DyModule):
         for i in reversed(range(n)):
             self.m[i]._bwd(tape, dY[:, (2 + i) * c:(3 + i) * c], dx_out=dY[:, (1 + i) * c:(2 + i) * c], accumulate=True)
         return self.cv1._bwd(tape, dY[:, :2 * c], needs=needs)
+
+
+class C3(DyModule):
+    """CSP bottleneck with three convolutions (reference block.py:473-486): cv3(cat(m(cv1(x)), cv2(x))).  cv2 and the last block of
+    m write the two halves of cv3's input buffer; backward: both input gradients meet in one buffer (cv2 adds into cv1's)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.cv3 = Conv(2 * c_, c2, 1)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
+        self._c = c_
+        if c_ % 8:
+            raise NotImplementedError("C3: a hidden width that is not a multiple of 8 is outside the Dedark-YOLO hot path")
+
+    def _fwd(self, tape, x, out=None):
+        c_, n = self._c, len(self.m)
+        B, _, H, W = x.shape
+        Z = empty_nhwc(B, 2 * c_, H, W, x.dtype, x.device)             # cv3's input: [m(cv1(x)) | cv2(x)]
+        self.cv2._fwd(tape, x, out=Z[:, c_:])
+        t = self.cv1._fwd(tape, x, out=Z[:, :c_] if n == 0 else None)
+        for i, m in enumerate(self.m):
+            t = m._fwd(tape, t, out=Z[:, :c_] if i == n - 1 else None)
+        return self.cv3._fwd(tape, Z, out=out)
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        c_, n = self._c, len(self.m)
+        dZ = self.cv3._bwd(tape, dy)
+        g = dZ[:, :c_]
+        for i in reversed(range(n)):
+            g = self.m[i]._bwd(tape, g)
+        dx = self.cv1._bwd(tape, g, needs=needs)
+        if not needs[0]:
+            return self.cv2._bwd(tape, dZ[:, c_:], needs=needs)
+        return self.cv2._bwd(tape, dZ[:, c_:], dx_out=dx, accumulate=True)
+
+
+class C3Ghost(C3):
+    """C3 with GhostBottleneck blocks (reference block.py:525-532)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.Sequential(*(GhostBottleneck(self._c, self._c) for _ in range(n)))
 
 
 class PConv(DyModule):

@@ -16,7 +16,8 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, Classify, Concat, Conv, Detect, DyModule, FasterC2f, FasterC2f_N, MFRU,
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, Classify, Concat, Conv, DWConv, Detect, DyModule, FasterC2f, FasterC2f_N,
+                      GhostBottleneck, GhostConv, MFRU,
                       PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SPPF, Segment, Tape, Upsample,
                       lowlight_recovery)
 
@@ -30,7 +31,8 @@ CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models" / "v8"
 _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Detect, AsffDetect=AsffDetect, AsffTribeLevel=AsffTribeLevel,
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
-                 Segment=Segment, Pose=Pose, Classify=Classify)
+                 Segment=Segment, Pose=Pose, Classify=Classify,
+                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -95,6 +97,7 @@ _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
     PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
+    GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f,   # tasks.py:856-874
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
     AsffTribeLevel: lambda r: (r.args, 512 if r.args[0] in (0, 1) else 256, r.repeats),       # tasks.py:892-896
@@ -109,14 +112,14 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2, C2f, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):
     """Spatial size of m(x) for the placeable module types."""
     H, W = x.shape[2], x.shape[3]
-    if isinstance(m, Conv):
-        c = m.conv
+    if isinstance(m, (Conv, GhostConv)):
+        c = m.conv if isinstance(m, Conv) else m.cv1.conv
         k, st, p, d = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
         return (H + 2 * p - d * (k - 1) - 1) // st + 1, (W + 2 * p - d * (k - 1) - 1) // st + 1
     if isinstance(m, Upsample):
@@ -590,9 +593,10 @@ class DetectionModel(BaseModel):
         for L in self.model:
             f = L.f
             prev = (s[L.i - 1] if L.i > 0 else 1) if f == -1 else None
-            if isinstance(L, Conv):
+            if isinstance(L, (Conv, GhostConv, GhostBottleneck)):
                 base = prev if f == -1 else s[f]
-                s.append(base * L.conv.stride[0])
+                s.append(base * (L.conv.stride[0] if isinstance(L, Conv) else L.cv1.conv.stride[0] if isinstance(L, GhostConv)
+                                 else (2 if L._s2 else 1)))
             elif isinstance(L, Upsample):
                 s.append((prev if f == -1 else s[f]) / L.scale_factor)
             elif isinstance(L, Concat):

@@ -817,6 +817,191 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
     return dx
 
 
+# ------------------------------------------------------------------------------------------------ depthwise conv
+def vec_ok(t):
+    """may the vectorised entries (dy_bn_act_*, dy_copy2d, the tiled convs) take view `t` as it is?  Whole 16-byte vectors: C a
+    vector multiple, 16-byte aligned pointer and pixel stride.  A half of GhostConv's buffer whose width is 4 / 12 / 20 channels in a
+    16-bit dtype is not; the depthwise kernels and copy_exact take it anyway."""
+    return t.shape[1] % vec_elems(t.dtype) == 0 and t.data_ptr() % 16 == 0 and (ld_of(t) * t.element_size()) % 16 == 0
+
+
+def copy_exact(src, dst, accumulate=False):
+    """dst[:, :C] (+)= src[:, :C] touching exactly C lanes per pixel (dy_copy2d_exact), for views that are not vec_ok"""
+    B, Cc, H, W = src.shape
+    if tuple(dst.shape) != (B, Cc, H, W) or dst.dtype != src.dtype:
+        raise RuntimeError("copy_exact: views differ in shape or dtype")
+    call("dy_copy2d_exact", ptr(src), ld_of(src), ptr(dst), ld_of(dst), B * H * W, Cc, 1 if accumulate else 0, dt_id(src.dtype), stream())
+
+
+def _w32(weight):
+    w = weight.detach()
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    return w
+
+
+class DwCtx:
+    __slots__ = ("x", "z", "aff", "weight", "bias", "bn", "act", "k", "stride", "y")
+
+
+def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
+    """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.
+    x / out: NHWC views of C channels that need not be vector multiples or aligned (exact lanes).
+
+    Training + bn: dy_dwconv_fwd in statistics mode (raw z + batch sums) -> dy_bn_finalize_valid -> dy_bn_act_fwd.  The
+    BatchNorm pass wants whole vectors: z is a vector-padded temporary (kept for the backward pass anyway), and y goes straight
+    into `out` where that view is vec_ok (no extra copy), else through a padded temporary and copy_exact.
+    Otherwise one launch with the affine (folded BN / bias) and the activation in the epilogue, written straight into `out`."""
+    dtype, dev = x.dtype, x.device
+    B, Cc, H, W = x.shape
+    k = weight.shape[2]
+    if tuple(weight.shape) != (Cc, 1, k, k):
+        raise RuntimeError(f"dwconv: weight {tuple(weight.shape)} is not depthwise over {Cc} channels")
+    pad = k // 2
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if out is not None and (tuple(out.shape) != (B, Cc, Ho, Wo) or out.dtype != dtype):
+        raise RuntimeError("dwconv: `out` does not match the output")
+    cpad = round_up(Cc, vec_elems(dtype))
+    pixels, es, did, st = B * Ho * Wo, x.element_size(), dt_id(dtype), stream()
+    w32 = _w32(weight)
+    has_bn = bn is not None
+    ctx = None
+    if tape is not None:
+        ctx = DwCtx()
+        ctx.x, ctx.weight, ctx.bias, ctx.bn, ctx.act, ctx.k, ctx.stride = x, weight, bias, bn, act, k, stride
+    flops, nbytes = 2.0 * pixels * Cc * k * k, float((B * H * W + pixels) * Cc * es + Cc * k * k * 4)
+    shape = f"dw {Cc} k{k} s{stride} in {B}x{H}x{W}"
+    if has_bn and training:
+        z = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        stats = arena.alloc(2 * cpad * _C.STATS_REPLICAS, dev)
+        aff = torch.empty((4, cpad), dtype=torch.float32, device=dev)     # scale, shift, mean, invstd
+        pa, sa = aff.data_ptr(), 4 * cpad
+        _bn_pending[bn] = _bn_pending.get(bn, 0) + 1
+        bn.__dict__.pop("_dy_fold", None)
+        _C._prof is not None and _C.set_meta(kind="dwconv_fwd", shape=shape, dtype=str(dtype), flops=flops, bytes=nbytes)
+        call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(z), ld_of(z), ptr(w32), B, H, W, Cc, k, stride, None, None, ACT_NONE, ptr(stats), cpad,
+             did, st)
+        emu_round(z)
+        call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+             float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cpad, Cc, st)
+        direct = out is not None and vec_ok(out)
+        y = out if direct else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        _C._prof is not None and _C.set_meta(kind="bn_act_fwd", shape=f"{cpad}ch {B}x{Ho}x{Wo}", dtype=str(dtype), flops=0.0,
+                                             bytes=float(pixels * cpad * es * 2))
+        call("dy_bn_act_fwd", ptr(z), ld_of(z), pa, pa + sa, act, None, 0, ptr(y), ld_of(y), pixels, cpad, did, st)
+        emu_round(y)
+        if out is not None and not direct:
+            copy_exact(y, out)
+            y = out
+        if ctx is not None:
+            ctx.z, ctx.aff, ctx.y = z, aff, None
+    else:
+        if has_bn:
+            aff = bn_fold(bn, cpad)
+            scale, shift = aff[0], aff[1]
+        else:
+            scale, shift = None, (None if bias is None else bias.detach().float())
+        y = out if out is not None else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        _C._prof is not None and _C.set_meta(kind="dwconv_fwd", shape=shape, dtype=str(dtype), flops=flops, bytes=nbytes)
+        call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(y), ld_of(y), ptr(w32), B, H, W, Cc, k, stride, ptr(scale), ptr(shift), act, None, 0,
+             did, st)
+        emu_round(y)
+        if ctx is not None:
+            if has_bn:
+                raise RuntimeError("dwconv: gradients through an eval-mode BatchNorm are not supported")
+            ctx.z, ctx.aff, ctx.y = None, None, y
+    if tape is not None:
+        tape.push(ctx)
+    return y
+
+
+def dwconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src=None):
+    """Backward of the matching dwconv_forward (pops its context), the contract of conv_backward: BatchNorm / activation backward
+    (dy_bn_act_bwd*, on a vector-padded copy of dy when the view is not vec_ok), the deterministic f32 weight gradient on the
+    compute stream, and dx = [dx_out +] dgrad [+ add_src] in one launch with exact channel bounds."""
+    ctx = tape.pop()
+    x = ctx.x
+    dtype, dev = x.dtype, x.device
+    B, Cc, H, W = x.shape
+    k, stride = ctx.k, ctx.stride
+    Ho, Wo = dy.shape[2], dy.shape[3]
+    cpad = round_up(Cc, vec_elems(dtype))
+    pixels, es, did, st = B * Ho * Wo, x.element_size(), dt_id(dtype), stream()
+    if tuple(dy.shape) != (B, Cc, Ho, Wo) or dy.dtype != dtype:
+        raise RuntimeError("dwconv_backward: gradient does not match the forward's output")
+    need_bias = ctx.bias is not None and ctx.bias.requires_grad
+    if (ctx.bn is not None or ctx.act != ACT_NONE or need_bias) and not vec_ok(dy):
+        t = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)           # the BatchNorm passes read whole vectors: stage the slice
+        copy_exact(dy, t)
+        dy = t
+    if ctx.bn is not None:
+        aff, z, bn = ctx.aff, ctx.z, ctx.bn
+        sums = arena.alloc(2 * cpad * _C.BN_BWD_REPLICAS, dev)
+        dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        gw_, gb_ = _grad_dst(bn.weight), _grad_dst(bn.bias)
+        direct = gw_ is not None and gb_ is not None
+        if not direct:
+            dgb = torch.empty((2, Cc), dtype=torch.float32, device=dev)
+            gw_, gb_ = dgb[0], dgb[1]
+        _C._prof is not None and _C.set_meta(kind="bn_act_bwd", shape=f"{cpad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cpad * es * 5))
+        call("dy_bn_act_bwd_valid", ptr(dy), ld_of(dy), ptr(z), ld_of(z), aff.data_ptr(), ptr(bn._parameters["weight"]), ctx.act,
+             ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cpad, Cc, did, st)
+        emu_round(dz)
+        if not direct:
+            _add_pgrad(tape, bn.weight, gw_)
+            _add_pgrad(tape, bn.bias, gb_)
+    elif ctx.act == ACT_NONE and not need_bias:
+        dz = dy
+    else:
+        y = ctx.y
+        if not vec_ok(y):
+            t = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+            copy_exact(y, t)
+            y = t
+        sums = arena.alloc(2 * cpad * _C.BN_BWD_REPLICAS, dev)
+        call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, ctx.act, 0, ptr(sums), pixels, cpad, did, st)
+        db = torch.empty(cpad, dtype=torch.float32, device=dev)
+        dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0, ptr(sums),
+             ptr(dz), ld_of(dz), None, ptr(db), pixels, cpad, Cc, did, st)
+        emu_round(dz)
+        if need_bias:
+            gd = _grad_dst(ctx.bias)
+            if gd is not None:
+                gd.copy_(db[:Cc])
+            else:
+                _add_pgrad(tape, ctx.bias, db[:Cc])
+    w32 = _w32(ctx.weight)
+    shape = f"dw {Cc} k{k} s{stride} in {B}x{H}x{W}"
+    flops = 2.0 * pixels * Cc * k * k
+    if ctx.weight.requires_grad:
+        gd = _grad_dst(ctx.weight)
+        gw = gd if gd is not None else torch.empty(ctx.weight.shape, dtype=torch.float32, device=dev)
+        scratch = wgrad_scratch(dev, tag=st)
+        _C._prof is not None and _C.set_meta(kind="dwconv_wgrad", shape=shape, dtype=str(dtype), flops=flops,
+                                             bytes=float((B * H * W + pixels) * Cc * es + Cc * k * k * 4))
+        call("dy_dwconv_wgrad", ptr(x), ld_of(x), ptr(dz), ld_of(dz), ptr(gw), B, H, W, Cc, k, stride, ptr(scratch), scratch.numel(), did, st)
+        if gd is None:
+            _add_pgrad(tape, ctx.weight, gw)
+    if not need_dx:
+        return None
+    if dx_out is None:
+        dx, accumulate = _nhwc_like(B, Cc, H, W, dtype, dev), False
+    else:
+        dx = dx_out
+        if tuple(dx.shape) != (B, Cc, H, W) or dx.dtype != dtype:
+            raise RuntimeError("dwconv_backward: dx_out does not match the input")
+    if add_src is not None and (tuple(add_src.shape) != (B, Cc, H, W) or add_src.dtype != dtype):
+        raise RuntimeError("dwconv_backward: add_src must be an NHWC view of dx's shape and dtype")
+    n_rw = 1 + (1 if accumulate else 0) + (1 if add_src is not None else 0)
+    _C._prof is not None and _C.set_meta(kind="dwconv_dgrad", shape=shape, dtype=str(dtype), flops=flops,
+                                         bytes=float((n_rw * B * H * W + pixels) * Cc * es + Cc * k * k * 4))
+    call("dy_dwconv_dgrad", ptr(dz), ld_of(dz), ptr(dx), ld_of(dx), ptr(w32), B, H, W, Cc, k, stride, 1 if accumulate else 0,
+         ptr(add_src), 0 if add_src is None else ld_of(add_src), did, st)
+    emu_round(dx)
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ small ops
 def copy2d(src, dst, accumulate=False):
     B, Cc, H, W = src.shape

@@ -207,10 +207,11 @@ def intersect_dicts(da, db, exclude=()):
 _REF_HOME = {"DetectionModel": "ultralytics.nn.tasks", "SegmentationModel": "ultralytics.nn.tasks", "Proto": "ultralytics.nn.modules.block",
              "Segment": "ultralytics.nn.modules.head", "PoseModel": "ultralytics.nn.tasks", "Pose": "ultralytics.nn.modules.head",
              "ClassificationModel": "ultralytics.nn.tasks", "Classify": "ultralytics.nn.modules.head"}
-_REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv")})
+_REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "SCConv", "SRU", "CRU", "GroupBatchnorm2d", "PConv", "GhostConv",
+                                                              "DWConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
-                                                               "PconvBottleneck")})
+                                                               "PconvBottleneck", "GhostBottleneck", "C3", "C3Ghost")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
@@ -239,6 +240,7 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "PConv": ("dim_conv3", "dim_untouched"), "FasterC2f_N": ("c",), "FasterC2f": ("c",), "PconvBottleneck_n": ("add",),
               "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr"),
               "Pose": ("nc", "nl", "reg_max", "no", "stride", "kpt_shape", "nk"),
+              "GhostConv": (), "DWConv": (), "GhostBottleneck": (), "C3": (), "C3Ghost": (),
               "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}

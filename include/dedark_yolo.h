@@ -189,6 +189,36 @@ int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, const
  * (>= 9*c3*c3 floats; more allows more chunks), summed in chunk order by a second launch; no atomics */
 int dy_pconv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw, int N, int H, int W, int c3, float* scratch,
                    int64_t scratch_elems, int dtype, void* stream);
+/* ------------------------------------------------------------------------------------ depthwise convolution (Ghost family)
+ * Replaces nn.Conv2d(c, c, k, s, k // 2, groups = c, bias = False) inside DWConv (U/nn/modules/conv.py:95-99), GhostConv's cv2
+ * (conv.py:142-154: cat(y, cv2(y)) with a 5x5 depthwise cv2) and GhostBottleneck's stride-2 stages (U/nn/modules/block.py:535-550), and
+ * its autograd backward.  Channel multiplier 1, k in {3, 5, 7}, stride 1 or 2, pad = k / 2, dilation 1.  Views are NHWC with their own
+ * pixel strides; x / dx are [N,H,W,C], y / dz are [N,Ho,Wo,C] with Ho = (H + 2 * (k / 2) - k) / stride + 1.  C >= 1 needs no vector
+ * padding and no alignment beyond the element size: only lanes [0, C) of a pixel are read or written, so the views may be sibling
+ * channel slices of one buffer (GhostConv's two halves) with live neighbours.  16-byte accesses are taken where every pointer, pixel
+ * stride and C allow, 8-byte ones where only those allow, single elements otherwise.  w / dw: f32 [C][1][k][k] (the state_dict layout).
+ * csrc/conv_route.h and dy_conv_desc are not involved. */
+/* forward, two exclusive modes on the f32 accumulator:
+ *   stats == NULL: y = act(acc * scale[c] + shift[c]) (scale NULL = 1, shift NULL = 0): eval with folded BatchNorm, or bias only;
+ *   stats != NULL: y = raw acc (scale, shift NULL, act NONE) and (sum, sum of squares) of the accumulators are added per channel c to
+ *                  stats[replica][c] / stats[replica][stats_c + c] of the zeroed double stats[DY_STATS_REPLICAS][2 * stats_c] that
+ *                  dy_conv2d_fwd fills (stats_c >= C: the row width of the caller's padded buffer); dy_bn_finalize_valid,
+ *                  dy_bn_act_fwd and dy_bn_act_bwd* then run unchanged. */
+int dy_dwconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* w, int N, int H, int W, int C, int k, int stride,
+                  const float* scale, const float* shift, int act, double* stats, int stats_c, int dtype, void* stream);
+/* data gradient, gather form (no atomics): dx[n,iy,ix,c] = [dx +] sum over taps with (iy + pad - ky) % stride == 0 and
+ * (ix + pad - kx) % stride == 0 and both quotients in range of dz[n, (iy+pad-ky)/stride, (ix+pad-kx)/stride, c] * w[c,ky,kx] [+ add_src];
+ * accumulate / add_src (optional view of dx's shape) as in dy_pconv_dgrad. */
+int dy_dwconv_dgrad(const void* dz, int64_t dz_ld, void* dx, int64_t dx_ld, const float* w, int N, int H, int W, int C, int k, int stride,
+                    int accumulate, const void* add_src, int64_t add_ld, int dtype, void* stream);
+/* dw[c,ky,kx] = sum_{n,oy,ox} dz[n,oy,ox,c] * x[n, oy*stride - pad + ky, ox*stride - pad + kx, c] (overwrite), f32.  Deterministic:
+ * per-block partials in `scratch` (>= C*k*k floats; more allows more blocks), summed in block order by a second launch; no atomics */
+int dy_dwconv_wgrad(const void* x, int64_t x_ld, const void* dz, int64_t dz_ld, float* dw, int N, int H, int W, int C, int k, int stride,
+                    float* scratch, int64_t scratch_elems, int dtype, void* stream);
+/* dy_copy2d for views that are not whole aligned vectors: exactly lanes [0, C) of `pixels` pixels, any C >= 1, element alignment
+ * (how a half of GhostConv's buffer is filled from / read into a vector-padded temporary when its width is not a vector multiple) */
+int dy_copy2d_exact(const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int64_t pixels, int C, int accumulate, int dtype,
+                    void* stream);
 /* ASFF blend (block.py:103-111): w = softmax(logits[.,3]); out = sum_i w_i * x_i */
 int dy_asff_fuse_fwd(const void* x0, int64_t ld0, const void* x1, int64_t ld1, const void* x2, int64_t ld2,
                      const void* logits, int64_t ldl, void* out, int64_t ldo, int64_t pixels, int C, int dtype, void* stream);
