@@ -7,6 +7,7 @@ legal input/output ("view" = pointer + pixel stride), which is how C2f / SPPF / 
 import ctypes as C
 import math
 import os
+import weakref
 
 import torch
 
@@ -158,6 +159,21 @@ def padded_channels(t):
     return Cp
 
 
+def vec_ok(t):
+    """may the vectorised entries (dy_bn_act_*, dy_copy2d, the tiled convs) take view `t` as it is?  Whole 16-byte vectors: C a
+    vector multiple, 16-byte aligned pointer and pixel stride.  A half of GhostConv's buffer whose width is 4 / 12 / 20 channels in a
+    16-bit dtype is not; the depthwise kernels and copy_exact take it anyway."""
+    return t.shape[1] % vec_elems(t.dtype) == 0 and t.data_ptr() % 16 == 0 and (ld_of(t) * t.element_size()) % 16 == 0
+
+
+def copy_exact(src, dst, accumulate=False):
+    """dst[:, :C] (+)= src[:, :C] touching exactly C lanes per pixel (dy_copy2d_exact), for views that are not vec_ok"""
+    B, Cc, H, W = src.shape
+    if tuple(dst.shape) != (B, Cc, H, W) or dst.dtype != src.dtype:
+        raise RuntimeError("copy_exact: views differ in shape or dtype")
+    call("dy_copy2d_exact", ptr(src), ld_of(src), ptr(dst), ld_of(dst), B * H * W, Cc, 1 if accumulate else 0, dt_id(src.dtype), stream())
+
+
 # ------------------------------------------------------------------------------------------------ scratch arena
 class _Arena:
     """Zero-initialised double scratch for per-channel statistics; one fill per step instead of one per conv.
@@ -224,6 +240,13 @@ arena = _Arena()
 
 
 # ------------------------------------------------------------------------------------------------ weights
+def _w32(weight):
+    w = weight.detach()
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    return w
+
+
 def _pack(weight, cout_pad, cin_pad, transposed, dtype):
     key = (cout_pad, cin_pad, transposed, dtype)
     cache = weight.__dict__.setdefault("_dy_pack", {})
@@ -236,9 +259,7 @@ def _pack(weight, cout_pad, cin_pad, transposed, dtype):
         global _pack_generation
         _pack_generation += 1                  # a new packed copy exists: PackPlan must re-collect
     out = hit[1] if hit is not None else torch.empty(cout_pad * KH * KW * cin_pad, dtype=dtype, device=weight.device)
-    w32 = weight.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():
-        w32 = w32.float().contiguous()
+    w32 = _w32(weight)
     call("dy_pack_weight", ptr(w32), ptr(out), Co, cout_pad, Ci, cin_pad, KH, KW, 1 if transposed else 0, dt_id(dtype), stream())
     cache[key] = (tag, out)
     return out
@@ -248,7 +269,6 @@ _extra_pack_views = []      # weakrefs of persistent weight VIEWS (fully connect
 
 
 def register_pack_view(t):
-    import weakref
     _extra_pack_views.append(weakref.ref(t))
 
 
@@ -260,7 +280,9 @@ class PackPlan:
         self.sig = None
         self.table = None
         self.n_blocks = 0
-        self.entries = []
+        self._ent_key = None       # (id(model), _pack_generation) that _ent / _ent_sig were collected for
+        self._ent = []
+        self._ent_sig = ()
 
     def _collect(self, model):
         ent = []
@@ -277,7 +299,7 @@ class PackPlan:
         # the entry list only changes when _pack() creates a new packed copy (first use of a layout) or the parameters move:
         # walking model.parameters() and rebuilding the signature cost ~1 ms of host time per step
         key = (id(model), _pack_generation)
-        if key != getattr(self, "_ent_key", None):
+        if key != self._ent_key:
             self._ent = self._collect(model)
             self._ent_sig = tuple((w.data_ptr(), out.data_ptr(), k) for w, k, out in self._ent)
             self._ent_key = key
@@ -368,6 +390,34 @@ def flush_bn_counters():
     _bn_pending.clear()
 
 
+def _conv_meta(Cin, Cout, KH, KW, stride, B, H, W, pixels, note=""):
+    """shape string and flops of a conv as keywords of _C.set_meta.  Formatting costs: only behind the `_C._prof is not None` guard."""
+    return dict(shape=f"{Cin}->{Cout} k{KH} s{stride} in {B}x{H}x{W}{note}", flops=2.0 * pixels * Cout * KH * KW * Cin)
+
+
+def _bn_train_begin(bn, C, dev):
+    """Bookkeeping of one training-mode BatchNorm forward; returns the [4, C] f32 buffer `aff` (rows scale, shift, mean, invstd)
+    that the finalize kernel fills and the backward pass reads."""
+    _bn_pending[bn] = _bn_pending.get(bn, 0) + 1
+    bn.__dict__.pop("_dy_fold", None)          # the kernels rewrite the running statistics through raw pointers
+    return torch.empty((4, C), dtype=torch.float32, device=dev)
+
+
+def _bn_train_tail(z, stats, bn, act, residual, y, pixels, C, C_valid, did, st):
+    """y = act(bn(z)) [+ residual] from the raw conv output z and its batch sums `stats`: dy_bn_finalize_valid (batch statistics ->
+    aff, running buffers) + dy_bn_act_fwd.  z / y: whole-vector NHWC views of C channels, C_valid of them real.  Returns aff."""
+    aff = _bn_train_begin(bn, C, z.device)
+    pa, sa = aff.data_ptr(), 4 * C
+    call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+         float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, C, C_valid, st)
+    rp, rld = (residual.data_ptr(), ld_of(residual)) if residual is not None else (None, 0)
+    _C._prof is not None and _C.set_meta(kind="bn_act_fwd", shape=f"{C}ch {y.shape[0]}x{y.shape[2]}x{y.shape[3]}", dtype=str(z.dtype), flops=0.0,
+                                         bytes=float(pixels * C * z.element_size() * (3 if residual is not None else 2)))
+    call("dy_bn_act_fwd", ptr(z), ld_of(z), pa, pa + sa, act, rp, rld, ptr(y), ld_of(y), pixels, C, did, st)
+    emu_round(y)
+    return aff
+
+
 def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pad=0, dil=1, training=False, out=None,
                  residual=None, owner=None, shared=False):
     """y = act(bn(conv(x) [+ bias])) [+ residual].  x: NHWC view; returns an NHWC view (into `out` when given).
@@ -403,30 +453,22 @@ def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pa
         stats = arena.alloc(2 * cout_pad * _C.STATS_REPLICAS, dev)
         d = _conv_desc(x, wp, z, B, H, W, cin_pad, Ho, Wo, cout_pad, KH, KW, stride, pad, dil, None, None, ACT_NONE, stats,
                        False, dtype)
-        aff = torch.empty((4, cout_pad), dtype=torch.float32, device=dev)     # scale, shift, mean, invstd
-        pa, sa = aff.data_ptr(), 4 * cout_pad
         pixels = B * Ho * Wo
-        _bn_pending[bn] = _bn_pending.get(bn, 0) + 1
-        bn.__dict__.pop("_dy_fold", None)          # the kernels below rewrite the running statistics through raw pointers
         y = out if out is not None else empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
         st = stream()
-        rp, rld = (residual.data_ptr(), ld_of(residual)) if residual is not None else (None, 0)
-        bp = bn._parameters
         if _C._prof is None and _emulate_storage is None:
             # conv (raw z + statistics) -> finalize -> affine/activation/residual: three launches, ONE foreign call
+            aff = _bn_train_begin(bn, cout_pad, dev)
+            rp, rld = (residual.data_ptr(), ld_of(residual)) if residual is not None else (None, 0)
+            bp = bn._parameters
             call("dy_conv2d_bn_act_fwd_valid", C.byref(d), pixels, ptr(bp["weight"]), ptr(bp["bias"]), ptr(bn.running_mean), ptr(bn.running_var),
-                 float(bn.momentum), float(bn.eps), pa, act, rp, rld, y.data_ptr(), ld_of(y), Cout, st)
+                 float(bn.momentum), float(bn.eps), aff.data_ptr(), act, rp, rld, y.data_ptr(), ld_of(y), Cout, st)
         else:                               # per-entry timing (bench.py roofline leg, tools/layer_profile.py)
-            _C.set_meta(kind="conv_fwd", shape=f"{Cin}->{Cout} k{KH} s{stride} in {B}x{H}x{W}", dtype=str(dtype), flops=2.0 * pixels * Cout * KH * KW * Cin,
-                        bytes=float((B * H * W * Cin + pixels * Cout + Cout * KH * KW * Cin) * x.element_size()))
+            _C._prof is not None and _C.set_meta(kind="conv_fwd", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, stride, B, H, W, pixels),
+                                                 bytes=float((B * H * W * Cin + pixels * Cout + Cout * KH * KW * Cin) * x.element_size()))
             call("dy_conv2d_fwd", C.byref(d), st)
             emu_round(z)                    # (the statistics come from the f32 accumulators in every dtype)
-            call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                 ptr(bn.running_var), float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cout_pad, Cout, st)
-            _C.set_meta(kind="bn_act_fwd", shape=f"{cout_pad}ch {B}x{Ho}x{Wo}", dtype=str(dtype), flops=0.0,
-                        bytes=float(pixels * cout_pad * x.element_size() * (3 if residual is not None else 2)))
-            call("dy_bn_act_fwd", ptr(z), ld_of(z), pa, pa + sa, act, rp, rld, ptr(y), ld_of(y), pixels, cout_pad, dt_id(dtype), st)
-            emu_round(y)
+            aff = _bn_train_tail(z, stats, bn, act, residual, y, pixels, cout_pad, Cout, dt_id(dtype), st)
         if ctx is not None:
             ctx.z, ctx.aff, ctx.y = z, aff, None
     else:
@@ -439,8 +481,8 @@ def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pa
         y = out if (out is not None and direct) else empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
         d = _conv_desc(x, wp, y, B, H, W, cin_pad, Ho, Wo, cout_pad, KH, KW, stride, pad, dil, scale, shift, act, None, False,
                        dtype)
-        _C._prof is not None and _C.set_meta(kind="conv_fwd", shape=f"{Cin}->{Cout} k{KH} s{stride} in {B}x{H}x{W}", dtype=str(dtype), flops=2.0 * B * Ho * Wo * Cout * KH * KW * Cin,
-                    bytes=float((B * H * W * Cin + B * Ho * Wo * Cout + Cout * KH * KW * Cin) * x.element_size()))
+        _C._prof is not None and _C.set_meta(kind="conv_fwd", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, stride, B, H, W, B * Ho * Wo),
+                                             bytes=float((B * H * W * Cin + B * Ho * Wo * Cout + Cout * KH * KW * Cin) * x.element_size()))
         call("dy_conv2d_fwd", C.byref(d), stream())
         if not direct:                  # eval-time residual: y_out = y + residual
             tgt = out if out is not None else y
@@ -523,7 +565,7 @@ def wgrad_side_stream(device=None):
     return s.stream
 
 
-def _side_wait_main(side=None):
+def _side_wait_main():
     """side stream waits for everything issued so far on the current (compute) stream."""
     call("dy_stream_fork", stream(), _wg_side.raw)
 
@@ -588,6 +630,66 @@ def _grad_dst(p):
     return None
 
 
+def _grad_sink(p, shape, dev, shared=False):
+    """(f32 tensor a kernel writes p's gradient into, whether that is p's own .grad slot).  Direct placement needs a trainable p
+    that the trainer marked (_grad_dst) and is not `shared`: a parameter used more than once per step (MFRU) goes through
+    tape.pgrads, which adds the uses up.  A result that is not direct is handed over with _add_pgrad."""
+    gd = None if shared else _grad_dst(p)
+    if gd is not None:
+        return gd, True
+    return torch.empty(shape, dtype=torch.float32, device=dev), False
+
+
+def _bn_backward(tape, dy, z, aff, bn, act, dz, pixels, C, C_valid, did, st, dev, shared):
+    """dz = gradient wrt the raw conv output z of y = act(bn(z)), from dy, plus dgamma / dbeta (C_valid entries each).  dy / z /
+    dz: whole-vector NHWC views of C channels.  One merged foreign call; the split reduce + apply entries while profiling."""
+    sums = arena.alloc(2 * C * _C.BN_BWD_REPLICAS, dev)
+    pa = aff.data_ptr()                                                     # rows of aff: scale, shift, mean, invstd
+    # dgamma / dbeta go direct only when both can; otherwise both through one [2, C_valid] temporary
+    gb_ = None if shared else _grad_dst(bn.bias)
+    gw_, direct = _grad_sink(bn.weight, (2, C_valid), dev, gb_ is None)
+    if not direct:
+        gw_, gb_ = gw_[0], gw_[1]
+    if _C._prof is None or _emulate_storage is not None:
+        call("dy_bn_act_bwd_valid", dy.data_ptr(), ld_of(dy), z.data_ptr(), ld_of(z), pa, ptr(bn._parameters["weight"]), act,
+             sums.data_ptr(), dz.data_ptr(), ld_of(dz), gw_.data_ptr(), gb_.data_ptr(), pixels, C, C_valid, did, st)
+    else:
+        sa, nb = 4 * C, float(pixels * C * dy.element_size())
+        _C.set_meta(kind="bn_act_bwd_reduce", shape=f"{C}ch {pixels}px", dtype=str(dy.dtype), flops=0.0, bytes=nb * 2)
+        call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
+             act, 1, ptr(sums), pixels, C, did, st)
+        _C.set_meta(kind="bn_act_bwd_apply", shape=f"{C}ch {pixels}px", dtype=str(dy.dtype), flops=0.0, bytes=nb * 3)
+        call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
+             ptr(bn.weight), act, 1, ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, C, C_valid, did, st)
+    emu_round(dz)
+    if not direct:
+        _add_pgrad(tape, bn.weight, gw_)
+        _add_pgrad(tape, bn.bias, gb_)
+
+
+def _act_backward(tape, dy, y, bias, act, dz, pixels, C, C_valid, did, st, dev, shared):
+    """Backward of y = act(z + bias) without BatchNorm: dz from dy (the caller passes dz = dy for ACT_NONE, where only the bias
+    gradient is left to compute: 0 pixels), and dbias.  dy / y / dz: whole-vector NHWC views of C channels."""
+    need_bias = bias is not None and bias.requires_grad
+    if dz is dy and not need_bias:
+        return
+    sums = arena.alloc(2 * C * _C.BN_BWD_REPLICAS, dev)
+    pdy, ldy, py, ly = dy.data_ptr(), ld_of(dy), y.data_ptr(), ld_of(y)
+    call("dy_bn_act_bwd_reduce", pdy, ldy, py, ly, None, None, None, None, act, 0, ptr(sums), pixels, C, did, st)
+    db, direct = _grad_sink(bias, C, dev, shared or C != C_valid)         # (a padded dbias never goes straight into bias.grad)
+    pdz, ldz, n = (pdy, ldy, 0) if dz is dy else (dz.data_ptr(), ld_of(dz), pixels)                  # 0 pixels: only dbias
+    call("dy_bn_act_bwd_apply_valid", pdy, ldy, py, ly, None, None, None, None, None, act, 0, ptr(sums), pdz, ldz, None, ptr(db),
+         n, C, C_valid, did, st)
+    if dz is not dy:
+        emu_round(dz)
+    if need_bias and not direct:
+        gd = None if shared else _grad_dst(bias)
+        if gd is not None:
+            gd.copy_(db[:C_valid])
+        else:
+            _add_pgrad(tape, bias, db[:C_valid])
+
+
 def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src=None):
     """Backward of the matching conv_forward (pops its context). dy: NHWC view of the gradient wrt the conv's output
     (for a residual conv the caller routes dy to the residual branch itself). Returns dx (NHWC view) or None.
@@ -607,63 +709,16 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
     pixels = B * Ho * Wo
     did = dt_id(dtype)
     st = stream()
-    _grad_dst = (lambda p: None) if getattr(ctx, "shared", False) else globals()["_grad_dst"]
     if ctx.has_bn:
-        aff, z, bn = ctx.aff, ctx.z, ctx.bn
-        sums = arena.alloc(2 * cout_pad * _C.BN_BWD_REPLICAS, dev)
-        pa, sa = aff.data_ptr(), 4 * cout_pad                               # rows of aff: scale, shift, mean, invstd
         dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
-        gw_, gb_ = _grad_dst(bn.weight), _grad_dst(bn.bias)
-        # (the kernels write Cout entries of dgamma / dbeta, also when the views are padded to cout_pad channels)
-        direct = gw_ is not None and gb_ is not None
-        if not direct:
-            dgb = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-            gw_, gb_ = dgb[0], dgb[1]
-        if _C._prof is None or _emulate_storage is not None:
-            call("dy_bn_act_bwd_valid", dy.data_ptr(), ld_of(dy), z.data_ptr(), ld_of(z), pa, ptr(bn._parameters["weight"]), ctx.act,
-                 sums.data_ptr(), dz.data_ptr(), ld_of(dz), gw_.data_ptr(), gb_.data_ptr(), pixels, cout_pad, Cout, did, st)
-        else:
-            _C.set_meta(kind="bn_act_bwd_reduce", shape=f"{cout_pad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cout_pad * x.element_size() * 2))
-            call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
-                 ctx.act, 1, ptr(sums), pixels, cout_pad, did, st)
-            _C.set_meta(kind="bn_act_bwd_apply", shape=f"{cout_pad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cout_pad * x.element_size() * 3))
-            call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(z), ld_of(z), pa, pa + sa, pa + 2 * sa, pa + 3 * sa,
-                 ptr(bn.weight), ctx.act, 1, ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cout_pad, Cout, did, st)
-        emu_round(dz)
-        if not direct:
-            _add_pgrad(tape, bn.weight, gw_)
-            _add_pgrad(tape, bn.bias, gb_)
+        _bn_backward(tape, dy, ctx.z, ctx.aff, ctx.bn, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
     else:
-        y = ctx.y
-        need_bias = ctx.bias is not None and ctx.bias.requires_grad
-        if ctx.act == ACT_NONE and not need_bias:
-            dz = dy
-        else:
-            sums = arena.alloc(2 * cout_pad * _C.BN_BWD_REPLICAS, dev)
-            call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, ctx.act, 0, ptr(sums),
-                 pixels, cout_pad, did, st)
-            gb_ = _grad_dst(ctx.bias) if (need_bias and cout_pad == Cout) else None
-            db = gb_ if gb_ is not None else torch.empty(cout_pad, dtype=torch.float32, device=dev)
-            if ctx.act == ACT_NONE:
-                dz = dy
-                call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
-                     ptr(sums), ptr(dy), ld_of(dy), None, ptr(db), 0, cout_pad, Cout, did, st)      # 0 pixels: only dbias
-            else:
-                dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
-                call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0,
-                     ptr(sums), ptr(dz), ld_of(dz), None, ptr(db), pixels, cout_pad, Cout, did, st)
-                emu_round(dz)
-            if need_bias and gb_ is None:
-                gd = _grad_dst(ctx.bias)
-                if gd is not None:
-                    gd.copy_(db[:Cout])
-                else:
-                    _add_pgrad(tape, ctx.bias, db[:Cout])
+        dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev) if ctx.act != ACT_NONE else dy
+        _act_backward(tape, dy, ctx.y, ctx.bias, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
     # weight gradient
     if ctx.owner.requires_grad:
-        gd = _grad_dst(ctx.owner)
-        gw = gd if gd is not None else torch.empty(ctx.weight.shape, dtype=torch.float32, device=dev)
-        side = wgrad_side_stream(dev) if gd is not None else None
+        gw, direct = _grad_sink(ctx.owner, ctx.weight.shape, dev, ctx.shared)
+        side = wgrad_side_stream(dev) if direct else None
         st_w = st
         if side is not None:
             if _C._prof is not None:
@@ -676,7 +731,7 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
                     pass
             st_w = side.cuda_stream
         scratch = wgrad_scratch(dev, tag=st_w)         # one workspace per launch stream: Detect's levels may run their wgrads side by side
-        _C._prof is not None and _C.set_meta(kind="conv_wgrad", shape=f"{Cin}->{Cout} k{KH} s{ctx.stride} in {B}x{H}x{W}", dtype=str(dtype), flops=2.0 * pixels * Cout * KH * KW * Cin,
+        _C._prof is not None and _C.set_meta(kind="conv_wgrad", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, ctx.stride, B, H, W, pixels),
                     bytes=float((B * H * W * Cin + pixels * Cout) * x.element_size() + Cout * KH * KW * Cin * 4))
         wargs = (ptr(x), ld_of(x), B, H, W, cin_pad, ptr(dz), ld_of(dz), Ho, Wo, cout_pad, KH, KW, ctx.stride, ctx.pad, ctx.dil, Cout, Cin,
                  ptr(scratch), scratch.numel(), ptr(gw), did)
@@ -689,7 +744,7 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
             call("dy_conv2d_wgrad", *wargs, st_w)
         if side is not None:
             _wg_track(x, dz)
-        if gd is None:
+        if not direct:
             _add_pgrad(tape, ctx.owner, gw.view(ctx.owner.shape))
     if not need_dx:
         return None
@@ -704,8 +759,8 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
                        None, False, dtype)
         d.dst_valid_channels = Cin
         d.dst_planar = dxp.data_ptr()
-        _C._prof is not None and _C.set_meta(kind="conv_dgrad", shape=f"{Cin}->{Cout} k{KH} s{ctx.stride} in {B}x{H}x{W} (planar)", dtype=str(dtype),
-                    flops=2.0 * pixels * Cout * KH * KW * Cin, bytes=float((B * H * W * Cin + pixels * Cout) * x.element_size()))
+        _C._prof is not None and _C.set_meta(kind="conv_dgrad", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, ctx.stride, B, H, W, pixels, " (planar)"),
+                    bytes=float((B * H * W * Cin + pixels * Cout) * x.element_size()))
         call("dy_conv2d_dgrad", C.byref(d), st)
         return dxp
     if dx_out is None:
@@ -722,7 +777,7 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
         if tuple(add_src.shape) != (B, Cin, H, W) or add_src.dtype != dtype or padded_channels(add_src) != cin_pad:
             raise RuntimeError("conv_backward: add_src must be an NHWC view of dx's shape and dtype")
         d.add_src, d.add_src_ld = add_src.data_ptr(), ld_of(add_src)
-    _C._prof is not None and _C.set_meta(kind="conv_dgrad", shape=f"{Cin}->{Cout} k{KH} s{ctx.stride} in {B}x{H}x{W}", dtype=str(dtype), flops=2.0 * pixels * Cout * KH * KW * Cin,
+    _C._prof is not None and _C.set_meta(kind="conv_dgrad", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, ctx.stride, B, H, W, pixels),
                 bytes=float((B * H * W * Cin * (2 if accumulate else 1) + pixels * Cout + Cout * KH * KW * Cin) * x.element_size()))
     call("dy_conv2d_dgrad", C.byref(d), st)
     emu_round(dxb)
@@ -765,9 +820,7 @@ def pconv_forward(tape, x, weight, out=None):
     if tuple(weight.shape) != (c3, c3, 3, 3) or c3 > Cc:
         raise RuntimeError(f"pconv: weight {tuple(weight.shape)} does not fit {Cc} channels")
     y = out if out is not None else _nhwc_like(B, Cc, H, W, x.dtype, x.device)
-    w32 = weight.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():
-        w32 = w32.float().contiguous()
+    w32 = _w32(weight)
     es = x.element_size()
     _C._prof is not None and _C.set_meta(kind="pconv_fwd", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(x.dtype),
                                          flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(2 * B * H * W * Cc * es + 9 * c3 * c3 * 4))
@@ -790,13 +843,12 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
     if tuple(dy.shape) != (B, Cc, H, W) or dy.dtype != dtype:
         raise RuntimeError("pconv_backward: gradient does not match the forward's output")
     if weight.requires_grad:
-        gd = _grad_dst(weight)
-        gw = gd if gd is not None else torch.empty(weight.shape, dtype=torch.float32, device=dev)
+        gw, direct = _grad_sink(weight, weight.shape, dev)
         scratch = wgrad_scratch(dev, tag=st)
         _C._prof is not None and _C.set_meta(kind="pconv_wgrad", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(dtype),
                                              flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(2 * B * H * W * c3 * es + 9 * c3 * c3 * 4))
         call("dy_pconv_wgrad", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(gw), B, H, W, c3, ptr(scratch), scratch.numel(), dt_id(dtype), st)
-        if gd is None:
+        if not direct:
             _add_pgrad(tape, weight, gw)
     if dx_out is None:
         dx, accumulate = _nhwc_like(B, Cc, H, W, dtype, dev), False
@@ -804,9 +856,7 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
         dx = dx_out
     if add_src is not None and (tuple(add_src.shape) != (B, Cc, H, W) or add_src.dtype != dtype):
         raise RuntimeError("pconv_backward: add_src must be an NHWC view of dx's shape and dtype")
-    w32 = weight.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():
-        w32 = w32.float().contiguous()
+    w32 = _w32(weight)
     n_rw = 2 + (1 if accumulate else 0) + (1 if add_src is not None else 0)
     _C._prof is not None and _C.set_meta(kind="pconv_dgrad", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(dtype),
                                          flops=2.0 * B * H * W * c3 * 9 * c3, bytes=float(n_rw * B * H * W * Cc * es + 9 * c3 * c3 * 4))
@@ -818,32 +868,6 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
 
 
 # ------------------------------------------------------------------------------------------------ depthwise conv
-def vec_ok(t):
-    """may the vectorised entries (dy_bn_act_*, dy_copy2d, the tiled convs) take view `t` as it is?  Whole 16-byte vectors: C a
-    vector multiple, 16-byte aligned pointer and pixel stride.  A half of GhostConv's buffer whose width is 4 / 12 / 20 channels in a
-    16-bit dtype is not; the depthwise kernels and copy_exact take it anyway."""
-    return t.shape[1] % vec_elems(t.dtype) == 0 and t.data_ptr() % 16 == 0 and (ld_of(t) * t.element_size()) % 16 == 0
-
-
-def copy_exact(src, dst, accumulate=False):
-    """dst[:, :C] (+)= src[:, :C] touching exactly C lanes per pixel (dy_copy2d_exact), for views that are not vec_ok"""
-    B, Cc, H, W = src.shape
-    if tuple(dst.shape) != (B, Cc, H, W) or dst.dtype != src.dtype:
-        raise RuntimeError("copy_exact: views differ in shape or dtype")
-    call("dy_copy2d_exact", ptr(src), ld_of(src), ptr(dst), ld_of(dst), B * H * W, Cc, 1 if accumulate else 0, dt_id(src.dtype), stream())
-
-
-def _w32(weight):
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        w = w.float().contiguous()
-    return w
-
-
-class DwCtx:
-    __slots__ = ("x", "z", "aff", "weight", "bias", "bn", "act", "k", "stride", "y")
-
-
 def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
     """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.
     x / out: NHWC views of C channels that need not be vector multiples or aligned (exact lanes).
@@ -867,29 +891,20 @@ def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, 
     has_bn = bn is not None
     ctx = None
     if tape is not None:
-        ctx = DwCtx()
+        ctx = ConvCtx()
         ctx.x, ctx.weight, ctx.bias, ctx.bn, ctx.act, ctx.k, ctx.stride = x, weight, bias, bn, act, k, stride
     flops, nbytes = 2.0 * pixels * Cc * k * k, float((B * H * W + pixels) * Cc * es + Cc * k * k * 4)
     shape = f"dw {Cc} k{k} s{stride} in {B}x{H}x{W}"
     if has_bn and training:
         z = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
         stats = arena.alloc(2 * cpad * _C.STATS_REPLICAS, dev)
-        aff = torch.empty((4, cpad), dtype=torch.float32, device=dev)     # scale, shift, mean, invstd
-        pa, sa = aff.data_ptr(), 4 * cpad
-        _bn_pending[bn] = _bn_pending.get(bn, 0) + 1
-        bn.__dict__.pop("_dy_fold", None)
         _C._prof is not None and _C.set_meta(kind="dwconv_fwd", shape=shape, dtype=str(dtype), flops=flops, bytes=nbytes)
         call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(z), ld_of(z), ptr(w32), B, H, W, Cc, k, stride, None, None, ACT_NONE, ptr(stats), cpad,
              did, st)
         emu_round(z)
-        call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-             float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cpad, Cc, st)
         direct = out is not None and vec_ok(out)
         y = out if direct else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
-        _C._prof is not None and _C.set_meta(kind="bn_act_fwd", shape=f"{cpad}ch {B}x{Ho}x{Wo}", dtype=str(dtype), flops=0.0,
-                                             bytes=float(pixels * cpad * es * 2))
-        call("dy_bn_act_fwd", ptr(z), ld_of(z), pa, pa + sa, act, None, 0, ptr(y), ld_of(y), pixels, cpad, did, st)
-        emu_round(y)
+        aff = _bn_train_tail(z, stats, bn, act, None, y, pixels, cpad, Cc, did, st)
         if out is not None and not direct:
             copy_exact(y, out)
             y = out
@@ -935,21 +950,8 @@ def dwconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_s
         copy_exact(dy, t)
         dy = t
     if ctx.bn is not None:
-        aff, z, bn = ctx.aff, ctx.z, ctx.bn
-        sums = arena.alloc(2 * cpad * _C.BN_BWD_REPLICAS, dev)
         dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
-        gw_, gb_ = _grad_dst(bn.weight), _grad_dst(bn.bias)
-        direct = gw_ is not None and gb_ is not None
-        if not direct:
-            dgb = torch.empty((2, Cc), dtype=torch.float32, device=dev)
-            gw_, gb_ = dgb[0], dgb[1]
-        _C._prof is not None and _C.set_meta(kind="bn_act_bwd", shape=f"{cpad}ch {pixels}px", dtype=str(dtype), flops=0.0, bytes=float(pixels * cpad * es * 5))
-        call("dy_bn_act_bwd_valid", ptr(dy), ld_of(dy), ptr(z), ld_of(z), aff.data_ptr(), ptr(bn._parameters["weight"]), ctx.act,
-             ptr(sums), ptr(dz), ld_of(dz), ptr(gw_), ptr(gb_), pixels, cpad, Cc, did, st)
-        emu_round(dz)
-        if not direct:
-            _add_pgrad(tape, bn.weight, gw_)
-            _add_pgrad(tape, bn.bias, gb_)
+        _bn_backward(tape, dy, ctx.z, ctx.aff, ctx.bn, ctx.act, dz, pixels, cpad, Cc, did, st, dev, False)
     elif ctx.act == ACT_NONE and not need_bias:
         dz = dy
     else:
@@ -958,30 +960,18 @@ def dwconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_s
             t = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
             copy_exact(y, t)
             y = t
-        sums = arena.alloc(2 * cpad * _C.BN_BWD_REPLICAS, dev)
-        call("dy_bn_act_bwd_reduce", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, ctx.act, 0, ptr(sums), pixels, cpad, did, st)
-        db = torch.empty(cpad, dtype=torch.float32, device=dev)
-        dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
-        call("dy_bn_act_bwd_apply_valid", ptr(dy), ld_of(dy), ptr(y), ld_of(y), None, None, None, None, None, ctx.act, 0, ptr(sums),
-             ptr(dz), ld_of(dz), None, ptr(db), pixels, cpad, Cc, did, st)
-        emu_round(dz)
-        if need_bias:
-            gd = _grad_dst(ctx.bias)
-            if gd is not None:
-                gd.copy_(db[:Cc])
-            else:
-                _add_pgrad(tape, ctx.bias, db[:Cc])
+        dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev) if ctx.act != ACT_NONE else dy
+        _act_backward(tape, dy, y, ctx.bias, ctx.act, dz, pixels, cpad, Cc, did, st, dev, False)
     w32 = _w32(ctx.weight)
     shape = f"dw {Cc} k{k} s{stride} in {B}x{H}x{W}"
     flops = 2.0 * pixels * Cc * k * k
     if ctx.weight.requires_grad:
-        gd = _grad_dst(ctx.weight)
-        gw = gd if gd is not None else torch.empty(ctx.weight.shape, dtype=torch.float32, device=dev)
+        gw, direct = _grad_sink(ctx.weight, ctx.weight.shape, dev)
         scratch = wgrad_scratch(dev, tag=st)
         _C._prof is not None and _C.set_meta(kind="dwconv_wgrad", shape=shape, dtype=str(dtype), flops=flops,
                                              bytes=float((B * H * W + pixels) * Cc * es + Cc * k * k * 4))
         call("dy_dwconv_wgrad", ptr(x), ld_of(x), ptr(dz), ld_of(dz), ptr(gw), B, H, W, Cc, k, stride, ptr(scratch), scratch.numel(), did, st)
-        if gd is None:
+        if not direct:
             _add_pgrad(tape, ctx.weight, gw)
     if not need_dx:
         return None
@@ -1229,8 +1219,8 @@ def conv_transpose2x2_forward(tape, x, weight, bias=None):
     y = empty_nhwc(B, c2_pad, 2 * H, 2 * W, dtype, x.device)
     d = _conv_desc(x, wt, y, B, H, W, c1_pad, 2 * H, 2 * W, c2_pad, 2, 2, 2, 0, 1, None, None, ACT_NONE, None, False, dtype)
     d.dst_valid_channels = c2
-    _C._prof is not None and _C.set_meta(kind="convT_fwd", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
-                                         flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + 4 * B * H * W * c2) * x.element_size()))
+    _C._prof is not None and _C.set_meta(kind="convT_fwd", dtype=str(dtype), **_conv_meta(c1, c2, 2, 2, 2, B, H, W, B * H * W),
+                                         bytes=float((B * H * W * c1 + 4 * B * H * W * c2) * x.element_size()))
     call("dy_conv2d_dgrad", C.byref(d), stream())
     if bias is not None:
         call("dy_bias_add", ptr(y), ld_of(y), ptr(bias.detach()), B * 4 * H * W, c2, dt_id(dtype), stream())
@@ -1260,29 +1250,27 @@ def conv_transpose2x2_backward(tape, dy, need_dx=True):
     did = dt_id(dtype)
     pixels = B * 4 * H * W
     if bias is not None and bias.requires_grad:
-        gd = _grad_dst(bias)
-        db = gd if gd is not None else torch.empty(c2, dtype=torch.float32, device=dev)
+        db, direct = _grad_sink(bias, c2, dev)
         scratch = wgrad_scratch(dev, tag=st)
         call("dy_bias_grad", ptr(dy), ld_of(dy), pixels, c2, did, ptr(scratch), scratch.numel(), ptr(db), st)
-        if gd is None:
+        if not direct:
             _add_pgrad(tape, bias, db)
     if weight.requires_grad:
-        gd = _grad_dst(weight)
-        gw = gd if gd is not None else torch.empty(weight.shape, dtype=torch.float32, device=dev)
+        gw, direct = _grad_sink(weight, weight.shape, dev)
         scratch = wgrad_scratch(dev, tag=st)
-        _C._prof is not None and _C.set_meta(kind="convT_wgrad", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
-                                             flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
+        _C._prof is not None and _C.set_meta(kind="convT_wgrad", dtype=str(dtype), **_conv_meta(c1, c2, 2, 2, 2, B, H, W, B * H * W),
+                                             bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
         call("dy_conv2d_wgrad", ptr(dy), ld_of(dy), B, 2 * H, 2 * W, c2_pad, ptr(x), ld_of(x), H, W, c1_pad, 2, 2, 2, 0, 1, c1, c2,
              ptr(scratch), scratch.numel(), ptr(gw), did, st)
-        if gd is None:
+        if not direct:
             _add_pgrad(tape, weight, gw)
     if not need_dx:
         return None
     wp = _pack(weight, c1_pad, c2_pad, False, dtype)
     dx = empty_nhwc(B, c1_pad, H, W, dtype, dev)
     d = _conv_desc(dy, wp, dx, B, 2 * H, 2 * W, c2_pad, H, W, c1_pad, 2, 2, 2, 0, 1, None, None, ACT_NONE, None, False, dtype)
-    _C._prof is not None and _C.set_meta(kind="convT_dgrad", shape=f"{c1}->{c2} k2 s2 in {B}x{H}x{W}", dtype=str(dtype),
-                                         flops=2.0 * B * H * W * c1 * 4 * c2, bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
+    _C._prof is not None and _C.set_meta(kind="convT_dgrad", dtype=str(dtype), **_conv_meta(c1, c2, 2, 2, 2, B, H, W, B * H * W),
+                                         bytes=float((B * H * W * c1 + pixels * c2) * x.element_size()))
     call("dy_conv2d_fwd", C.byref(d), st)
     emu_round(dx)
     return dx if c1_pad == c1 else dx[:, :c1]
