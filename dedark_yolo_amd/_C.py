@@ -138,6 +138,7 @@ _SIGS = {
     "dy_bbox_ciou": [vp, vp, i64, vp, vp, vp],
     "dy_bbox_iou": [vp, vp, i64, i32, i32, f32, vp, vp, vp],
     "dy_aug_resize_u8": [vp, i32, i32, i64, vp, i32, i32, i64, vp],
+    "dy_aug_resize_area_u8": [vp, i32, i32, i64, vp, i32, i32, i64, vp],
     "dy_aug_letterbox": [vp, i32, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp],
     "dy_aug_mosaic_warp": [vp, i32, i32, i32, vp, vp],
     "dy_aug_mosaic_warp_mix": [vp, i32, i32, i32, vp, vp],

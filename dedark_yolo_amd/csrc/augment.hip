@@ -13,6 +13,10 @@
 // oracle/augment.py (OpenCV itself is absent from the image: its algorithms are restated from the published source, parity unpinned).
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
+#include <string.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
 
 // HIP's __fmul_rn / __fsub_rn / __dmul_rn are plain operators on AMD targets: they document the intent; what keeps hipcc from contracting
 // `1 - s * h` or `m1 * y + m2` into a fused multiply-add (one rounding instead of two: off by one level at exact .5 ties) is
@@ -55,6 +59,43 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__
   const ResizeAxis ax = resize_axis(x, sw, dw, true), ay = resize_axis(y, sh, dh, false);
 #pragma unroll
   for (int c = 0; c < 3; ++c) dst[(long)y * dpitch + x * 3 + c] = (uint8_t)resize_px(src, spitch, ax, ay, c);
+}
+
+// ---- cv::resize, INTER_AREA, 8-bit shrink (resize.cpp: computeResizeAreaTab + ResizeArea_Invoker, the scalar code) --------------------
+// The per-axis tables (source index, f32 weight) are built on the host in double (area_axis_table below) and read here; the kernel
+// only accumulates in f32, in table order, multiply and add rounded separately (-ffp-contract=off): buf = sum_x src * ax per source row,
+// sum += buf * by, then saturate_cast<uchar>(cvRound(sum)).  A thread per output pixel; the 64 lanes of a wave are 64 neighbouring
+// output columns, so every tap instruction of the wave reads one contiguous span of 64 * scale source pixels of a row.
+struct AreaTap {
+  int si;
+  float w;
+};
+__global__ __launch_bounds__(256) void resize_area_kernel(const uint8_t* __restrict__ src, long spitch, uint8_t* __restrict__ dst, int dh, int dw,
+                                                          long dpitch, const int* __restrict__ xofs, const AreaTap* __restrict__ xtab,
+                                                          const int* __restrict__ yofs, const AreaTap* __restrict__ ytab) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= dw || y >= dh) return;
+  const int x0 = xofs[x], x1 = xofs[x + 1], y0 = yofs[y], y1 = yofs[y + 1];
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (int j = y0; j < y1; ++j) {
+    const AreaTap ty = ytab[j];
+    const uint8_t* row = src + (long)ty.si * spitch;
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+    for (int k = x0; k < x1; ++k) {
+      const AreaTap tx = xtab[k];
+      const uint8_t* p = row + 3 * tx.si;
+      b0 = __fadd_rn(b0, __fmul_rn((float)p[0], tx.w));
+      b1 = __fadd_rn(b1, __fmul_rn((float)p[1], tx.w));
+      b2 = __fadd_rn(b2, __fmul_rn((float)p[2], tx.w));
+    }
+    s0 = __fadd_rn(s0, __fmul_rn(b0, ty.w));
+    s1 = __fadd_rn(s1, __fmul_rn(b1, ty.w));
+    s2 = __fadd_rn(s2, __fmul_rn(b2, ty.w));
+  }
+  uint8_t* o = dst + (long)y * dpitch + 3 * x;
+  o[0] = (uint8_t)min(max(__float2int_rn(s0), 0), 255);
+  o[1] = (uint8_t)min(max(__float2int_rn(s1), 0), 255);
+  o[2] = (uint8_t)min(max(__float2int_rn(s2), 0), 255);
 }
 
 // LetterBox + Format: resize to (nh, nw), constant border 114 around it, HWC BGR -> CHW RGB
@@ -309,6 +350,68 @@ extern "C" int dy_aug_resize_u8(const uint8_t* src, int sh, int sw, int64_t src_
   DY_CHECK(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0 && src_pitch >= 3L * sw && dst_pitch >= 3L * dw, "dy_aug_resize_u8: bad arguments");
   resize_kernel<<<dim3(dy_cdiv(dw, 64), dy_cdiv(dh, 4)), 256, 0, (hipStream_t)stream>>>(src, sh, sw, src_pitch, dst, dh, dw, dst_pitch);
   DY_LAUNCH_CHECK();
+  return 0;
+}
+
+// computeResizeAreaTab for one axis: entries (source index, weight) of destination index d are tab[ofs[d] .. ofs[d + 1]).  double
+// throughout, each weight rounded once to f32 -- the same expressions as tests/resize_area_ref.py::axis_table.
+static void area_axis_table(int S, int D, std::vector<int>& ofs, std::vector<AreaTap>& tab) {
+  const double scale = (double)S / (double)D;
+  ofs.assign(D + 1, 0);
+  tab.clear();
+  for (int d = 0; d < D; ++d) {
+    ofs[d] = (int)tab.size();
+    const double f1 = d * scale, f2 = f1 + scale, cell = std::min(scale, S - f1);
+    int s1 = (int)std::ceil(f1);
+    const int s2 = std::min((int)std::floor(f2), S - 1);
+    s1 = std::min(s1, s2);
+    if (s1 - f1 > 1e-3) tab.push_back({s1 - 1, (float)((s1 - f1) / cell)});
+    for (int s = s1; s < s2; ++s) tab.push_back({s, (float)(1.0 / cell)});
+    if (f2 - s2 > 1e-3) tab.push_back({s2, (float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)});
+  }
+  ofs[D] = (int)tab.size();
+}
+
+extern "C" int dy_aug_resize_area_u8(const uint8_t* src, int sh, int sw, int64_t src_pitch, uint8_t* dst, int dh, int dw, int64_t dst_pitch,
+                                     void* stream) {
+  DY_CHECK(src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0 && src_pitch >= 3L * sw && dst_pitch >= 3L * dw,
+           "dy_aug_resize_area_u8: bad arguments");
+  DY_CHECK(dh <= sh && dw <= sw, "dy_aug_resize_area_u8: INTER_AREA is the shrinking rule (%dx%d -> %dx%d)", sh, sw, dh, dw);
+  static thread_local std::vector<int> xofs, yofs;
+  static thread_local std::vector<AreaTap> xtab, ytab;
+  static thread_local std::vector<char> packed;                 // [xofs | yofs | xtab | ytab], one copy
+  area_axis_table(sw, dw, xofs, xtab);
+  area_axis_table(sh, dh, yofs, ytab);
+  for (const AreaTap& t : xtab) DY_CHECK(t.si >= 0 && t.si < sw, "dy_aug_resize_area_u8: column table out of range");
+  for (const AreaTap& t : ytab) DY_CHECK(t.si >= 0 && t.si < sh, "dy_aug_resize_area_u8: row table out of range");
+  const size_t b_xofs = xofs.size() * sizeof(int), b_yofs = yofs.size() * sizeof(int), b_xtab = xtab.size() * sizeof(AreaTap),
+               b_ytab = ytab.size() * sizeof(AreaTap), bytes = b_xofs + b_yofs + b_xtab + b_ytab;
+  packed.resize(bytes);
+  memcpy(packed.data(), xofs.data(), b_xofs);
+  memcpy(packed.data() + b_xofs, yofs.data(), b_yofs);
+  memcpy(packed.data() + b_xofs + b_yofs, xtab.data(), b_xtab);
+  memcpy(packed.data() + b_xofs + b_yofs + b_xtab, ytab.data(), b_ytab);
+  hipStream_t s = (hipStream_t)stream;
+  // Stream-ordered: allocated, filled, read and freed on `stream`, whichever device it belongs to.  The source is pageable host
+  // memory, which the runtime stages before hipMemcpyAsync returns, so `packed` may be rewritten by the next call at once.
+  void* dev = nullptr;
+  DY_CHECK(hipMallocAsync(&dev, bytes, s) == hipSuccess, "dy_aug_resize_area_u8: table allocation (%zu bytes)", bytes);
+  const hipError_t e = hipMemcpyAsync(dev, packed.data(), bytes, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) {
+    (void)hipFreeAsync(dev, s);
+    DY_CHECK(false, "dy_aug_resize_area_u8: table upload failed: %s", hipGetErrorString(e));
+  }
+  const int* d_xofs = (const int*)dev;
+  const int* d_yofs = d_xofs + dw + 1;
+  const AreaTap* d_xtab = (const AreaTap*)(d_yofs + dh + 1);
+  const AreaTap* d_ytab = d_xtab + xtab.size();
+  resize_area_kernel<<<dim3(dy_cdiv(dw, 64), dy_cdiv(dh, 4)), 256, 0, s>>>(src, src_pitch, dst, dh, dw, dst_pitch, d_xofs, d_xtab, d_yofs, d_ytab);
+  const hipError_t le = hipGetLastError();
+  (void)hipFreeAsync(dev, s);
+  if (le != hipSuccess) {
+    dy_set_error("dy_aug_resize_area_u8: launch failed: %s", hipGetErrorString(le));
+    return 2;
+  }
   return 0;
 }
 

@@ -439,16 +439,19 @@ def train_labels(plan, labels, shapes, segments=None, keypoints=None, flip_idx=N
     return c, nb
 
 
-def val_labels(bboxes, shape, imgsz, segments=None, keypoints=None):
+def val_labels(bboxes, shape, imgsz, segments=None, keypoints=None, rect_shape=None):
     """LetterBox(scaleup=False)._update_labels + Format for the validation set (augment.py:593-603, 719-733).  Returns (bboxes
     normalised xywh float32, ratio_pad ((r, r), (dw, dh)), geometry).  With `segments` (list of [k, 2] normalised polygons, or the
     resampled [n, 1000, 2] array) or `keypoints` ([n, K, 2 or 3] normalised) a fourth value follows: the int32 [n, 1000, 2] polygons
     polygon2mask hands to cv2.fillPoly (in label order), or the normalised keypoints [n, K, 3]: Instances.denormalize(w, h),
-    scale(r, r), add_padding(dw, dh), then Format's normalize(imgsz, imgsz)."""
+    scale(r, r), add_padding(dw, dh), then Format's normalize(imgsz, imgsz).  `rect_shape` (H, W): the batch shape of a rect
+    validation set (LetterBox pops it in place of its own new_shape, augment.py:563; Format normalises by the letter-boxed image's
+    own width and height)."""
     if segments is not None and keypoints is not None:
         raise ValueError("Can not use both segments and keypoints.")
     h, w = shape
-    geo = letterbox_geometry((h, w), (imgsz, imgsz), scaleup=False)
+    H, W = (imgsz, imgsz) if rect_shape is None else (int(rect_shape[0]), int(rect_shape[1]))
+    geo = letterbox_geometry((h, w), (H, W), scaleup=False)
     b = _xywh2xyxy(np.array(bboxes, dtype=F32, copy=True).reshape(-1, 4))
     _mul(b, w, h)
     _mul(b, geo.r, geo.r)
@@ -457,7 +460,7 @@ def val_labels(bboxes, shape, imgsz, segments=None, keypoints=None):
     b[:, 2] += geo.dw
     b[:, 3] += geo.dh
     b = _xyxy2xywh(b)
-    _mul(b, 1 / imgsz, 1 / imgsz)
+    _mul(b, 1 / W, 1 / H)
     out = (b, ((geo.r, geo.r), (geo.dw, geo.dh)), geo)
     if segments is None and keypoints is None:
         return out
@@ -474,8 +477,8 @@ def val_labels(bboxes, shape, imgsz, segments=None, keypoints=None):
     e[..., 1] += geo.dh
     if segments is not None:
         return out + (e.astype(np.int32),)
-    e[..., 0] /= imgsz
-    e[..., 1] /= imgsz
+    e[..., 0] /= W
+    e[..., 1] /= H
     return out + (e,)
 
 
@@ -505,7 +508,11 @@ class DeviceAugmenter:
             raise RuntimeError("DeviceAugmenter: the pixel pipeline only exists on the device")
         self.imgsz = int(imgsz)
         self.hyp = hyp or AugmentHyp()
-        self.images = [ops.require_gpu(im) if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)).to(self.device) for im in images]
+        self.images = []
+        for im in images:
+            if torch.is_tensor(im):
+                ops.require_gpu(im)
+            self.images.append(im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)).to(self.device))
         for im in self.images:
             if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
                 raise ValueError("DeviceAugmenter: images must be contiguous uint8 HWC with 3 channels")
@@ -726,9 +733,11 @@ def invert_affine(M):
     return m
 
 
-def load_resize(image, imgsz):
-    """BaseDataset.load_image's resize (base.py:152-157, training: INTER_LINEAR) of a decoded uint8 HWC device image: long side -> imgsz.
-    Returns the image itself when the ratio is 1."""
+def load_resize(image, imgsz, augment=True):
+    """BaseDataset.load_image's resize (base.py:152-157) of a decoded uint8 HWC device image: long side -> imgsz, with the reference's
+    `interp = cv2.INTER_LINEAR if (self.augment or r > 1) else cv2.INTER_AREA`: training (augment=True) and every enlargement are
+    linear (dy_aug_resize_u8), a validation image that shrinks goes through dy_aug_resize_area_u8.  Returns the image itself when the
+    ratio is 1."""
     from .._C import call
     from ..ops import ptr, stream
     h0, w0 = int(image.shape[0]), int(image.shape[1])
@@ -737,24 +746,52 @@ def load_resize(image, imgsz):
         return image
     w, h = min(math.ceil(w0 * r), imgsz), min(math.ceil(h0 * r), imgsz)
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=image.device)
-    call("dy_aug_resize_u8", ptr(image), h0, w0, image.stride(0), ptr(out), h, w, out.stride(0), stream())
+    kernel = "dy_aug_resize_u8" if (augment or r > 1) else "dy_aug_resize_area_u8"
+    call(kernel, ptr(image), h0, w0, image.stride(0), ptr(out), h, w, out.stride(0), stream())
     return out
 
 
+def _hw(shape):
+    """an int means a square (h, w)"""
+    return (int(shape), int(shape)) if isinstance(shape, (int, np.integer)) else (int(shape[0]), int(shape[1]))
+
+
 def letterbox_batch(images, imgsz, scaleup=False):
-    """Validation transform: LetterBox(new_shape=(imgsz, imgsz), scaleup) + Format's CHW RGB for a list of decoded uint8 HWC device images
-    -> uint8 [B, 3, imgsz, imgsz] (resize + constant border 114 + channel flip in one launch per image)."""
+    """Validation transform: LetterBox(new_shape, scaleup) + Format's CHW RGB for a list of decoded uint8 HWC device images
+    -> uint8 [B, 3, H, W] (resize + constant border 114 + channel flip in one launch per image).  `imgsz`: an int (square) or the
+    (H, W) of a rect batch (the `rect_shape` LetterBox pops, augment.py:563)."""
     from .._C import call
     from ..ops import ptr, stream
     dev = images[0].device
-    out = torch.empty((len(images), 3, imgsz, imgsz), dtype=torch.uint8, device=dev)
+    H, W = _hw(imgsz)
+    out = torch.empty((len(images), 3, H, W), dtype=torch.uint8, device=dev)
     geos = []
     for k, im in enumerate(images):
         h, w = int(im.shape[0]), int(im.shape[1])
-        g = letterbox_geometry((h, w), (imgsz, imgsz), scaleup)
+        g = letterbox_geometry((h, w), (H, W), scaleup)
         geos.append(g)
-        call("dy_aug_letterbox", ptr(im), h, w, im.stride(0), g.new_unpad[1], g.new_unpad[0], g.top, g.left, imgsz, imgsz, ptr(out[k]), stream())
+        call("dy_aug_letterbox", ptr(im), h, w, im.stride(0), g.new_unpad[1], g.new_unpad[0], g.top, g.left, H, W, ptr(out[k]), stream())
     return out, geos
+
+
+def letterbox_auto(image, imgsz, stride=32):
+    """The predictor's pre_transform for ONE decoded uint8 HWC BGR device image (engine/predictor.py:134-147: LetterBox(imgsz,
+    auto=True, stride), augment.py:566-590): scale the long side to imgsz (scaleup, linear), pad each axis only up to the next
+    multiple of `stride` (np.mod(dw, stride)), centred, border 114 -> uint8 [3, H, W] RGB and the geometry (r, new_unpad, dw, dh,
+    top, left, out_hw)."""
+    from .._C import call
+    from ..ops import ptr, stream
+    h, w = int(image.shape[0]), int(image.shape[1])
+    S = _hw(imgsz)
+    r = min(S[0] / h, S[1] / w)
+    nw, nh = int(round(w * r)), int(round(h * r))
+    dw, dh = (S[1] - nw) % stride, (S[0] - nh) % stride
+    H, W = nh + dh, nw + dw
+    dw, dh = dw / 2, dh / 2
+    top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
+    out = torch.empty((3, H, W), dtype=torch.uint8, device=image.device)
+    call("dy_aug_letterbox", ptr(image), h, w, image.stride(0), nh, nw, top, left, H, W, ptr(out), stream())
+    return out, SimpleNamespace(r=r, new_unpad=(nw, nh), dw=dw, dh=dh, top=top, left=left, out_hw=(H, W))
 
 
 def dark_channel_prior(img):

@@ -5,6 +5,7 @@ reference (ultralytics/data/build.py:72-109, dataset.py:171-188), with the decod
 several times over -- 16.5 k images x ~0.9 MB) keeps them in HBM, so a step reads nothing over PCIe; `resident=False` keeps them in pinned
 host memory and uploads the source images of batch i+1 on a copy stream while step i runs (the PCIe-inclusive mode bench.py reports).
 Either way the augmented pixels are produced on the device by ONE launch per batch (DeviceAugmenter.render)."""
+import math
 import random as _random
 
 import numpy as np
@@ -174,3 +175,133 @@ class _Sparse:
 
     def __getitem__(self, i):
         return self.d[i]
+
+
+# ---------------------------------------------------------------------------------------------------------------- datasets from disk
+def _device_images(decoded, imgsz, device, augment, keep_on_device=True):
+    """decoded uint8 HWC BGR arrays brought to their load_image size on the device (base.py:142-157: linear for training, area for a
+    validation image that shrinks): list of uint8 HWC tensors, on the device or (keep_on_device=False) copied back to the host"""
+    from .augment import load_resize
+    out = []
+    for im in decoded:
+        t = load_resize(torch.from_numpy(im).to(device), imgsz, augment=augment)
+        out.append(t if keep_on_device else t.cpu())
+    return out
+
+
+def _augment_hyp(args):
+    """AugmentHyp from the cfg: every augmentation key the cfg (or a train(**kwargs) override) carries, the reference's defaults else"""
+    return AugmentHyp(**{k: getattr(args, k) for k in vars(AugmentHyp()) if getattr(args, k, None) is not None})
+
+
+def build_train_loader(args, data, task, device="cuda", rank=-1, world_size=1):
+    """The training set of a checked data dict (dataset.check_det_dataset) as a DeviceAugmentLoader: what build_yolo_dataset(mode=
+    'train') + build_dataloader are in the reference (ultralytics/data/build.py:72-109).  Labels are read and verified
+    (dataset.load_split: fraction, single_cls, classes), every image is decoded once and resized on the device to its load_image size
+    (linear: augment=True).  The images stay in HBM unless they would take more than half of the free device memory
+    (torch.cuda.mem_get_info), then in pinned host memory (resident=False); the choice is logged.  world_size > 1: rank r takes the
+    files r::world_size of the sorted list -- a plain shard, not DistributedSampler's per-epoch permutation."""
+    from .dataset import LOGGER, decode_all, load_split, task_labels
+    device = torch.device(device)
+    files, labels, _ = load_split(data, "train", task, args)
+    if world_size > 1:
+        files, labels = files[max(rank, 0)::world_size], labels[max(rank, 0)::world_size]
+    imgsz, workers = int(args.imgsz), getattr(args, "workers", 8)
+    decoded = decode_all(files, workers)
+    need = sum(3 * min(math.ceil(h * imgsz / max(h, w)), imgsz) * min(math.ceil(w * imgsz / max(h, w)), imgsz)
+               for h, w in (im.shape[:2] for im in decoded))
+    free = torch.cuda.mem_get_info(device)[0]
+    resident = need <= free // 2
+    LOGGER.info(f"train: {len(files)} images, {need / 2 ** 20:.1f} MiB at imgsz {imgsz}; {free / 2 ** 20:.0f} MiB of device memory free -> "
+                f"{'resident in device memory' if resident else 'pinned host memory, uploaded per batch'}")
+    images = _device_images(decoded, imgsz, device, augment=True, keep_on_device=resident)
+    return DeviceAugmentLoader(images, task_labels(labels, task), imgsz, int(args.batch), hyp=_augment_hyp(args), device=device,
+                               resident=resident, seed=int(getattr(args, "seed", 0) or 0), task=task, flip_idx=data.get("flip_idx"),
+                               mask_ratio=int(getattr(args, "mask_ratio", 4)), overlap_mask=bool(getattr(args, "overlap_mask", True)))
+
+
+def build_val_loader(args, data, task, device="cuda", split="val", batch=None, stride=32):
+    """`split` of a checked data dict as a DeviceValLoader: build_yolo_dataset(mode='val') -- rect=True, pad=0.5 -- of the reference
+    (ultralytics/data/build.py:72-88; models/yolo/detect/val.py:176-185).  `batch`: the cfg's unless given (the trainer gives 2 x)."""
+    from .dataset import load_split
+    files, labels, _ = load_split(data, split, task, args)
+    return DeviceValLoader(files, labels, int(args.imgsz), int(batch or args.batch), stride=stride, pad=0.5, rect=True, task=task,
+                           device=device, workers=getattr(args, "workers", 8), mask_ratio=int(getattr(args, "mask_ratio", 4)),
+                           overlap_mask=bool(getattr(args, "overlap_mask", True)))
+
+
+class DeviceValLoader:
+    """The reference's validation dataset + dataloader (YOLODataset(augment=False, rect=True, pad=0.5) behind build_dataloader,
+    shuffle off) with the pixels on the device.  `labels`: dataset.read_labels' dicts (with `shape`), `im_files` in the same order.
+      * rect: dataset.set_rectangle orders the images by aspect ratio and gives every batch its own (H_b, W_b);
+      * every image is decoded ONCE, uploaded and resized to its load_image size by load_resize(augment=False) -- dy_aug_resize_area_u8
+        when it shrinks (cv2.INTER_AREA), linear when it grows -- and kept on the device between epochs;
+      * per batch: dy_aug_letterbox to (H_b, W_b), scaleup=False, centred, border 114, CHW RGB; labels through val_labels.
+    Batches follow the reference's collate schema: img uint8 [b, 3, H_b, W_b] (device), batch_idx [N], cls [N, 1], bboxes [N, 4]
+    normalised xywh, im_file, ori_shape (decoded h, w), resized_shape (load_image h, w), ratio_pad = ((h / h0, w / w0), (dw, dh)) as
+    get_image_and_label + LetterBox leave it (base.py:245-246, augment.py:589-590); segment adds `masks` (and cls / bboxes / batch_idx
+    become the device rows in mask order), pose adds `keypoints` [N, K, 3].  The last batch may be smaller."""
+
+    def __init__(self, im_files, labels, imgsz, batch_size, stride=32, pad=0.5, rect=True, task="detect", device="cuda", workers=8,
+                 mask_ratio=4, overlap_mask=True):
+        from .dataset import decode_all, set_rectangle, task_labels
+        if len(im_files) != len(labels) or not labels:
+            raise ValueError("DeviceValLoader: one label dict per image file, at least one")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceValLoader: the pixel pipeline only exists on the device")
+        self.imgsz, self.bs, self.task = int(imgsz), int(batch_size), task
+        self.mask_ratio, self.overlap_mask = int(mask_ratio), bool(overlap_mask)
+        n = len(labels)
+        if rect:
+            order, self.batch, self.batch_shapes = set_rectangle([lab["shape"] for lab in labels], self.bs, self.imgsz, stride, pad)
+        else:
+            order, self.batch = np.arange(n), np.arange(n) // self.bs
+            self.batch_shapes = np.full((int(self.batch[-1]) + 1, 2), self.imgsz)
+        self.order = [int(i) for i in order]
+        self.im_files = [im_files[i] for i in self.order]
+        self.labels = task_labels([labels[i] for i in self.order], task)
+        decoded = decode_all(self.im_files, workers)
+        self.ori_shapes = [(int(im.shape[0]), int(im.shape[1])) for im in decoded]
+        self.images = _device_images(decoded, self.imgsz, self.device, augment=False)
+        self.samples = [self._sample(k) for k in range(n)]
+
+    def __len__(self):
+        return int(self.batch[-1]) + 1
+
+    def _sample(self, k):
+        """label bookkeeping of image k (position in rect order), once: (cls, bboxes, [polygons | keypoints]), ratio_pad"""
+        from .augment import val_labels
+        lab, im = self.labels[k], self.images[k]
+        shape = (int(im.shape[0]), int(im.shape[1]))
+        out = val_labels(lab["bboxes"], shape, self.imgsz, segments=lab.get("segments"), keypoints=lab.get("keypoints"),
+                         rect_shape=tuple(int(v) for v in self.batch_shapes[self.batch[k]]))
+        (h0, w0), geo = self.ori_shapes[k], out[2]
+        meta = dict(resized_shape=shape, ratio_pad=((shape[0] / h0, shape[1] / w0), (geo.dw, geo.dh)))
+        return (np.array(lab["cls"], dtype=np.float32).reshape(-1, 1), out[0]) + tuple(out[3:]), meta
+
+    def __iter__(self):
+        from .augment import collate, letterbox_batch
+        for b in range(len(self)):
+            ks = [k for k in range(len(self.images)) if self.batch[k] == b]
+            H, W = (int(v) for v in self.batch_shapes[b])
+            img, _ = letterbox_batch([self.images[k] for k in ks], (H, W), scaleup=False)
+            lab = [self.samples[k][0] for k in ks]
+            meta = dict(im_file=[self.im_files[k] for k in ks], ori_shape=[self.ori_shapes[k] for k in ks],
+                        resized_shape=[self.samples[k][1]["resized_shape"] for k in ks],
+                        ratio_pad=[self.samples[k][1]["ratio_pad"] for k in ks])
+            if self.task == "segment":
+                if H % self.mask_ratio or W % self.mask_ratio:
+                    raise ValueError("the batch shape must be a multiple of mask_ratio")
+                dev = lambda a: torch.from_numpy(a).to(self.device)
+                rows = dev(pack_rows(lab))
+                masks, rows_sorted, _ = polygon_masks(dev(pack_polygons(lab)), dev(instance_offsets(lab)), rows, len(lab), H, W,
+                                                      self.mask_ratio, self.overlap_mask)
+                rows = rows_sorted if self.overlap_mask else rows
+                yield dict(img=img, batch_idx=rows[:, 0], cls=rows[:, 1:2], bboxes=rows[:, 2:6], masks=masks, **meta)
+                continue
+            bi, cls, bb = collate([l[:2] for l in lab])
+            batch = dict(img=img, batch_idx=bi, cls=cls, bboxes=bb, **meta)
+            if self.task == "pose":
+                batch["keypoints"] = torch.from_numpy(np.concatenate([l[2] for l in lab], 0))
+            yield batch

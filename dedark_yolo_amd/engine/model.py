@@ -102,31 +102,134 @@ class YOLO:
         self.model.fuse()
         return self
 
-    def train(self, loader=None, **kwargs):
-        """model.train(data=..., epochs=..., imgsz=..., batch=..., device=...) -- `loader` is any iterable of reference-schema batch
-        dicts (the cv2 data pipeline is outside the hot path)."""
+    def _attach_data(self, data):
+        """What the reference trainer's get_model / set_model_attributes do with the data dict (models/yolo/detect/train.py:104-121,
+        pose/train.py:33-46): a model whose class count (pose: kpt_shape) differs from the dataset's is rebuilt from its yaml with the
+        dataset's -- tensors that keep their shape are carried over, as a pretrained load does -- then `names` (pose: `kpt_shape`)
+        are attached."""
+        nc, kpt = int(data["nc"]), data.get("kpt_shape")
+        rebuild = nc != int(self.model.yaml["nc"])
+        kw = {}
+        if self.task == "pose" and kpt is not None:
+            kw["data_kpt_shape"] = list(kpt)
+            rebuild = rebuild or list(kpt) != list(self.model.yaml["kpt_shape"])
+        if rebuild:
+            from copy import deepcopy
+            dev = next(self.model.parameters()).device
+            old = self.model
+            self.model = _model_class(self.task)(deepcopy(old.yaml), nc=nc, **kw).to(dev)
+            if getattr(self, "ckpt", None) is not None:
+                self.model.load(old.state_dict())
+        self.model.names = dict(data["names"])
+        if self.task == "pose" and kpt is not None:
+            self.model.kpt_shape = list(kpt)
+
+    def _data_args(self, kwargs):
         ov = dict(self.overrides)
         ov.update(kwargs)
-        self.trainer = DetectionTrainer(get_cfg(ov))
-        if loader is None:
-            raise ValueError("pass loader=<iterable of batch dicts>; dataset decoding/augmentation is outside the hot path")
-        self.trainer.setup(self.model, total_iterations=len(loader) * self.trainer.args.epochs)
-        return self.trainer.train(loader)
+        return get_cfg(ov)
+
+    def train(self, loader=None, save_dir=None, **kwargs):
+        """model.train(data='dataset/data.yaml', epochs=..., imgsz=..., batch=..., ...): the training set of the data yaml through
+        data.build_train_loader (labels read and verified, images decoded once, augmentation on the device) and, with `val: True`, its
+        val split through data.build_val_loader at twice the batch (the reference's trainer does the same) for the per-epoch
+        validation.  Checkpoints are written to `save_dir`, or to project/name when either is given; otherwise nothing is written.
+        `loader=<iterable of reference-schema batch dicts>` instead of `data=` is the path for batches that are already in memory."""
+        args = self._data_args(kwargs)
+        self.trainer = DetectionTrainer(args)
+        if loader is not None:
+            self.trainer.setup(self.model, total_iterations=len(loader) * self.trainer.args.epochs)
+            return self.trainer.train(loader)
+        if not getattr(args, "data", None):
+            raise ValueError("pass data=<path to a data yaml> (the dataset is read from disk) or loader=<iterable of batch dicts>")
+        if self.task == "classify":
+            raise NotImplementedError("the classify task reads one folder per class, not YOLO label files: pass loader=")
+        from ..data import build_train_loader, build_val_loader, check_det_dataset
+        data = check_det_dataset(args.data)
+        self._attach_data(data)
+        tr = self.trainer
+        torch.cuda.set_device(tr.device)                      # the loaders launch their resize kernels on the current device's stream
+        loader = build_train_loader(args, data, self.task, tr.device, tr.rank, tr.world_size)
+        if len(loader) == 0:
+            raise ValueError(f"the training set holds {len(loader.shapes)} images, fewer than one batch of {args.batch}")
+        tr.setup(self.model, total_iterations=len(loader) * args.epochs)
+        val_loader = None
+        if getattr(args, "val", True) and tr.rank in (-1, 0):
+            stride = max(int(self.model.stride.max()), 32)
+            val_loader = build_val_loader(args, data, self.task, tr.device, "val", batch=2 * int(args.batch), stride=stride)
+        if save_dir is None and (getattr(args, "project", None) or getattr(args, "name", None)):
+            save_dir = Path(args.project or "runs") / (args.name or "train")
+        return tr.train(loader, val_loader=val_loader, save_dir=save_dir)
 
     def val(self, loader=None, **kwargs):
-        ov = dict(self.overrides)
-        ov.update(kwargs)
-        return all_tasks()[self.task][2](get_cfg(ov))(self.model, loader)
+        """model.val(data='dataset/data.yaml', split='val', ...): the split as rect batches of the cfg's `batch` (data.DeviceValLoader);
+        `loader=` as before.  The model must be on the GPU."""
+        args = self._data_args(kwargs)
+        if loader is None and getattr(args, "data", None):
+            if self.task == "classify":
+                raise NotImplementedError("the classify task reads one folder per class, not YOLO label files: pass loader=")
+            from ..data import build_val_loader, check_det_dataset
+            data = check_det_dataset(args.data)
+            dev = next(self.model.parameters()).device
+            if len(data["names"]) != len(self.model.names):
+                raise ValueError(f"val(data=): the dataset has {len(data['names'])} classes, the model {len(self.model.names)}: "
+                                 "their class ids do not mean the same")
+            self.model.names = dict(data["names"])
+            torch.cuda.set_device(dev)
+            loader = build_val_loader(args, data, self.task, dev, getattr(args, "split", None) or "val",
+                                      stride=max(int(self.model.stride.max()), 32))
+        return all_tasks()[self.task][2](args)(self.model, loader)
 
     @torch.no_grad()
     def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, augment=False,
                 **kw):
-        """reference engine/predictor.py stream_inference + DetectionPredictor.postprocess (models/yolo/detect/predict.py:12-38)
-        for an already letter-boxed batch: `source` is a uint8 [B,3,H,W] RGB tensor (or float in [0,1]); returns one `Results`
-        per image with boxes scaled back to `orig_shapes[i]` (default: the network input shape).  A segment model also fills
-        `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Image decoding / letter-boxing (cv2), plotting
+        """reference engine/predictor.py stream_inference + DetectionPredictor.postprocess (models/yolo/detect/predict.py:12-38).
+        `source` is either
+          * an already letter-boxed batch: a uint8 [B,3,H,W] RGB tensor (or float in [0,1]); boxes are scaled back to `orig_shapes[i]`
+            (default: the network input shape); or
+          * an image file, a directory of images, or a list of files / decoded uint8 HWC BGR arrays: every image is letter-boxed on the
+            device to the stride-multiple shape of its own aspect ratio (data.augment.letterbox_auto: the predictor's
+            LetterBox(imgsz, auto=True), scaleup, linear resize; `imgsz=` in the call or the cfg's), one image per forward (files are
+            decoded one at a time); detect / segment / pose only; `orig_shapes` is filled from the images and `Results.path` from the files.
+        Returns one `Results` per image.  A segment model also fills
+        `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Plotting
         and the mask contours (`Masks.xy`) are outside the hot path.  A classify model returns `Results.probs` (the eval soft-max row
         of each image; classify/predict.py:23-31) and no boxes.  `augment=True`: multi-scale, flipped inference (DetectionModel._predict_augment) before the NMS."""
+        if torch.is_tensor(source):
+            return self._predict_batch(source, conf, iou, max_det, agnostic_nms, orig_shapes, retina_masks, augment)
+        import numpy as np
+        from ..data.augment import letterbox_auto
+        from ..data.dataset import decode, get_img_files
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("predict() needs the model on a GPU (there is no CPU path)")
+        if self.task == "classify":
+            raise NotImplementedError("predict(path): the classify transform (resize + centre crop) is not implemented: pass a tensor")
+        items = source if isinstance(source, (list, tuple)) else [source]
+        images, paths = [], []
+        for it in items:
+            if isinstance(it, np.ndarray):
+                if it.dtype != np.uint8 or it.ndim != 3 or it.shape[2] != 3:
+                    raise ValueError("predict(): an image array must be uint8 HWC with 3 channels (BGR, as cv2.imread gives it)")
+                images.append(np.ascontiguousarray(it))
+                paths.append(None)
+            else:
+                files = get_img_files(str(it)) if Path(str(it)).is_dir() else [str(it)]
+                images += files                                # decoded one at a time, below
+                paths += files
+        imgsz = int(kw.get("imgsz") or getattr(get_cfg(dict(self.overrides)), "imgsz", 640))
+        stride = max(int(self.model.stride.max()), 32)
+        out = []
+        for im in images:                                     # one image per forward, as the reference's file stream (batch 1) runs
+            im = decode(im) if isinstance(im, str) else im
+            boxed = letterbox_auto(torch.from_numpy(im).to(dev), imgsz, stride)[0]
+            out += self._predict_batch(boxed[None], conf, iou, max_det, agnostic_nms, [tuple(im.shape[:2])], retina_masks, augment)
+        for r, p in zip(out, paths):
+            r.path = p
+        return out
+
+    def _predict_batch(self, source, conf, iou, max_det, agnostic_nms, orig_shapes, retina_masks, augment):
+        """predict() for a letter-boxed tensor batch"""
         from ..utils import ops as uops
         from .results import Results
         from .validator import DetectionValidator

@@ -143,7 +143,7 @@ class DetectionValidator:
         """engine/validator.py:95-200 (model given directly; the trainer passes its EMA weights loaded into `model`)."""
         loader = dataloader if dataloader is not None else self.dataloader
         if loader is None:
-            raise ValueError("pass an iterable of reference-schema batch dicts; dataset decoding is outside the hot path")
+            raise ValueError("pass an iterable of reference-schema batch dicts (YOLO.val(data=<data yaml>) builds one from a dataset on disk)")
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("DetectionValidator needs the model on a GPU (there is no CPU path)")

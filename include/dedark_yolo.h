@@ -493,6 +493,11 @@ typedef struct dy_aug_sample {
 } dy_aug_sample;
 /* cv2.resize(INTER_LINEAR) of load_image (base.py:152-157). */
 int dy_aug_resize_u8(const uint8_t* src, int sh, int sw, int64_t src_pitch, uint8_t* dst, int dh, int dw, int64_t dst_pitch, void* stream);
+/* cv2.resize(INTER_AREA) of load_image for a validation image that shrinks (base.py:152-157: `interp = cv2.INTER_LINEAR if (self.augment or
+   r > 1) else cv2.INTER_AREA`), uint8 HWC, 3 channels, dh <= sh and dw <= sw (anything else: argument error).  OpenCV's scalar rule
+   (computeResizeAreaTab + ResizeArea_Invoker) as tests/resize_area_ref.py states it: per-axis (index, f32 weight) tables built on the host in
+   double and uploaded with the call on `stream`, f32 accumulation in table order without FMA, cvRound + saturate. */
+int dy_aug_resize_area_u8(const uint8_t* src, int sh, int sw, int64_t src_pitch, uint8_t* dst, int dh, int dw, int64_t dst_pitch, void* stream);
 /* LetterBox + Format (augment.py:559-591,745-751): resize to new_h x new_w, border 114 (top / left given), out = uint8 [3, out_h, out_w] RGB. */
 int dy_aug_letterbox(const uint8_t* src, int sh, int sw, int64_t src_pitch, int new_h, int new_w, int top, int left, int out_h, int out_w,
                      uint8_t* out, void* stream);
