@@ -92,7 +92,6 @@ _SIGS = {
     "dy_pack_weight": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_pack_item_blocks": [i32, i32, i32, i32],
     "dy_pack_weights_multi": [vp, i32, i64, vp],
-    "dy_unpack_wgrad": [vp, vp, i32, i32, i32, i32, i32, vp],
     "dy_bn_finalize": [vp, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp],
     "dy_bn_fold_eval": [vp, vp, vp, vp, f32, vp, vp, i32, vp],
     "dy_bn_finalize_valid": [vp, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp],

@@ -682,7 +682,42 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// ---- weight (un)packing -----------------------------------------------------------------------------------------------
+// The same for slabs with the output channel contiguous (DyCoSlabs, conv_route.h: wgrad_v2.hip, wgrad_v3.hip).  Block = (32
+// consecutive co, one k'); eight split-lanes walk the slabs with four loads in flight each and are added in a fixed order.
+// (The layout comes as scalars: a struct by value is read from the kernel arguments where it is used, one exposed round trip more
+//  per block -- 56 -> 59 us for the 73,728 blocks of 512->512 3x3 at 20x20, B = 32.)
+__global__ __launch_bounds__(256) void wgrad_reduce_co_kernel(const float* __restrict__ part, int splits, int co_tile, int k_tile, int Cin_pad,
+                                                               int KH, int KW, int Cout, int Cin, long co_stride, long k_stride,
+                                                               long sstride, float* __restrict__ g) {
+  __shared__ float red[8][33];
+  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int co = blockIdx.x * 32 + cl;
+  const int k = blockIdx.y;
+  const int tap = k / Cin_pad, ci = k - tap * Cin_pad;
+  if (ci >= Cin) return;                                     // block-uniform
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  if (co < Cout) {
+    const float* src = part + (co / co_tile) * co_stride + (k / k_tile) * k_stride + (long)(k % k_tile) * co_tile + (co % co_tile);
+    int s = sl;
+    for (; s + 24 < splits; s += 32) {
+      const float v0 = src[(long)s * sstride], v1 = src[(long)(s + 8) * sstride], v2 = src[(long)(s + 16) * sstride],
+                  v3 = src[(long)(s + 24) * sstride];
+      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+    }
+    for (; s < splits; s += 8) a0 += src[(long)s * sstride];
+  }
+  red[sl][cl] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (sl == 0 && co < Cout) {
+    float t = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t += red[u][cl];
+    const int kh = tap / KW, kw = tap - kh * KW;
+    g[(((long)co * Cin + ci) * KH + kh) * KW + kw] = t;
+  }
+}
+
+// ---- weight packing ---------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ out, int Cout, int Cout_pad, int Cin,
                                    int Cin_pad, int KH, int KW, int transposed) {
@@ -798,19 +833,6 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const dy_pack_item* __r
   else if (T == 1) pack_chunk<1>(it, tile, co0, ci0, 1, 0, 1);
   else
     for (int t0 = 0; t0 < T; t0 += PACK_TAPS) pack_chunk<0>(it, tile, co0, ci0, T, t0, T - t0 < PACK_TAPS ? T - t0 : PACK_TAPS);
-}
-
-__global__ void unpack_wgrad_kernel(const float* __restrict__ dwp, float* __restrict__ g, int Cout, int Cin, int Cin_pad,
-                                    int KH, int KW) {
-  long total = (long)Cout * Cin * KH * KW;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long r = i;
-    int kw = (int)(r % KW); r /= KW;
-    int kh = (int)(r % KH); r /= KH;
-    int ci = (int)(r % Cin); r /= Cin;
-    int co = (int)r;
-    g[i] = dwp[(((long)co * KH + kh) * KW + kw) * Cin_pad + ci];
-  }
 }
 
 template <typename T, int MODE>
@@ -1046,7 +1068,9 @@ extern "C" int dy_conv2d_dgrad(const dy_conv_desc* d, void* stream) {
 
 namespace {
 template <typename T>
-int launch_wgrad(WgP p, float* scratch, long scratch_elems, float* g_oihw, int Cout_real, int Cin_real, hipStream_t st) {
+int launch_wgrad(const DyWgradArgs& a, hipStream_t st) {
+  WgP p;
+  dy_route::fill_wgrad_problem(p, a);
   constexpr int MK = 8 * DT<T>::VE;
   int bm, bn;
   bn = p.Ktot <= 32 ? 32 : (p.Ktot <= 64 ? 64 : 128);
@@ -1061,21 +1085,13 @@ int launch_wgrad(WgP p, float* scratch, long scratch_elems, float* g_oihw, int C
   // 1024 by 7 % and 256 lose 55 %), at least 4 steps of pixels per split, and the slabs must fit
   static const int env_blocks = dy_env("DY_WGRAD_BLOCKS") ? atoi(dy_env("DY_WGRAD_BLOCKS")) : 0;     // tuning aids
   static const int env_steps = dy_env("DY_WGRAD_STEPS") ? atoi(dy_env("DY_WGRAD_STEPS")) : 0;
-  const int min_steps = env_steps > 0 ? env_steps : 4;
-  long max_splits = (p.M + (long)min_steps * MK - 1) / ((long)min_steps * MK);
-  long want = ((env_blocks > 0 ? env_blocks : 2048) + tiles - 1) / tiles;
-  long splits = want < max_splits ? want : max_splits;
-  const long fit = scratch_elems / ((long)tiles * bm * bn);
-  DY_CHECK(fit >= 1, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", scratch_elems, (long)tiles * bm * bn);
-  if (splits > fit) splits = fit;
-  if (splits < 1) splits = 1;
-  if (splits > 65535) splits = 65535;
-  long chunk = (p.M + splits - 1) / splits;
-  chunk = (chunk + MK - 1) / MK * MK;
-  splits = (p.M + chunk - 1) / chunk;
-  p.chunk = chunk;
-  p.part = scratch;
-  dim3 grid(tiles, (unsigned)splits);
+  const long fit = a.scratch_elems / ((long)tiles * bm * bn);
+  DY_CHECK(fit >= 1, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", a.scratch_elems, (long)tiles * bm * bn);
+  const long want = ((env_blocks > 0 ? env_blocks : 2048) + tiles - 1) / tiles;
+  const dy_route::WgradSplits plan =
+      dy_route::plan_wgrad_splits(p.M, want, (long)(env_steps > 0 ? env_steps : 4) * MK, MK, fit, dy_route::kGridDimYCap);
+  p.chunk = plan.chunk;
+  dim3 grid(tiles, (unsigned)plan.splits);
   dy_note_kernel("conv_wgrad_kernel+wgrad_reduce_kernel");
 #define WG(BM_, BN_, WM_, WN_) conv_wgrad_kernel<T, BM_, BN_, WM_, WN_><<<grid, NTHREADS, 0, st>>>(p)
   if (bm == 128 && bn == 128) WG(128, 128, 2, 2);
@@ -1086,26 +1102,40 @@ int launch_wgrad(WgP p, float* scratch, long scratch_elems, float* g_oihw, int C
   else WG(128, 32, 4, 1);
 #undef WG
   DY_LAUNCH_CHECK();
-  wgrad_reduce_kernel<<<dim3(Cout_real, dy_cdiv(p.Ktot, 32)), 256, 0, st>>>(scratch, (int)splits, tiles, p.tiles_k, bm, bn,
-                                                                            Cin_real, p.Cin, p.KH, p.KW, p.Ktot, g_oihw);
+  wgrad_reduce_kernel<<<dim3(a.Cout, dy_cdiv(p.Ktot, 32)), 256, 0, st>>>(a.scratch, (int)plan.splits, tiles, p.tiles_k, bm, bn, a.Cin, p.Cin,
+                                                                         p.KH, p.KW, p.Ktot, a.g_oihw);
   DY_LAUNCH_CHECK();
   return 0;
 }
 
 int wgrad_generic(const DyWgradArgs& a, void* stream) {
-  WgP p;
-  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad;
-  p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
-  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil; p.part = a.scratch;
-  p.M = (long)a.N * a.Ho * a.Wo;
-  p.Ktot = a.KH * a.KW * a.Cin_pad;
-  p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
-  hipStream_t st = (hipStream_t)stream;
-  return a.dtype == DY_F32 ? launch_wgrad<float>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st)
-                           : (a.dtype == DY_F16 ? launch_wgrad<f16_t>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st)
-                                                : launch_wgrad<bf16_t>(p, a.scratch, a.scratch_elems, a.g_oihw, a.Cout, a.Cin, st));
+  int rc = 0;
+  DY_DISPATCH_DTYPE("dy_conv2d_wgrad", a.dtype, rc = launch_wgrad<T>(a, (hipStream_t)stream));
+  return rc;
 }
+
+// The weight-gradient routes, in the order they are tried: the first row whose `eligible` accepts the problem launches it, the last
+// row accepts everything.
+struct WgradRoute {
+  bool (*eligible)(const DyWgradArgs& a);
+  int (*launch)(const DyWgradArgs& a, void* stream);
+};
+
+const WgradRoute kWgradRoutes[] = {
+    {dy_dense_wgrad_eligible, dy_dense_wgrad_launch},          // dense.hip: whole-input window
+    {dy_wgrad_v3_eligible, dy_wgrad_v3_launch},                // wgrad_v3.hip: band kernel of the 64 / 128-channel 3x3 layers
+    {dy_wgrad_v4_eligible, dy_wgrad_v4_launch},                // wgrad_v4.hip: 256 x 256 tiles
+    {dy_wgrad_v2_eligible, dy_wgrad_v2_launch},                // wgrad_v2.hip: pipelined 128 x 128 / 256 x 256 tiles
+    {[](const DyWgradArgs&) { return true; }, wgrad_generic},  // this file: conv_wgrad_kernel
+};
 }  // namespace
+
+int dy_wgrad_reduce_co_slabs(const float* part, int splits, const DyCoSlabs& L, int Cout, int Cin, float* g_oihw, void* stream) {
+  wgrad_reduce_co_kernel<<<dim3(dy_cdiv(Cout, 32), L.KH * L.KW * L.Cin_pad), 256, 0, (hipStream_t)stream>>>(
+      part, splits, L.co_tile, L.k_tile, L.Cin_pad, L.KH, L.KW, Cout, Cin, L.co_stride, L.k_stride, L.split_stride, g_oihw);
+  DY_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int dy_conv2d_wgrad(const void* x, int64_t x_ld, int N, int Hi, int Wi, int Cin_pad, const void* dz, int64_t dz_ld,
                                int Ho, int Wo, int Cout_pad, int KH, int KW, int stride, int pad, int dil, int Cout, int Cin,
@@ -1121,11 +1151,9 @@ extern "C" int dy_conv2d_wgrad(const void* x, int64_t x_ld, int N, int Hi, int W
   DY_CHECK(ho == Ho && wo == Wo, "dy_conv2d_wgrad: dz %dx%d does not match conv output %dx%d", Ho, Wo, ho, wo);
   const DyWgradArgs a = {x, x_ld, N, Hi, Wi, Cin_pad, dz, dz_ld, Ho, Wo, Cout_pad, KH, KW, stride, pad, dil, Cout, Cin,
                          scratch, scratch_elems, g_oihw, dtype};
-  if (dy_dense_wgrad_eligible(a)) return dy_dense_wgrad_launch(a, stream);                 // dense.hip
-  if (dy_wgrad_v3_eligible(a)) return dy_wgrad_v3_launch(a, stream);                       // wgrad_v3.hip
-  if (dy_wgrad_v4_eligible(a)) return dy_wgrad_v4_launch(a, stream);                       // wgrad_v4.hip
-  if (dy_wgrad_v2_eligible(a)) return dy_wgrad_v2_launch(a, stream);                       // wgrad_v2.hip
-  return wgrad_generic(a, stream);                                                         // this file: conv_wgrad_kernel
+  for (const WgradRoute& r : kWgradRoutes)
+    if (r.eligible(a)) return r.launch(a, stream);
+  return 0;        // not reached: the last row takes every problem
 }
 
 extern "C" int dy_pack_weight(const float* w, void* packed, int Cout, int Cout_pad, int Cin, int Cin_pad, int KH, int KW,
@@ -1149,16 +1177,6 @@ extern "C" int64_t dy_pack_item_blocks(int Cout_pad, int Cin_pad, int KH, int KW
 extern "C" int dy_pack_weights_multi(const dy_pack_item* items_dev, int n_items, int64_t n_blocks, void* stream) {
   DY_CHECK(items_dev && n_items > 0 && n_blocks > 0 && n_blocks < (1LL << 31), "dy_pack_weights_multi: bad args");
   pack_multi_kernel<<<(unsigned)n_blocks, 256, 0, (hipStream_t)stream>>>(items_dev, n_items);
-  DY_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int dy_unpack_wgrad(const float* dwp, float* g, int Cout, int Cin, int Cin_pad, int KH, int KW, void* stream) {
-  DY_CHECK(dwp && g, "dy_unpack_wgrad: null");
-  long total = (long)Cout * Cin * KH * KW;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  unpack_wgrad_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(dwp, g, Cout, Cin, Cin_pad, KH, KW);
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -12,7 +12,7 @@
 //     group g) so that a lane owns 8 consecutive channels of its pixel: one 16-byte store, the four lane groups covering 64 contiguous
 //     bytes; optional `dst +=` / addend view; BatchNorm sums of the raw output stay in registers (N <= 128).
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
 
@@ -201,8 +201,6 @@ bool dy_conv_px_eligible(const dy_conv_desc* d, int mode) {
 template <int KB, int NS, typename T>
 static int px_go(const px::P& p, bool stats, size_t shm, unsigned blocks, hipStream_t st) {
   constexpr bool HAS_STATS = NS <= 4;
-  static bool configured_s = false, configured_p = false;
-  bool& configured = stats ? configured_s : configured_p;
   const void* fn = reinterpret_cast<const void*>(&px::px1x1_kernel<KB, NS, T, false>);
   if constexpr (HAS_STATS) {
     if (stats) fn = reinterpret_cast<const void*>(&px::px1x1_kernel<KB, NS, T, true>);
@@ -210,13 +208,7 @@ static int px_go(const px::P& p, bool stats, size_t shm, unsigned blocks, hipStr
     dy_set_error("conv_px: no statistics variant for %d output channels per block", 32 * NS);
     return 3;
   }
-  if (!configured) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-      dy_set_error("conv_px: hipFuncSetAttribute failed");
-      return 3;
-    }
-    configured = true;
-  }
+  if (int e = dy_raise_lds_limit("conv_px", {{fn, 150 * 1024}})) return e;
   if constexpr (HAS_STATS) {
     if (stats) {
       px::px1x1_kernel<KB, NS, T, true><<<blocks, px::NT, shm, st>>>(p);

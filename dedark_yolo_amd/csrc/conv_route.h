@@ -1,7 +1,10 @@
 // What the convolution routes share outside their kernels: two device helpers, the descriptor -> kernel-parameter fills, the
-// eligibility checks more than one route repeats, and the prototype of every route's entry points.  The order in which the routes
-// are tried is the table in conv.hip (kRoutes); tile-count and K thresholds stay with the kernel they tune.
+// eligibility checks more than one route repeats, and the prototype of every route's entry points; for the weight gradient also
+// the split plan of the pixel loop and the slab layout its shared reduce kernel reads.  The order in which the routes are tried is
+// the pair of tables in conv.hip (kRoutes, kWgradRoutes); tile-count and K thresholds stay with the kernel they tune.
 #pragma once
+#include <type_traits>
+#include <utility>
 #include "dy_common.h"
 #include "../../include/dedark_yolo.h"
 
@@ -188,6 +191,58 @@ struct DyWgradArgs {
   float* g_oihw;
   int dtype;
 };
+
+namespace dy_route {
+
+// the problem description WgP (conv.hip), wg2::P and wg4::P share; `pointwise` (1x1 / stride 1 / no padding: x rows are the output
+// pixels) only where the kernel reads it from its parameters
+template <typename P, typename = void> struct HasPointwise : std::false_type {};
+template <typename P> struct HasPointwise<P, std::void_t<decltype(std::declval<P&>().pointwise)>> : std::true_type {};
+
+template <typename P>
+inline void fill_wgrad_problem(P& p, const DyWgradArgs& a) {
+  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad;
+  p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
+  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil; p.part = a.scratch;
+  p.M = (long)a.N * a.Ho * a.Wo;
+  p.Ktot = a.KH * a.KW * a.Cin_pad;
+  if constexpr (HasPointwise<P>::value) p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
+}
+
+// The M output pixels of a weight gradient in `splits` chunks of `chunk` pixels, one slab set (all tiles) per split: `want` splits
+// (the caller's target block count over its tile count), no more than leave `min_pixels` per split, than `fit` slab sets in the
+// scratch buffer (scratch_elems / slab_set_elems) or than `grid_cap`, at least one; the chunk is a whole number of `step`-pixel
+// K-steps, and the splits are recounted for it.
+struct WgradSplits {
+  long splits, chunk;
+};
+constexpr long kGridDimYCap = 65535, kNoGridCap = 1L << 40;
+inline WgradSplits plan_wgrad_splits(long M, long want, long min_pixels, long step, long fit, long grid_cap) {
+  const long max_splits = (M + min_pixels - 1) / min_pixels;
+  long splits = want < max_splits ? want : max_splits;
+  if (splits > fit) splits = fit;
+  if (splits < 1) splits = 1;
+  if (splits > grid_cap) splits = grid_cap;
+  long chunk = (M + splits - 1) / splits;
+  chunk = (chunk + step - 1) / step * step;
+  return {(M + chunk - 1) / chunk, chunk};
+}
+
+}  // namespace dy_route
+
+// Slabs with the output channel contiguous (wgrad_v2.hip, wgrad_v3.hip): split s keeps the partial dW[k'][co], k' = tap * Cin_pad +
+// ci, at part[s * split_stride + (co / co_tile) * co_stride + (k' / k_tile) * k_stride + (k' % k_tile) * co_tile + co % co_tile].
+struct DyCoSlabs {
+  int co_tile;           // output channels per tile = length of a tile row
+  long co_stride;        // elements from one co tile to the next
+  int k_tile;            // k' rows per tile
+  long k_stride;         // elements from one k' tile to the next
+  long split_stride;     // elements from one split's slab set to the next
+  int Cin_pad, KH, KW;
+};
+// conv.hip: g[co][ci][kh][kw] (f32 OIHW, real channel counts) = sum over the splits, in a fixed order
+int dy_wgrad_reduce_co_slabs(const float* part, int splits, const DyCoSlabs& L, int Cout, int Cin, float* g_oihw, void* stream);
+
 bool dy_dense_wgrad_eligible(const DyWgradArgs& a);                          // dense.hip
 int dy_dense_wgrad_launch(const DyWgradArgs& a, void* stream);
 bool dy_wgrad_v3_eligible(const DyWgradArgs& a);                             // wgrad_v3.hip: band kernel of the 64 / 128-channel 3x3 layers

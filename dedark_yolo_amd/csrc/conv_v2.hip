@@ -11,7 +11,7 @@
 //   * v_mfma_f32_32x32x16_bf16, f32 accumulate; BatchNorm batch statistics from the accumulators (replicated f64 atomics).
 // Requirements (checked by the dispatcher): bf16, Cs % 64 == 0 (a K-step never straddles two taps), dense 16-byte aligned views.
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
@@ -293,16 +293,7 @@ int launch_t(P& p, hipStream_t st) {
   constexpr int RING = NSTAGE * (BM + BN) * ROW, EPI = dy_epi::image_bytes<BM, BN>();
   constexpr int SHMEM = RING > EPI ? RING : EPI;            // the epilogue image reuses the ring
   static_assert(SHMEM <= 160 * 1024, "LDS budget");
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_kernel<BM, BN, MODE, SMALLC, NSTAGE, T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    if (e != hipSuccess) {
-      dy_set_error("conv_v2: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured = true;
-  }
+  if (int e = dy_raise_lds_limit("conv_v2", {{&conv_kernel<BM, BN, MODE, SMALLC, NSTAGE, T>, SHMEM}})) return e;
   p.tiles_n = dy_cdiv(p.Cd, BN);
   p.nblk = dy_cdiv(p.M, BM) * p.tiles_n;
   if (p.ncls > 1) p.nblk = dy_route::number_parity_blocks(p, BM, dy_route::CLS_SEQUENTIAL);
@@ -316,7 +307,8 @@ int launch_t(P& p, hipStream_t st) {
 
 template <int BN, int MODE, bool SMALLC, int NSTAGE = 3, int BM = 256>
 int launch(P& p, hipStream_t st) {
-  return p.f16 ? launch_t<BN, MODE, SMALLC, NSTAGE, BM, f16_t>(p, st) : launch_t<BN, MODE, SMALLC, NSTAGE, BM, bf16_t>(p, st);
+  return dy_dispatch_16bit("conv_v2", p.f16 ? DY_F16 : DY_BF16,
+                           [&](auto tag) { return launch_t<BN, MODE, SMALLC, NSTAGE, BM, typename decltype(tag)::type>(p, st); });
 }
 
 }  // namespace v2

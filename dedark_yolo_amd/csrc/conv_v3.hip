@@ -12,7 +12,7 @@
 //   * 256 x BN tile, 8 waves (4 x 2), v_mfma_f32_32x32x16_bf16; epilogue through LDS with 16-byte stores; BN batch statistics.
 // Data gradient (MODE 1) is the same walk with the taps mirrored: dx[m] += dz[m + (1-kh)*W + (1-kw)] * Wt[kh][kw].
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
@@ -298,16 +298,7 @@ int shmem_bytes(const P& p) {
 template <int BN, int MODE, typename T>
 int launch_t(P& p, hipStream_t st) {
   const int shm = shmem_bytes<BN>(p);
-  static int configured = 0;
-  if (shm > configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<BN, MODE, T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-    if (e != hipSuccess) {
-      dy_set_error("conv_v3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured = LDS_LIMIT;
-  }
+  if (int e = dy_raise_lds_limit("conv_v3", {{&conv3x3_kernel<BN, MODE, T>, LDS_LIMIT}})) return e;
   p.tiles_n = dy_cdiv(p.Cd, BN);
   p.nblk = dy_cdiv(p.M, BM) * p.tiles_n;
   dy_note_kernel(BN == 128 ? (MODE ? "v3::conv3x3_kernel<128, 1>" : "v3::conv3x3_kernel<128, 0>") : (MODE ? "v3::conv3x3_kernel<64, 1>" : "v3::conv3x3_kernel<64, 0>"));

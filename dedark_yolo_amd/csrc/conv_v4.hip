@@ -29,7 +29,7 @@
 // 16x16 accumulator layout.
 #include <stdlib.h>
 #include <type_traits>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
@@ -566,15 +566,7 @@ static int v4_launch(const dy_conv_desc* d, int mode, void* stream, int force_va
   constexpr int EPI256 = dy_epi::row_image_bytes<256, 256>();
   constexpr int SH256 = 2 * v4::BUF > EPI256 ? 2 * v4::BUF : EPI256;
   static_assert(SH256 <= 160 * 1024, "LDS budget");
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v4::conv_kernel<ABL, T>), hipFuncAttributeMaxDynamicSharedMemorySize, SH256);
-    if (e != hipSuccess) {
-      dy_set_error("conv_v4: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured = true;
-  }
+  if (int e = dy_raise_lds_limit("conv_v4", {{&v4::conv_kernel<ABL, T>, SH256}})) return e;
   dy_note_kernel("v4::conv_kernel");
   v4::conv_kernel<ABL, T><<<p.nblk, 512, SH256, (hipStream_t)stream>>>(p);
   DY_LAUNCH_CHECK();

@@ -17,7 +17,7 @@
 // ds_read_b128 (16x16x32 operand: lane = row l&15, chunk l>>4) then hit 16 different slots of the 256-byte bank row.
 #include <stdlib.h>
 #include <type_traits>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "conv_epilogue.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
@@ -711,26 +711,14 @@ static int v5_launch(const dy_conv_desc* d, int mode, void* stream, const dy_con
   static const bool no_band = dy_env("DY_NO_CONV_BAND") != nullptr;
   const bool band = ncls <= 1 && !no_band && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1 && d->KHf <= 0 && d->Hs == d->Hd &&
                     d->Ws == d->Wd && d->Ws >= 16;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<128, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SH128);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<64, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SH64);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<128, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SH128);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<64, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SH64);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<64, bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SH64S);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::conv_kernel<64, f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SH64S);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<128, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SB128);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<64, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SB64);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<128, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SB128);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<64, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SB64);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<64, bf16_t, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, SB64S);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&v5::band_kernel<64, f16_t, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, SB64S);
-    if (e != hipSuccess) {
-      dy_set_error("conv_v5: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured = true;
-  }
+  // all twelve instantiations at the first launch of any
+  if (int e = dy_raise_lds_limit("conv_v5", {{&v5::conv_kernel<128, bf16_t>, SH128}, {&v5::conv_kernel<64, bf16_t>, SH64},
+                                             {&v5::conv_kernel<128, f16_t>, SH128}, {&v5::conv_kernel<64, f16_t>, SH64},
+                                             {&v5::conv_kernel<64, bf16_t, true>, SH64S}, {&v5::conv_kernel<64, f16_t, true>, SH64S},
+                                             {&v5::band_kernel<128, bf16_t>, SB128}, {&v5::band_kernel<64, bf16_t>, SB64},
+                                             {&v5::band_kernel<128, f16_t>, SB128}, {&v5::band_kernel<64, f16_t>, SB64},
+                                             {&v5::band_kernel<64, bf16_t, 2>, SB64S}, {&v5::band_kernel<64, f16_t, 2>, SB64S}}))
+    return e;
   const bool f16 = d->dtype == DY_F16;
   if (band && bn == 128) {
     dy_note_kernel("v5::band_kernel<128>");

@@ -1,6 +1,8 @@
-// Host-side helpers shared by the C-ABI launchers of the element-wise, BatchNorm, loss and task files: the dtype dispatch, the
-// NHWC view check and the small grid / alignment helpers.  Nothing here is device code.
+// Host-side helpers shared by the C-ABI launchers: the dtype dispatches, the dynamic-LDS limit of the big-tile kernels, the NHWC
+// view check and the small grid / alignment helpers.  Nothing here is device code.
 #pragma once
+#include <initializer_list>
+#include <unordered_set>
 #include "dy_common.h"
 
 static inline int dy_elem_size(int dtype) { return dtype == DY_F32 ? 4 : 2; }   // bytes per element
@@ -33,6 +35,38 @@ template <typename F> inline int dy_dispatch_dtype(const char* who, int dtype, F
         }))                                                                                     \
       return e__;                                                                               \
   } while (0)
+
+// The kernels that exist for the two 16-bit types only: the same tag form, but f returns the launcher's status and that is what
+// comes back; any other dtype calls nothing, sets "<who>: dtype %d is not a 16-bit type" and returns 1.
+template <typename F> inline int dy_dispatch_16bit(const char* who, int dtype, F&& f) {
+  if (dtype == DY_F16) return f(DyType<f16_t>{});
+  if (dtype == DY_BF16) return f(DyType<bf16_t>{});
+  DY_CHECK(false, "%s: dtype %d is not a 16-bit type", who, dtype);
+  return 1;
+}
+
+// Raise the dynamic-LDS limit of kernels that use more than the default 64 KiB: each {kernel, bytes} pair is configured the first
+// time it is passed and remembered, so a launcher calls this in front of every launch with the kernels it wants ready from then on
+// (one kernel: configured at its own first launch; a whole family: all of them at the first launch of any).  Like the flags it
+// replaces this expects the launchers to run on one host thread.  Returns 3 with "<family>: hipFuncSetAttribute failed: ..." set.
+struct DyLdsLimit {
+  const void* kernel;
+  int bytes;
+  template <typename K> DyLdsLimit(K* k, int b) : kernel(reinterpret_cast<const void*>(k)), bytes(b) {}
+};
+inline int dy_raise_lds_limit(const char* family, std::initializer_list<DyLdsLimit> kernels) {
+  static std::unordered_set<const void*> raised;
+  for (const DyLdsLimit& k : kernels) {
+    if (raised.count(k.kernel)) continue;
+    const hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
+    if (e != hipSuccess) {
+      dy_set_error("%s: hipFuncSetAttribute failed: %s", family, hipGetErrorString(e));
+      return 3;
+    }
+    raised.insert(k.kernel);
+  }
+  return 0;
+}
 
 // the NHWC view (pointer + pixel stride ld, C channels) every vectorised kernel takes: whole 16-byte vectors, 16-byte aligned rows
 static inline int dy_check_view(const char* who, const void* p, long ld, int C, int dtype) {

@@ -17,7 +17,7 @@
 //   * the pixel range is split over gridDim.y; partial tiles go to `scratch` and a second kernel adds them in a fixed order
 //     (deterministic) while scattering to the OIHW f32 master-gradient layout.
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
 
@@ -240,39 +240,17 @@ __global__ __launch_bounds__(BP * 2) void wgrad_kernel(P p) {
     }
 }
 
-// g[co][ci][kh][kw] = sum over splits of part[split][tile(k', co)][k' % BP][co % BQ].  Block = (32 consecutive co, one k'); eight
-// split-lanes walk the slabs with four loads in flight each and are added in a fixed order (deterministic).
-__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ part, int splits, int tiles, int tiles_q, int BP, int BQ,
-                                                     int Cout, int Cin, int Cin_pad, int KH, int KW, int Ktot,
-                                                     float* __restrict__ g) {
-  __shared__ float red[8][33];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int co = blockIdx.x * 32 + cl;
-  const int k = blockIdx.y;
-  const int tap = k / Cin_pad, ci = k - tap * Cin_pad;
-  if (ci >= Cin) return;                                     // block-uniform
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (co < Cout) {
-    const int tile = (k / BP) * tiles_q + co / BQ;
-    const float* src = part + ((long)tile * BP + (k % BP)) * BQ + (co % BQ);
-    const long sstride = (long)tiles * BP * BQ;
-    int s = sl;
-    for (; s + 24 < splits; s += 32) {
-      const float v0 = src[(long)s * sstride], v1 = src[(long)(s + 8) * sstride], v2 = src[(long)(s + 16) * sstride],
-                  v3 = src[(long)(s + 24) * sstride];
-      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-    }
-    for (; s < splits; s += 8) a0 += src[(long)s * sstride];
-  }
-  red[sl][cl] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (sl == 0 && co < Cout) {
-    float t = 0.f;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t += red[u][cl];
-    const int kh = tap / KW, kw = tap - kh * KW;
-    g[(((long)co * Cin + ci) * KH + kh) * KW + kw] = t;
-  }
+// one tile variant in the layer's 16-bit type; its LDS limit is raised at its own first launch
+template <int BP, int BQ, int NSTAGE>
+int launch(const P& p, dim3 grid, int dtype, hipStream_t st) {
+  constexpr int SHMEM = NSTAGE * (BP / 128 + BQ / 128) * IMG;
+  return dy_dispatch_16bit("wgrad_v2", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (int e = dy_raise_lds_limit("wgrad_v2", {{&wgrad_kernel<BP, BQ, NSTAGE, T>, SHMEM}})) return e;
+    wgrad_kernel<BP, BQ, NSTAGE, T><<<grid, BP * 2, SHMEM, st>>>(p);
+    DY_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace wg2
@@ -298,30 +276,9 @@ int dy_wgrad_v2_launch(const DyWgradArgs& a, void* stream) {
   static const int exp_env = dy_env("DY_WG2_EXP") ? atoi(dy_env("DY_WG2_EXP")) : 0;
   const int exp_mode = exp_env == 3 ? 0 : (exp_env > 0 ? exp_env : (a.Cout_pad >= 256 ? 2 : 0));
   P p;
-  p.x = (const char*)a.x; p.x_ld = a.x_ld; p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad;
-  p.dz = (const char*)a.dz; p.dz_ld = a.dz_ld; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
-  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil; p.part = a.scratch;
-  p.M = (long)a.N * a.Ho * a.Wo;
-  p.Ktot = a.KH * a.KW * a.Cin_pad;
-  p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
+  dy_route::fill_wgrad_problem(p, a);
   const int bp = (exp_mode == 1 || exp_mode == 2 || exp_mode == 4) ? 256 : 128;
   const int BQ = exp_mode == 2 ? 256 : 128;
-  const int nstage = exp_mode == 1 ? 3 : 2;      // exp_mode 4: 256 x 128 x 2 stages (96 KiB)
-  const int shmem = nstage * (bp / 128 + BQ / 128) * IMG;
-  const bool f16 = a.dtype == DY_F16;
-#define WG2_FN(...) (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<__VA_ARGS__, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<__VA_ARGS__, bf16_t>))
-  const void* fn = exp_mode == 1 ? WG2_FN(256, 128, 3) : exp_mode == 2 ? WG2_FN(256, 256, 2) : exp_mode == 4 ? WG2_FN(256, 128, 2) : WG2_FN(128, 128, 2);
-#undef WG2_FN
-  static int configured = 0;          // bit mask of the variants whose LDS limit has been raised
-  const int cfg_bit = 1 << (exp_mode + (f16 ? 8 : 0));
-  if (!(configured & cfg_bit)) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    if (e != hipSuccess) {
-      dy_set_error("wgrad_v2: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured |= cfg_bit;
-  }
   const int tiles_p = dy_cdiv(p.Ktot, bp);
   p.tiles_q = dy_cdiv(a.Cout_pad, BQ);
   const int tiles = tiles_p * p.tiles_q;
@@ -329,34 +286,19 @@ int dy_wgrad_v2_launch(const DyWgradArgs& a, void* stream) {
   // scratch buffer.  1,024 blocks were no faster on the YOLOv8-n shapes (sum of 19 layers 913 us vs 908 us) and write + re-read
   // twice the partial tiles (64 KiB per block).
   static const long env_target = dy_env("DY_WG2_TARGET") ? atol(dy_env("DY_WG2_TARGET")) : 0;
-  const long target = env_target > 0 ? env_target : 512;
-  long splits = (target + tiles - 1) / tiles;
-  const long max_splits = (p.M + 8L * BKP - 1) / (8L * BKP);
-  if (splits > max_splits) splits = max_splits;
   const long fit = a.scratch_elems / ((long)tiles * bp * BQ);
   DY_CHECK(fit >= 1, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", a.scratch_elems, (long)tiles * bp * BQ);
-  if (splits > fit) splits = fit;
-  if (splits < 1) splits = 1;
-  if (splits > 65535) splits = 65535;
-  long chunk = (p.M + splits - 1) / splits;
-  chunk = (chunk + BKP - 1) / BKP * BKP;
-  splits = (p.M + chunk - 1) / chunk;
-  p.chunk = chunk;
+  const long want = ((env_target > 0 ? env_target : 512) + tiles - 1) / tiles;
+  const dy_route::WgradSplits plan = dy_route::plan_wgrad_splits(p.M, want, 8L * BKP, BKP, fit, dy_route::kGridDimYCap);
+  p.chunk = plan.chunk;
+  const dim3 grid(tiles, (unsigned)plan.splits);
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel(exp_mode == 2 ? "wg2::wgrad_kernel<256, 256, 2>+reduce_kernel" : (exp_mode == 0 ? "wg2::wgrad_kernel<128, 128, 2>+reduce_kernel" : "wg2::wgrad_kernel<256, 128>+reduce_kernel"));
-#define WG2_GO(NT_, ...)                                                                              \
-  do {                                                                                                 \
-    if (f16) wgrad_kernel<__VA_ARGS__, f16_t><<<dim3(tiles, (unsigned)splits), NT_, shmem, st>>>(p);   \
-    else wgrad_kernel<__VA_ARGS__, bf16_t><<<dim3(tiles, (unsigned)splits), NT_, shmem, st>>>(p);      \
-  } while (0)
-  if (exp_mode == 1) WG2_GO(512, 256, 128, 3);
-  else if (exp_mode == 2) WG2_GO(512, 256, 256, 2);
-  else if (exp_mode == 4) WG2_GO(512, 256, 128, 2);
-  else WG2_GO(256, 128, 128, 2);
-#undef WG2_GO
-  DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(a.Cout, 32), p.Ktot), 256, 0, st>>>(a.scratch, (int)splits, tiles, p.tiles_q, bp, BQ, a.Cout, a.Cin, a.Cin_pad,
-                                                                            a.KH, a.KW, p.Ktot, a.g_oihw);
-  DY_LAUNCH_CHECK();
-  return 0;
+  const int rc = exp_mode == 1   ? launch<256, 128, 3>(p, grid, a.dtype, st)
+                 : exp_mode == 2 ? launch<256, 256, 2>(p, grid, a.dtype, st)
+                 : exp_mode == 4 ? launch<256, 128, 2>(p, grid, a.dtype, st)      // 96 KiB
+                                 : launch<128, 128, 2>(p, grid, a.dtype, st);
+  if (rc) return rc;
+  const DyCoSlabs slabs = {BQ, (long)bp * BQ, bp, (long)p.tiles_q * bp * BQ, (long)tiles * bp * BQ, a.Cin_pad, a.KH, a.KW};
+  return dy_wgrad_reduce_co_slabs(a.scratch, (int)plan.splits, slabs, a.Cout, a.Cin, a.g_oihw, stream);
 }

@@ -16,7 +16,7 @@
 // 36 k' tiles on 12 waves; every block covers 64 output channels (blockIdx.y selects the 64-wide slice of dz).
 // Partial sums go to `scratch` as [co slice][block][9*CI][64] f32 and a second kernel adds them in a fixed order.
 #include <stdlib.h>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
 
@@ -234,35 +234,16 @@ __global__ __launch_bounds__(CI * 6) void wgrad_kernel(P p) {
     }
 }
 
-// g[co][ci][kh][kw] = sum over blocks of part[co / 64][block][(kh*3+kw)*CI + ci][co % 64]; threads run along co (contiguous reads)
-__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ part, int nblk, int CI, int Cout, int Cin,
-                                                     float* __restrict__ g) {
-  // block = (32 consecutive co, one k); eight split-lanes walk the slabs, added in a fixed order
-  __shared__ float red[8][33];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int co = blockIdx.x * 32 + cl;
-  const int k = blockIdx.y;
-  const int tap = k / CI, ci = k - tap * CI;
-  if (ci >= Cin) return;                                     // block-uniform
-  const long slab = (long)9 * CI * CO;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (co < Cout) {
-    const float* src = part + (long)(co / CO) * nblk * slab + (long)k * CO + (co % CO);
-    int s = sl;
-    for (; s + 24 < nblk; s += 32) {
-      const float v0 = src[(long)s * slab], v1 = src[(long)(s + 8) * slab], v2 = src[(long)(s + 16) * slab], v3 = src[(long)(s + 24) * slab];
-      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-    }
-    for (; s < nblk; s += 8) a0 += src[(long)s * slab];
-  }
-  red[sl][cl] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (sl == 0 && co < Cout) {
-    float t = 0.f;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t += red[u][cl];
-    g[((long)co * Cin + ci) * 9 + tap] = t;
-  }
+// CI input channels in the layer's 16-bit type (CI / 64 * 6 waves); its LDS limit is raised at its own first launch
+template <int CI>
+int launch(const P& p, dim3 grid, int shmem, int dtype, hipStream_t st) {
+  return dy_dispatch_16bit("wgrad_v3", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (int e = dy_raise_lds_limit("wgrad_v3", {{&wgrad_kernel<CI, T>, 160 * 1024}})) return e;
+    wgrad_kernel<CI, T><<<grid, CI * 6, shmem, st>>>(p);
+    DY_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // namespace wg3
@@ -322,30 +303,10 @@ int dy_wgrad_v3_launch(const DyWgradArgs& a, void* stream) {
   DY_CHECK((long)nblk * ny * slab <= a.scratch_elems, "dy_conv2d_wgrad: scratch too small (%ld floats, need %ld)", a.scratch_elems,
            (long)nblk * ny * slab);
   const int shmem = 4 * p.XW * a.Cin_pad * 2 + 2 * p.PW * ZPB;
-  static int configured = 0;
-  const bool f16 = a.dtype == DY_F16;
-  const int bit = (a.Cin_pad == 64 ? 1 : 2) << (f16 ? 2 : 0);
-  if (!(configured & bit)) {
-    const void* fn = a.Cin_pad == 64 ? (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<64, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<64, bf16_t>))
-                                   : (f16 ? reinterpret_cast<const void*>(&wgrad_kernel<128, f16_t>) : reinterpret_cast<const void*>(&wgrad_kernel<128, bf16_t>));
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      dy_set_error("wgrad_v3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured |= bit;
-  }
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel(a.Cin_pad == 64 ? "wg3::wgrad_kernel<64>+reduce_kernel" : "wg3::wgrad_kernel<128>+reduce_kernel");
-  if (a.Cin_pad == 64) {
-    if (f16) wgrad_kernel<64, f16_t><<<dim3(nblk, ny), 384, shmem, st>>>(p);
-    else wgrad_kernel<64, bf16_t><<<dim3(nblk, ny), 384, shmem, st>>>(p);
-  } else {
-    if (f16) wgrad_kernel<128, f16_t><<<dim3(nblk, ny), 768, shmem, st>>>(p);
-    else wgrad_kernel<128, bf16_t><<<dim3(nblk, ny), 768, shmem, st>>>(p);
-  }
-  DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(a.Cout, 32), 9 * a.Cin_pad), 256, 0, st>>>(a.scratch, nblk, a.Cin_pad, a.Cout, a.Cin, a.g_oihw);
-  DY_LAUNCH_CHECK();
-  return 0;
+  if (int e = a.Cin_pad == 64 ? launch<64>(p, dim3(nblk, ny), shmem, a.dtype, st) : launch<128>(p, dim3(nblk, ny), shmem, a.dtype, st)) return e;
+  // part[co / 64][block][(kh*3+kw)*CI + ci][co % 64]: one k' tile, the blocks are the splits
+  const DyCoSlabs slabs = {CO, (long)nblk * slab, 9 * a.Cin_pad, 0, slab, a.Cin_pad, 3, 3};
+  return dy_wgrad_reduce_co_slabs(a.scratch, nblk, slabs, a.Cout, a.Cin, a.g_oihw, stream);
 }

@@ -24,7 +24,7 @@
 //     contiguously.
 #include <stdlib.h>
 #include <type_traits>
-#include "dy_common.h"
+#include "dy_host.h"
 #include "../../include/dedark_yolo.h"
 #include "conv_route.h"
 
@@ -459,55 +459,36 @@ bool dy_wgrad_v4_eligible(const DyWgradArgs& a) {
 int dy_wgrad_v4_launch(const DyWgradArgs& a, void* stream) {
   using namespace wg4;
   P p;
-  p.x = (const char*)a.x; p.dz = (const char*)a.dz; p.x_ld = a.x_ld; p.dz_ld = a.dz_ld;
-  p.N = a.N; p.Hi = a.Hi; p.Wi = a.Wi; p.Cin = a.Cin_pad; p.Ho = a.Ho; p.Wo = a.Wo; p.Cout = a.Cout_pad;
-  p.KH = a.KH; p.KW = a.KW; p.stride = a.stride; p.pad = a.pad; p.dil = a.dil;
-  p.M = (long)a.N * a.Ho * a.Wo;
-  p.Ktot = a.KH * a.KW * a.Cin_pad;
+  dy_route::fill_wgrad_problem(p, a);
   p.x_bytes = (unsigned)((((long)a.N * a.Hi * a.Wi - 1) * a.x_ld + a.Cin_pad) * 2);
   p.dz_bytes = (unsigned)(((p.M - 1) * a.dz_ld + a.Cout_pad) * 2);
-  p.part = a.scratch;
   p.tiles_q = dy_cdiv(a.Cout_pad, BQ);
   p.tiles = dy_cdiv(p.Ktot, BP) * p.tiles_q;
-  // one round of blocks over the 256 CUs, at least 8 K-steps each, slabs must fit the workspace
-  long splits = 256 / p.tiles;
-  const long max_splits = (p.M + 8L * BKP - 1) / (8L * BKP);
-  if (splits > max_splits) splits = max_splits;
+  // one round of blocks over the 256 CUs (rounded down: never a second round), at least 8 K-steps each, slabs must fit the workspace
+  // (dy_wgrad_v4_eligible saw to room for two splits); the blocks are a 1-D grid
   const long fit = a.scratch_elems / ((long)p.tiles * BP * BQ);
-  if (splits > fit) splits = fit;
-  if (splits < 1) splits = 1;
-  long chunk = (p.M + splits - 1) / splits;
-  chunk = (chunk + BKP - 1) / BKP * BKP;
-  splits = (p.M + chunk - 1) / chunk;
-  p.chunk = chunk;
-  p.nblk = (int)(splits * p.tiles);
+  const dy_route::WgradSplits plan = dy_route::plan_wgrad_splits(p.M, 256 / p.tiles, 8L * BKP, BKP, fit, dy_route::kNoGridCap);
+  p.chunk = plan.chunk;
+  p.nblk = (int)(plan.splits * p.tiles);
   p.q64_w = BKP / a.Wo; p.r64_w = BKP % a.Wo;
   p.q_h = p.q64_w / a.Ho; p.r_h = p.q64_w % a.Ho;
   const bool pointwise = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
   constexpr int SHMEM = 2 * BUF;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<false, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<true, bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<false, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<true, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, SHMEM);
-    if (e != hipSuccess) {
-      dy_set_error("wgrad_v4: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return 3;
-    }
-    configured = true;
-  }
+  // all four instantiations at the first launch of any
+  if (int e = dy_raise_lds_limit("wgrad_v4", {{&wgrad_kernel<false, bf16_t>, SHMEM}, {&wgrad_kernel<true, bf16_t>, SHMEM},
+                                              {&wgrad_kernel<false, f16_t>, SHMEM}, {&wgrad_kernel<true, f16_t>, SHMEM}}))
+    return e;
   hipStream_t st = (hipStream_t)stream;
   dy_note_kernel("wg4::wgrad_kernel+reduce_kernel");
-  if (a.dtype == DY_F16) {
-    if (pointwise) wgrad_kernel<true, f16_t><<<p.nblk, 512, SHMEM, st>>>(p);
-    else wgrad_kernel<false, f16_t><<<p.nblk, 512, SHMEM, st>>>(p);
-  } else {
-    if (pointwise) wgrad_kernel<true, bf16_t><<<p.nblk, 512, SHMEM, st>>>(p);
-    else wgrad_kernel<false, bf16_t><<<p.nblk, 512, SHMEM, st>>>(p);
-  }
-  DY_LAUNCH_CHECK();
-  reduce_kernel<<<dim3(dy_cdiv(a.Cin, 256), a.Cout, a.KH * a.KW), 256, 0, st>>>(a.scratch, (int)splits, p.tiles, p.tiles_q, a.Cout, a.Cin, a.Cin_pad, a.KH * a.KW, a.g_oihw);
+  if (int e = dy_dispatch_16bit("wgrad_v4", a.dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (pointwise) wgrad_kernel<true, T><<<p.nblk, 512, SHMEM, st>>>(p);
+        else wgrad_kernel<false, T><<<p.nblk, 512, SHMEM, st>>>(p);
+        DY_LAUNCH_CHECK();
+        return 0;
+      }))
+    return e;
+  reduce_kernel<<<dim3(dy_cdiv(a.Cin, 256), a.Cout, a.KH * a.KW), 256, 0, st>>>(a.scratch, (int)plan.splits, p.tiles, p.tiles_q, a.Cout, a.Cin, a.Cin_pad, a.KH * a.KW, a.g_oihw);
   DY_LAUNCH_CHECK();
   return 0;
 }

@@ -100,8 +100,6 @@ typedef struct {
 } dy_pack_item;
 int64_t dy_pack_item_blocks(int Cout_pad, int Cin_pad, int KH, int KW);
 int dy_pack_weights_multi(const dy_pack_item* items_dev, int n_items, int64_t n_blocks, void* stream);
-/* packed f32 grad [Cout][KH][KW][Cin_pad] -> OIHW f32 (overwrite) */
-int dy_unpack_wgrad(const float* dw_packed, float* g_oihw, int Cout, int Cin, int Cin_pad, int KH, int KW, void* stream);
 
 /* ------------------------------------------------------------------------------------ BatchNorm + activation
  * Replaces nn.BatchNorm2d (train: batch statistics, eps 1e-3, momentum 0.03, U/utils/torch_utils.py:263-265) followed by

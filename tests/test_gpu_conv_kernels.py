@@ -325,3 +325,64 @@ def test_big_output_epilogue_non_temporal_stores(mode):
     if mode == "add":
         ref = ref + addend.float()
     assert _err(y.float(), ref) < 1e-2
+
+
+# One case per weight-gradient route and tile variant: dtype, (B, Cin, Cout, H, W, k, s, p), expected kernel, the smallest
+# scratch_elems at which the route is still taken (its slab set, or what its eligibility asks for), and whether one float less is the
+# route's own "scratch too small" error (the wgrad_v3 / wgrad_v4 predicates hand such a problem to the next route instead).
+_BF16, _F16 = torch.bfloat16, torch.float16
+WGRAD_PLAN = [
+    (torch.float32, (2, 16, 32, 48, 40, 3, 1, 1), "conv_wgrad_kernel", 8192, True),         # 2 tiles of 32 x 128
+    (_BF16, (4, 32, 32, 40, 40, 3, 1, 1), "conv_wgrad_kernel", 12288, True),                # 3 tiles of 32 x 128
+    (_BF16, (4, 64, 64, 32, 32, 3, 1, 1), "wg2::wgrad_kernel<128, 128, 2>", 81920, True),   # 5 tiles of 128 x 128
+    (_F16, (4, 64, 64, 32, 32, 3, 1, 1), "wg2::wgrad_kernel<128, 128, 2>", 81920, True),
+    (_BF16, (4, 64, 256, 32, 32, 3, 1, 1), "wg2::wgrad_kernel<256, 256, 2>", 196608, True), # 3 tiles of 256 x 256
+    (_BF16, (4, 256, 256, 64, 64, 1, 1, 0), "wg4::wgrad_kernel", 131072, False),            # pointwise; two splits' worth of one tile
+    (_F16, (4, 256, 256, 64, 64, 1, 1, 0), "wg4::wgrad_kernel", 131072, False),
+    (_BF16, (4, 56, 256, 64, 64, 3, 1, 1), "wg4::wgrad_kernel", 262144, False),             # two splits' worth of two tiles
+    (_BF16, (8, 64, 64, 128, 128, 3, 1, 1), "wg3::wgrad_kernel<64>", 294912, False),        # one block per image
+    (_F16, (8, 64, 64, 128, 128, 3, 1, 1), "wg3::wgrad_kernel<64>", 294912, False),
+]
+_WGRAD_BOUND = {torch.float32: 1e-5, torch.bfloat16: 1e-2, torch.float16: 2e-3}
+
+
+@pytest.mark.parametrize("dtype,shape,kernel,min_scratch,own_error", WGRAD_PLAN,
+                         ids=[_DTYPE_NAME[c[0]] + ":" + "x".join(map(str, c[1])) for c in WGRAD_PLAN])
+def test_wgrad_routes_plan_edges(dtype, shape, kernel, min_scratch, own_error):
+    """dy_conv2d_wgrad called directly, per route and tile variant, with the default 32 Mi-float scratch and with scratch_elems cut to
+    the smallest value at which the route is still taken (the shared split plan's "clamped by what fits" branch): the expected kernel
+    ran, dW is within the file's bounds of F.conv2d's on the rounded operands, and a repeat gives the same bits (the slabs are added in
+    a fixed order).  One float less is "scratch too small" for the routes that plan from the scratch they are given."""
+    from dedark_yolo_amd import _C, ops
+    B, Cin, Cout, H, W, k, s, p = shape
+    torch.manual_seed(B * 1000 + Cin + Cout + H)
+    x = ops.as_nhwc(torch.randn(B, Cin, H, W, device="cuda"), dtype)
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    dz = ops.as_nhwc(torch.randn(B, Cout, Ho, Wo, device="cuda"), dtype)
+    w0 = torch.zeros(Cout, Cin, k, k, device="cuda", requires_grad=True)
+    F.conv2d(x.float(), w0, None, s, p).backward(dz.float())
+    ref = w0.grad
+    st = ops.stream()
+    scratch = ops.wgrad_scratch(x.device, tag=st)
+    assert scratch.numel() == 32 << 20
+    ve = ops.vec_elems(dtype)
+    assert Cin % ve == 0 and Cout % ve == 0          # no channel padding in these cases
+
+    def run(elems):
+        gw = torch.full((Cout, Cin, k, k), float("nan"), device="cuda")
+        _C.lib().dy_clear_last_kernel()
+        _C.call("dy_conv2d_wgrad", ops.ptr(x), ops.ld_of(x), B, H, W, Cin, ops.ptr(dz), ops.ld_of(dz), Ho, Wo, Cout, k, k, s, p, 1, Cout, Cin,
+                ops.ptr(scratch), elems, ops.ptr(gw), ops.dt_id(dtype), st)
+        return gw, _C.lib().dy_last_kernel().decode()
+
+    for elems in (scratch.numel(), min_scratch):
+        gw, sym = run(elems)
+        assert sym.startswith(kernel), (elems, sym)
+        err = _err(gw, ref)
+        print(f"{_DTYPE_NAME[dtype]} {shape} scratch_elems={elems}: {sym} err={err:.3g}")
+        assert err < _WGRAD_BOUND[dtype], (elems, err)
+        again, _ = run(elems)
+        assert torch.equal(gw, again), elems
+    if own_error:
+        with pytest.raises(RuntimeError, match="scratch too small"):
+            run(min_scratch - 1)
