@@ -189,6 +189,8 @@ _SIGS = {
     "dy_cls_softmax": [vp, i64, i32, i32, i32, vp, vp],
     "dy_cls_topk": [vp, i64, i32, i32, i32, i32, vp, vp],
     "dy_cls_metrics_update": [vp, i32, vp, i32, i32, vp, vp, vp],
+    "dy_val_box_match": [vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp],
+    "dy_val_iou_match": [vp, i64, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp],
 }
 
 _lib = None

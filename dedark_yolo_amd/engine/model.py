@@ -51,6 +51,7 @@ class YOLO:
             raise NotImplementedError("only the detect, segment, pose and classify tasks are on the Dedark-YOLO hot path")
         self.task = task
         self.trainer = None
+        self.validator = None
         self.overrides = {}
         suffix = Path(str(model)).suffix
         if suffix == ".yaml":
@@ -178,7 +179,8 @@ class YOLO:
             torch.cuda.set_device(dev)
             loader = build_val_loader(args, data, self.task, dev, getattr(args, "split", None) or "val",
                                       stride=max(int(self.model.stride.max()), 32))
-        return all_tasks()[self.task][2](args)(self.model, loader)
+        self.validator = all_tasks()[self.task][2](args)        # kept: confusion_matrix, nt_per_class, stats, print_results()
+        return self.validator(self.model, loader)
 
     @torch.no_grad()
     def predict(self, source, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, orig_shapes=None, retina_masks=None, augment=False,

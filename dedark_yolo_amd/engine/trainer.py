@@ -305,6 +305,7 @@ class DetectionTrainer:
         self.world_size = int(os.environ.get("WORLD_SIZE", 1))
         self.device = torch.device("cuda", self.local_rank)
         self.model = None
+        self.validator = None              # the validator of the last validate()
         self.flat = None
         self.buckets = None
         self.updates = 0
@@ -669,7 +670,8 @@ class DetectionTrainer:
         dt = ops.get_compute_dtype()
         try:
             with self.ema_weights() as model:
-                metrics = V(self.args)(model, val_loader, dtype=torch.float32)
+                self.validator = V(self.args)
+                metrics = self.validator(model, val_loader, dtype=torch.float32)
         finally:
             ops.set_compute_dtype(dt)
             self.model.train()

@@ -2,9 +2,13 @@
 ultralytics/models/yolo/detect/val.py:30-174): preprocess -> model (eval) -> batched HIP NMS -> per-image greedy matching at
 10 IoU thresholds -> AP per class / mAP50 / mAP50-95 / fitness.
 
-The device part (img/255, front-end, network, Detect decode, NMS) stays on the GPU; one D2H copy per batch brings the kept
-detections to the host, where the matching and AP bookkeeping run in numpy exactly as in the reference (val.py:151-174 uses
-numpy for the matching as well)."""
+The device part (img/255, front-end, network, Detect decode, NMS, box scaling, IoU, matching, confusion matrix: csrc/nms.hip,
+csrc/valmatch.hip) stays on the GPU; the detect batch loop copies nothing to the host.  `get_stats` reads the matched-prediction
+table and the confusion matrix back once, and the AP bookkeeping runs in numpy as in the reference."""
+import json
+from pathlib import Path
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -12,7 +16,7 @@ from .. import ops as kops
 from .._C import call
 from ..ops import ptr, stream
 from ..utils import ops
-from ..utils.metrics import ClassifyMetrics, DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou, oks_sigmas
+from ..utils.metrics import LOGGER, ClassifyMetrics, ConfusionMatrix, DetMetrics, PoseMetrics, SegmentMetrics, box_iou, kpt_iou, oks_sigmas
 
 
 def match_predictions(detections, labels, iouv):
@@ -50,10 +54,51 @@ def match_from_iou(iou, label_cls, det_cls, iouv):
     return torch.from_numpy(correct)
 
 
-class DetectionValidator:
-    n_task = 0          # `correct` matrices per image besides the box one (_task_correct)
+def scale_record(img1_shape, img0_shape, ratio_pad=None):
+    """(gain, pad_x, pad_y, h0, w0) of one image exactly as utils/ops.scale_boxes derives them (ops.py:44-56): with `ratio_pad`
+    its ratio_pad[0][0] and ratio_pad[1], else the min / round(... - 0.1) rule.  dy_val_box_match reads the five as f32."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = round((img1_shape[1] - img0_shape[1] * gain) / 2 - 0.1), round((img1_shape[0] - img0_shape[0] * gain) / 2 - 0.1)
+    else:
+        gain = ratio_pad[0][0]
+        pad = ratio_pad[1]
+    return [float(gain), float(pad[0]), float(pad[1]), float(img0_shape[0]), float(img0_shape[1])]
 
-    def __init__(self, args=None, dataloader=None):
+
+def save_one_txt(predn, save_conf, shape, file):
+    """detect/val.py:212-219: one `cls x y w h [conf]` line per row of predn [n, 6] (native-space xyxy, conf, cls; host), the box
+    normalised by the original (h, w) `shape`, every number through %g."""
+    gn = torch.tensor(shape)[[1, 0, 1, 0]]
+    xywh = (ops.xyxy2xywh(predn[:, :4].float()) / gn).tolist()
+    lines = []
+    for (*_, conf, cls), box in zip(predn.tolist(), xywh):
+        line = (cls, *box, conf) if save_conf else (cls, *box)
+        lines.append(("%g " * len(line)).rstrip() % line + "\n")
+    with open(file, "w") as f:
+        f.writelines(lines)
+
+
+def pred_to_json(predn, filename):
+    """detect/val.py:221-232: the COCO-style records of predn [n, 6] (host): image_id = the integer stem when it is numeric, bbox =
+    top-left xywh rounded to 3 places, score rounded to 5, category_id = the class."""
+    stem = Path(filename).stem
+    image_id = int(stem) if stem.isnumeric() else stem
+    box = ops.xyxy2xywh(predn[:, :4].float())
+    box[:, :2] -= box[:, 2:] / 2
+    return [dict(image_id=image_id, category_id=int(p[5]), bbox=[round(x, 3) for x in b], score=round(p[4], 5))
+            for p, b in zip(predn.tolist(), box.tolist())]
+
+
+class DetectionValidator:
+    """Detect validator.  Per batch: batched NMS (`postprocess` keeps its padded [B, max_det, 6] rows and counts on the device), then ONE
+    dy_val_box_match launch for the whole batch: native-space boxes, the `correct` matrix at the 10 IoU thresholds and the confusion
+    matrix.  Nothing is copied to the host inside the batch loop; `get_stats` (or the first read of `.stats`) reads everything back
+    once.  `match_predictions` / `match_from_iou` above stay as the host statement of the rule the kernel applies."""
+
+    n_task = 0          # `correct` matrices per image besides the box one (_task_iou)
+
+    def __init__(self, args=None, dataloader=None, save_dir=None):
         from .trainer import get_cfg
         self.args = args if args is not None else get_cfg()
         self.dataloader = dataloader
@@ -62,8 +107,19 @@ class DetectionValidator:
         self.metrics = DetMetrics()
         self.device = None
         self.training = False
+        a = self.args
+        save_dir = save_dir if save_dir is not None else getattr(a, "save_dir", None)
+        if save_dir is None and (getattr(a, "project", None) or getattr(a, "name", None)):
+            save_dir = Path(a.project or "runs") / (a.name or "val")
+        self.save_dir = None if save_dir is None else Path(save_dir)
+        self.confusion_matrix = None
+        self.nt_per_class = None
+        self.jdict = []
         # engine/validator.py:86-87: conf None -> 0.001; this fork's default.yaml:48 sets conf 0.25, which therefore applies
         self.conf = 0.001 if getattr(self.args, "conf", None) is None else self.args.conf
+
+    def _flag(self, name, default=False):
+        return bool(getattr(self.args, name, default))
 
     # ------------------------------------------------------------------------------------------ per batch
     def preprocess(self, batch):
@@ -79,10 +135,16 @@ class DetectionValidator:
         return batch
 
     def postprocess(self, preds, nc=0):
-        """NMS on the eval output; `nc` = the class count when task columns follow the class scores (segment, pose)."""
+        """NMS on the eval output.  Detect (nc == 0): the padded rows [B, max_det, 6] and the counts [B] as nms_batched leaves them,
+        both on the device.  `nc` = the class count when task columns follow the class scores (segment, pose): the per-image list of
+        non_max_suppression, whose counts those validators need on the host anyway."""
         a = self.args
-        return ops.non_max_suppression(preds, self.conf, a.iou, multi_label=True, agnostic=bool(getattr(a, "single_cls", False)),
-                                       max_det=a.max_det, nc=nc)
+        if nc:
+            return ops.non_max_suppression(preds, self.conf, a.iou, multi_label=True, agnostic=self._flag("single_cls"), max_det=a.max_det,
+                                           nc=nc)
+        if isinstance(preds, (list, tuple)):
+            preds = preds[0]
+        return ops.nms_batched(preds, self.conf, a.iou, True, self._flag("single_cls"), a.max_det, 30000, 7680)
 
     def init_metrics(self, model):
         self.nc = model.model[-1].nc
@@ -90,52 +152,154 @@ class DetectionValidator:
         self.metrics.names = self.names
         self.seen = 0
         self.stats = []
+        self.jdict = []
+        self.confusion_matrix = ConfusionMatrix(nc=self.nc)
+        self._confusion = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int32, device=self.device)
+        self._iouv_dev = self.iouv.to(self.device)
+
+    # `stats`: one row per image that has predictions or labels -- (correct matrices ..., conf, predicted cls, label cls), host tensors.
+    # update_metrics only queues device tensors; the rows are built, with one read-back for everything queued, when they are first read.
+    @property
+    def stats(self):
+        if self._pending:
+            self._rows.extend(self._read_back(self._pending))
+            self._pending = []
+        return self._rows
+
+    @stats.setter
+    def stats(self, rows):
+        self._rows, self._pending = list(rows), []
+
+    def _read_back(self, pending):
+        def host(parts):
+            dev = [p for p in parts if p.is_cuda]                 # one copy for all of them
+            if dev:
+                flat = iter(torch.cat([p.reshape(-1) for p in dev]).cpu().split([p.numel() for p in dev]))
+                parts = [next(flat).view(p.shape) if p.is_cuda else p for p in parts]
+            return parts
+        n_cor = 1 + self.n_task
+        cors = [host([q["correct"][k] for q in pending]) for k in range(n_cor)]
+        ccs = host([q["cc"] for q in pending])
+        cnts = [q["lens"] for q in pending]
+        if any(c is None for c in cnts):
+            got = iter(host([q["cnt"] for q in pending if q["lens"] is None]))
+            cnts = [c if c is not None else next(got).tolist() for c in cnts]
+        tcls = host([q["tcls"] for q in pending])
+        loffs = [q["loff_h"] for q in pending]
+        if any(l is None for l in loffs):
+            got = iter(host([q["loff"] for q in pending if q["loff_h"] is None]))
+            loffs = [l if l is not None else next(got).tolist() for l in loffs]
+        rows = []
+        for i in range(len(pending)):
+            for b, n in enumerate(cnts[i]):
+                l0, l1 = loffs[i][b], loffs[i][b + 1]
+                if n == 0 and l1 == l0:
+                    continue
+                rows.append((*(cors[k][i][b, :n].bool() for k in range(n_cor)), ccs[i][b, :n, 0], ccs[i][b, :n, 1], tcls[i][l0:l1]))
+        return rows
 
     def update_metrics(self, preds, batch):
-        """val.py:72-116 on host copies.  Per image one row of `self.stats`: the box `correct` matrix, the task's own ones
-        (`_task_correct`; `n_task` of them), confidences, predicted classes, label classes."""
-        bi = batch["batch_idx"].cpu()
-        cls_all, box_all = batch["cls"].cpu().float(), batch["bboxes"].cpu().float()
+        """val.py:72-116 for the whole batch in one launch.  preds: postprocess' (rows [B, max_det, >= 6], counts [B]) pair, or a list of
+        per-image [n, >= 6] tensors (non_max_suppression)."""
+        dev = self.device
+        if isinstance(preds, tuple) and len(preds) == 2 and torch.is_tensor(preds[0]) and preds[0].dim() == 3:
+            det, cnt, lens = preds[0].float().contiguous(), preds[1], None
+        else:
+            lens = [int(p.shape[0]) for p in preds]
+            det = torch.zeros((len(preds), max(lens + [1]), preds[0].shape[1] if len(preds) else 6), dtype=torch.float32, device=dev)
+            for i, p in enumerate(preds):
+                if lens[i]:
+                    det[i, :lens[i]] = p
+            cnt = torch.tensor(lens, dtype=torch.int32).to(dev)
+        B = det.shape[0]
         height, width = batch["img"].shape[2:]
-        for si, pred in enumerate(preds):
-            pred = pred.cpu()
-            idx = bi == si
-            cls, bbox = cls_all[idx], box_all[idx]
-            nl, npr = cls.shape[0], pred.shape[0]
-            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
-            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
-            correct = [torch.zeros(npr, self.niou, dtype=torch.bool) for _ in range(1 + self.n_task)]
-            self.seen += 1
-            if npr == 0:
-                if nl:
-                    self.stats.append((*correct, torch.zeros(0), torch.zeros(0), cls.squeeze(-1)))
-                continue
-            if getattr(self.args, "single_cls", False):
-                pred[:, 5] = 0
-            predn = pred.clone()
-            ops.scale_boxes((height, width), predn[:, :4], shape, ratio_pad=ratio_pad)
-            if nl:
-                tbox = ops.xywh2xyxy(bbox) * torch.tensor((width, height, width, height), dtype=torch.float32)
-                ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
-                labelsn = torch.cat((cls, tbox), 1)
-                correct = [match_predictions(predn, labelsn, self.iouv),
-                           *self._task_correct(batch, si, idx, predn, labelsn, shape, ratio_pad)]
-            self.stats.append((*correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
+        single = self._flag("single_cls")
+        # the labels sorted by image (stable: the order inside an image stays), on whichever device they live
+        bi = batch["batch_idx"].reshape(-1).float()
+        order = torch.argsort(bi, stable=True)
+        loff = torch.searchsorted(bi[order].contiguous(), torch.arange(B + 1, dtype=torch.float32, device=bi.device)).to(torch.int32)
+        tcls = batch["cls"].reshape(-1).float()[order.to(batch["cls"].device)]
+        lxywh = batch["bboxes"].reshape(-1, 4).float()[order.to(batch["bboxes"].device)]
+        rec = torch.tensor([scale_record((height, width), batch["ori_shape"][si] if "ori_shape" in batch else (height, width),
+                                         batch["ratio_pad"][si] if "ratio_pad" in batch else None) for si in range(B)],
+                           dtype=torch.float32).view(B, 5).to(dev)
+        lcls, loff_d = tcls.to(dev), loff.to(dev)
+        cm = self.confusion_matrix
+        correct, predn, tboxn = kops.val_box_match(det, cnt, lcls, lxywh.to(dev), loff_d, (height, width), rec, self._iouv_dev, single,
+                                                   self._confusion, cm.conf, cm.iou_thres)
+        ctx = SimpleNamespace(det=det, cnt=cnt, lens=lens, lcls=lcls, loff=loff_d, order=order, height=height, width=width,
+                              loff_h=None if loff.is_cuda else loff.tolist())
+        task = self._task_correct(batch, ctx) if self.n_task else ()
+        cc = det[:, :, 4:6].contiguous()
+        if single:
+            cc[:, :, 1] = 0
+        self._pending.append(dict(correct=(correct, *task), cc=cc, cnt=cnt, lens=lens, tcls=tcls, loff=loff, loff_h=ctx.loff_h))
+        self.seen += B
+        save_json = self._flag("save_json") and self.n_task == 0
+        if self._flag("save_txt") or save_json:
+            self._save_predictions(batch, torch.cat((predn, cc), 2), cnt if lens is None else lens, save_json)
 
-    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
-        """The task's own `correct` matrices of image `si` (labels `idx` of the batch; predn / labelsn scaled to `shape`)."""
+    def _task_correct(self, batch, ctx):
+        """The task's own `correct` matrices of the batch: uint8 [B, max_det, niou] device tensors, `n_task` of them."""
         return ()
 
+    def _match_iou(self, mats, ctx):
+        """One dy_val_iou_match for the batch: mats[b] = the device IoU matrix [labels of image b, its detections], or None for an image
+        without labels or without detections."""
+        dev = self.device
+        sizes = [0 if m is None else m.numel() for m in mats]
+        moff = torch.tensor([sum(sizes[:b]) for b in range(len(mats))], dtype=torch.int64).to(dev)
+        live = [m.reshape(-1) for m in mats if m is not None and m.numel()]
+        flat = torch.cat(live) if live else torch.zeros(1, dtype=torch.float32, device=dev)
+        return kops.val_iou_match(flat.float().contiguous(), moff, ctx.det, ctx.cnt, ctx.lcls, ctx.loff, self._iouv_dev,
+                                  self._flag("single_cls"))
+
+    def _save_predictions(self, batch, predn, counts, save_json):
+        """save_txt -> save_dir/labels/<stem>.txt, save_json -> records for save_dir/predictions.json (val.py:111-116).  This is the one
+        place where a batch's predictions are read back inside the loop."""
+        if "im_file" not in batch or self.save_dir is None:
+            raise ValueError("save_txt / save_json need the batch's 'im_file' names and a save_dir (save_dir=, or project= / name=)")
+        predn = predn.cpu()
+        counts = counts.tolist() if torch.is_tensor(counts) else counts
+        height, width = batch["img"].shape[2:]
+        if self._flag("save_txt"):
+            (self.save_dir / "labels").mkdir(parents=True, exist_ok=True)
+        for si, n in enumerate(counts):
+            if n == 0:
+                continue
+            if save_json:
+                self.jdict.extend(pred_to_json(predn[si, :n], batch["im_file"][si]))
+            if self._flag("save_txt"):
+                shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
+                save_one_txt(predn[si, :n], self._flag("save_conf"), shape, self.save_dir / "labels" / f"{Path(batch['im_file'][si]).stem}.txt")
+
     def get_stats(self):
-        """val.py:123-129"""
-        if not self.stats:
+        """val.py:118-129: the one read-back of the run (the queued `correct` / confidence / class tensors and the confusion matrix)."""
+        rows = self.stats
+        self.confusion_matrix.matrix = self._confusion.cpu().numpy().astype(np.float64)
+        self.metrics.confusion_matrix = self.confusion_matrix
+        if self._flag("save_json") and self.n_task == 0 and self.jdict:
+            self.save_dir.mkdir(parents=True, exist_ok=True)
+            with open(self.save_dir / "predictions.json", "w") as f:
+                json.dump(self.jdict, f)
+        if not rows:
             self.nt_per_class = np.zeros(self.nc, dtype=int)
             return self.metrics.results_dict
-        stats = [torch.cat(x, 0).numpy() for x in zip(*self.stats)]
+        stats = [torch.cat(x, 0).numpy() for x in zip(*rows)]
         if len(stats) and stats[0].any():
             self.metrics.process(*stats)
         self.nt_per_class = np.bincount(stats[-1].astype(int), minlength=self.nc)
         return self.metrics.results_dict
+
+    def print_results(self):
+        """val.py:131-142: the `all` row, then with `verbose`, outside training and nc > 1 one row per class that has labels."""
+        pf = "%22s" + "%11i" * 2 + "%11.3g" * len(self.metrics.keys)
+        LOGGER.info(pf % ("all", self.seen, self.nt_per_class.sum(), *self.metrics.mean_results()))
+        if self.nt_per_class.sum() == 0:
+            LOGGER.warning(f"WARNING no labels found in {getattr(self.args, 'task', 'detect')} set, can not compute metrics without labels")
+        if self._flag("verbose", True) and not self.training and self.nc > 1 and len(self.stats):
+            for i, c in enumerate(self.metrics.ap_class_index):
+                LOGGER.info(pf % (self.names[c], self.seen, self.nt_per_class[c], *self.metrics.class_result(i)))
 
     # ------------------------------------------------------------------------------------------ loop
     @torch.no_grad()
@@ -159,14 +323,16 @@ class DetectionValidator:
             preds = self.postprocess(preds)
             self.update_metrics(preds, batch)
         stats = self.get_stats()
+        self.print_results()
         model.train(was_training)
         return {k: float(v) for k, v in stats.items()}
 
 
 class SegmentationValidator(DetectionValidator):
     """Segment validator (reference models/yolo/segment/val.py): NMS with the mask-coefficient columns, predicted masks of the whole
-    batch in one launch, mask IoU against the gt masks with integer counts (dy_seg_mask_iou), box and mask `correct` matrices by
-    the same matching rule, SegmentMetrics.  `process` as in init_metrics (val.py:31-39): save_json False -> process_mask at the
+    batch in one launch, mask IoU against the gt masks with integer counts (dy_seg_mask_iou), the box `correct` matrices and the
+    confusion matrix from dy_val_box_match, the mask ones from one dy_val_iou_match on the batch's mask-IoU matrices, SegmentMetrics.
+    `process` as in init_metrics (val.py:31-39): save_json False -> process_mask at the
     proto resolution (dy_seg_mask_decode), save_json True -> process_mask_upsample at the input resolution
     (dy_seg_mask_upsample).  gt masks (index maps or planes) at another resolution than the predicted masks are resized
     bilinearly and thresholded at 0.5 (val.py:146-148; dy_mask_resize).  Writing predictions.json itself (RLE through pycocotools,
@@ -174,8 +340,8 @@ class SegmentationValidator(DetectionValidator):
 
     n_task = 1
 
-    def __init__(self, args=None, dataloader=None):
-        super().__init__(args, dataloader)
+    def __init__(self, args=None, dataloader=None, save_dir=None):
+        super().__init__(args, dataloader, save_dir)
         self.args.task = "segment"
         self.metrics = SegmentMetrics()
 
@@ -190,27 +356,35 @@ class SegmentationValidator(DetectionValidator):
         pmasks = ops.process_masks_batched(proto, [d[:, :6 + proto.shape[1]] for d in dets], (height, width), mode=mode)
         super().update_metrics(dets, dict(batch, masks=batch["masks"].to(self.device, non_blocking=True), pmasks=pmasks))
 
-    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
-        overlap, masks = bool(getattr(self.args, "overlap_mask", True)), batch["masks"]
-        gt = masks[si] if overlap else masks[idx.to(masks.device)]
-        pred, m = batch["pmasks"][si], labelsn.shape[0]
-        if tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]) and m:
-            gt = ops.resize_masks(gt, pred.shape[-2:], m=m if overlap else None)       # -> uint8 planes [m, h, w]
-            overlap = False
-        iou_m = ops.mask_iou_binary(gt, pred, overlap, m).cpu().numpy()
-        return (match_from_iou(iou_m, labelsn[:, 0], predn[:, 5], self.iouv),)
+    def _task_correct(self, batch, ctx):
+        masks = batch["masks"]
+        loff = ctx.loff_h if ctx.loff_h is not None else ctx.loff.tolist()
+        mats = []
+        for si, n in enumerate(ctx.lens):
+            m = loff[si + 1] - loff[si]
+            if n == 0 or m == 0:
+                mats.append(None)
+                continue
+            overlap = bool(getattr(self.args, "overlap_mask", True))
+            gt = masks[si] if overlap else masks[ctx.order[loff[si]:loff[si + 1]].to(masks.device)]
+            pred = batch["pmasks"][si]
+            if tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]):
+                gt = ops.resize_masks(gt, pred.shape[-2:], m=m if overlap else None)       # -> uint8 planes [m, h, w]
+                overlap = False
+            mats.append(ops.mask_iou_binary(gt, pred, overlap, m))
+        return (self._match_iou(mats, ctx),)
 
 
 class PoseValidator(DetectionValidator):
     """Pose validator (reference models/yolo/pose/val.py): NMS with multi_label and the K * ndim keypoint columns appended,
     boxes (scale_boxes) and keypoints (scale_coords) to ori_shape / ratio_pad, OKS against the gt keypoints in native space with
-    area = gt box w * h * 0.53 (kpt_iou on dy_kpt_oks), box and pose `correct` matrices by the same matching rule, PoseMetrics.
-    sigma = metrics.oks_sigmas(kpt_shape)."""
+    area = gt box w * h * 0.53 (kpt_iou on dy_kpt_oks), the box `correct` matrices and the confusion matrix from dy_val_box_match, the
+    pose ones from one dy_val_iou_match on the batch's OKS matrices, PoseMetrics.  sigma = metrics.oks_sigmas(kpt_shape)."""
 
     n_task = 1
 
-    def __init__(self, args=None, dataloader=None):
-        super().__init__(args, dataloader)
+    def __init__(self, args=None, dataloader=None, save_dir=None):
+        super().__init__(args, dataloader, save_dir)
         self.args.task = "pose"
         self.metrics = PoseMetrics()
 
@@ -223,24 +397,38 @@ class PoseValidator(DetectionValidator):
         return super().postprocess(preds, nc=self.nc)
 
     def update_metrics(self, preds, batch):
-        """val.py:62-109 on host copies (the OKS matrix on the device)."""
+        """val.py:62-109: the keypoints are scaled on host copies (one per batch), the OKS matrices stay on the device."""
         if "keypoints" not in batch:
             raise ValueError("pose validation: the batch has no 'keypoints'")
         super().update_metrics(preds, dict(batch, keypoints=batch["keypoints"].cpu().float()))
 
-    def _task_correct(self, batch, si, idx, predn, labelsn, shape, ratio_pad):
-        height, width = batch["img"].shape[2:]
-        kpts = batch["keypoints"][idx]
-        nk = kpts.shape[1] if kpts.dim() == 3 else int(self.kpt_shape[0])
-        pred_kpts = predn[:, 6:].view(predn.shape[0], nk, -1)
-        ops.scale_coords((height, width), pred_kpts, shape, ratio_pad=ratio_pad)
-        tkpts = kpts.clone()
-        tkpts[..., 0] *= width
-        tkpts[..., 1] *= height
-        tkpts = ops.scale_coords((height, width), tkpts, shape, ratio_pad=ratio_pad)
-        area = ops.xyxy2xywh(labelsn[:, 1:])[:, 2:].prod(1) * 0.53
-        oks = kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma).cpu().numpy()
-        return (match_from_iou(oks, labelsn[:, 0], predn[:, 5], self.iouv),)
+    def _task_correct(self, batch, ctx):
+        height, width = ctx.height, ctx.width
+        loff = ctx.loff_h if ctx.loff_h is not None else ctx.loff.tolist()
+        order, pred_h = ctx.order.cpu(), ctx.det.cpu()
+        box_all = batch["bboxes"].cpu().float()
+        mats = []
+        for si, n in enumerate(ctx.lens):
+            m = loff[si + 1] - loff[si]
+            if n == 0 or m == 0:
+                mats.append(None)
+                continue
+            idx = order[loff[si]:loff[si + 1]]
+            shape = batch["ori_shape"][si] if "ori_shape" in batch else (height, width)
+            ratio_pad = batch["ratio_pad"][si] if "ratio_pad" in batch else None
+            kpts = batch["keypoints"][idx]
+            nk = kpts.shape[1] if kpts.dim() == 3 else int(self.kpt_shape[0])
+            pred_kpts = pred_h[si, :n, 6:].clone().view(n, nk, -1)
+            ops.scale_coords((height, width), pred_kpts, shape, ratio_pad=ratio_pad)
+            tkpts = kpts.clone()
+            tkpts[..., 0] *= width
+            tkpts[..., 1] *= height
+            tkpts = ops.scale_coords((height, width), tkpts, shape, ratio_pad=ratio_pad)
+            tbox = ops.xywh2xyxy(box_all[idx]) * torch.tensor((width, height, width, height), dtype=torch.float32)
+            ops.scale_boxes((height, width), tbox, shape, ratio_pad=ratio_pad)
+            area = ops.xyxy2xywh(tbox)[:, 2:].prod(1) * 0.53
+            mats.append(kpt_iou(tkpts.to(self.device), pred_kpts.to(self.device), area, self.sigma))
+        return (self._match_iou(mats, ctx),)
 
 
 class ClassificationValidator:

@@ -1198,6 +1198,69 @@ def cls_metrics_update(idx, cls, nc, counts, confusion=None):
         require_gpu(t)
     call("dy_cls_metrics_update", ptr(idx.contiguous()), k, ptr(cls.contiguous()), B, nc, ptr(counts), ptr(confusion), stream())
 
+# ------------------------------------------------------------------------------------------------ validation matching
+VAL_MATCH_SLOTS, VAL_MATCH_LDS = 5, 40 * 1024       # csrc/valmatch.hip: ints of state per detection, bytes of it that LDS holds
+
+
+def _val_match_ws(B, max_det, device):
+    """The global workspace of the per-detection state when it does not fit in LDS (include/dedark_yolo.h), else None."""
+    if max_det * VAL_MATCH_SLOTS * 4 <= VAL_MATCH_LDS:
+        return None
+    return torch.empty(B * max_det * VAL_MATCH_SLOTS, dtype=torch.int32, device=device)
+
+
+def _val_match_args(det, ocnt, lcls, loff, iouv):
+    if det.dim() != 3 or det.dtype != torch.float32 or not det.is_contiguous() or det.shape[1] < 1 or det.shape[2] < 6:
+        raise RuntimeError("val match: det must be a contiguous f32 [B, max_det >= 1, >= 6] tensor (nms_batched's rows)")
+    B = det.shape[0]
+    if ocnt.dtype != torch.int32 or ocnt.numel() != B or loff.dtype != torch.int32 or loff.numel() != B + 1:
+        raise RuntimeError("val match: ocnt int32 [B], loff int32 [B + 1]")
+    if lcls.dtype != torch.float32 or lcls.dim() != 1 or iouv.dtype != torch.float32 or not 1 <= iouv.numel() <= 16:
+        raise RuntimeError("val match: lcls f32 [L], iouv f32 [T <= 16]")
+    for t in (det, ocnt, lcls, loff, iouv):
+        require_gpu(t)
+    return B, det.shape[1], det.shape[2]
+
+
+def val_box_match(det, ocnt, lcls, lxywh, loff, shape, rec, iouv, single_cls=False, confusion=None, conf=0.25, iou_thres=0.45):
+    """dy_val_box_match on one batch (all device tensors): det [B, max_det, >= 6] f32 + ocnt [B] int32 from nms_batched, the labels
+    sorted by image (lcls [L] f32, lxywh [L, 4] f32 normalised, loff [B + 1] int32), shape = the network input (H, W), rec [B, 5] f32
+    = (gain, pad_x, pad_y, h0, w0), iouv [T] f32 -> (correct uint8 [B, max_det, T], predn f32 [B, max_det, 4], tboxn f32 [L, 4]).
+    confusion: int32 [nc + 1, nc + 1] accumulator [predicted][true], updated in place (None: not filled)."""
+    B, max_det, ld = _val_match_args(det, ocnt, lcls, loff, iouv)
+    L, T, dev = lcls.numel(), iouv.numel(), det.device
+    if lxywh.dtype != torch.float32 or tuple(lxywh.shape) != (L, 4) or rec.dtype != torch.float32 or tuple(rec.shape) != (B, 5):
+        raise RuntimeError("val_box_match: lxywh f32 [L, 4], rec f32 [B, 5]")
+    nc = 1
+    if confusion is not None:
+        nc = confusion.shape[0] - 1
+        if confusion.dtype != torch.int32 or tuple(confusion.shape) != (nc + 1, nc + 1) or not confusion.is_contiguous() or nc < 1:
+            raise RuntimeError("val_box_match: confusion must be a contiguous int32 [nc + 1, nc + 1]")
+        require_gpu(confusion)
+    correct = torch.empty((B, max_det, T), dtype=torch.uint8, device=dev)
+    predn = torch.empty((B, max_det, 4), dtype=torch.float32, device=dev)
+    tboxn = torch.empty((L, 4), dtype=torch.float32, device=dev)
+    ws = _val_match_ws(B, max_det, dev)
+    call("dy_val_box_match", ptr(det), ld, ptr(ocnt), B, max_det, ptr(lcls.contiguous()), ptr(lxywh.contiguous()), ptr(loff.contiguous()),
+         L, int(shape[0]), int(shape[1]), ptr(rec.contiguous()), ptr(iouv.contiguous()), T, int(bool(single_cls)), float(conf),
+         float(iou_thres), nc, ptr(correct), ptr(predn), ptr(tboxn), ptr(confusion), ptr(ws), stream())
+    return correct, predn, tboxn
+
+
+def val_iou_match(iou, moff, det, ocnt, lcls, loff, iouv, single_cls=False):
+    """dy_val_iou_match: iou = the batch's [M_b, N_b] f32 matrices packed one after another (f32 [sum M_b * N_b]), moff int64 [B] their
+    offsets; the other arguments as val_box_match -> correct uint8 [B, max_det, T]."""
+    B, max_det, ld = _val_match_args(det, ocnt, lcls, loff, iouv)
+    if iou.dtype != torch.float32 or not iou.is_contiguous() or moff.dtype != torch.int64 or moff.numel() != B:
+        raise RuntimeError("val_iou_match: iou contiguous f32, moff int64 [B]")
+    require_gpu(moff)
+    T, dev = iouv.numel(), det.device
+    correct = torch.empty((B, max_det, T), dtype=torch.uint8, device=dev)
+    ws = _val_match_ws(B, max_det, dev)
+    call("dy_val_iou_match", ptr(iou), iou.numel(), ptr(moff.contiguous()), ptr(det), ld, ptr(ocnt), B, max_det, ptr(lcls.contiguous()),
+         ptr(loff.contiguous()), lcls.numel(), ptr(iouv.contiguous()), T, int(bool(single_cls)), ptr(correct), ptr(ws), stream())
+    return correct
+
 # ------------------------------------------------------------------------------------------------ ConvTranspose2d(k=2, s=2)
 class ConvTCtx:
     __slots__ = ("x", "weight", "bias")

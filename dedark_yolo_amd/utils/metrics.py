@@ -8,9 +8,12 @@ Organisation (own design, checked against the reference's values in tests/golden
   * `envelope_area` integrates the monotone precision envelope on the 101-point grid for every IoU threshold of a class at once;
   * `BoxSummary` stores the per-class arrays and derives every reported number from one table of reductions.
 """
+import logging
+
 import numpy as np
 import torch
 
+LOGGER = logging.getLogger("dedark_yolo_amd")
 _CONF_GRID = np.linspace(0.0, 1.0, 1000)       # confidence axis of the P / R / F1 curves
 _REC_GRID = np.linspace(0.0, 1.0, 101)         # recall axis of the AP integral (COCO-style 101 points)
 _trapezoid = getattr(np, "trapezoid", None) or np.trapz
@@ -296,6 +299,68 @@ class ClassifyMetrics:
     @property
     def results_dict(self):
         return dict(zip(self.keys + ["fitness"], [self.top1, self.top5, self.fitness]))
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (metrics.py:177-317, without the plot): `.matrix` float64 [nc + 1, nc + 1] indexed
+    [predicted][true] with the background last (task 'detect'; [nc, nc] for 'classify'), `process_batch`, `process_cls_preds`,
+    `tp_fp()`, `print()`.
+
+    `process_batch(detections [N, 6] (xyxy, conf, cls), labels [M, 5] (cls, xyxy))` on host tensors is the host statement of the rule
+    that dy_val_box_match applies on the device (the validators fill `.matrix` from that kernel's int32 accumulator):
+      * only detections with conf > self.conf count, the candidates are the pairs with IoU > self.iou_thres, whatever their classes
+        (both comparisons strict, in f32);
+      * every counted detection keeps the label it overlaps most, every label then keeps the best-overlapping detection that chose it;
+      * a matched label adds 1 at [det cls][gt cls], an unmatched one at [nc][gt cls]; a counted detection without a label adds 1 at
+        [det cls][nc], but only in an image that has at least one match; an image without labels adds nothing (both as the reference
+        does); `detections=None` with labels = the classes [M]: every label is unmatched.  Classes are truncated like int().
+    Exact IoU ties, which the reference's `argsort()[::-1]` leaves to the sort's implementation: a detection prefers the LOWER label
+    index, a label the LOWER detection index."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, task="detect"):
+        self.task = task
+        self.matrix = np.zeros((nc + 1, nc + 1)) if task == "detect" else np.zeros((nc, nc))
+        self.nc, self.conf, self.iou_thres = nc, conf, iou_thres
+
+    def process_cls_preds(self, preds, targets):
+        """metrics.py:197-207: preds = list of [n, k] top-k class indices, targets = list of [n] classes."""
+        preds, targets = torch.cat(list(preds))[:, 0], torch.cat(list(targets))
+        np.add.at(self.matrix, (preds.cpu().numpy().astype(int), targets.cpu().numpy().astype(int)), 1)
+
+    def process_batch(self, detections, labels):
+        nc = self.nc
+        labels = torch.as_tensor(labels).detach().cpu().float()
+        if detections is None:
+            np.add.at(self.matrix, (nc, labels.view(-1).numpy().astype(int)), 1)
+            return
+        detections = torch.as_tensor(detections).detach().cpu().float()
+        detections = detections[detections[:, 4].numpy() > np.float32(self.conf)]
+        gt_cls, det_cls = labels[:, 0].numpy().astype(int), detections[:, 5].numpy().astype(int)
+        n_lab, n_det = len(gt_cls), len(det_cls)
+        winner = np.full(n_lab, -1)                                   # per label: the detection it is matched with
+        if n_lab and n_det:
+            iou = box_iou(labels[:, 1:], detections[:, :4]).numpy()
+            cand = iou > np.float32(self.iou_thres)
+            chosen = np.where(cand, iou, -1.0).argmax(0)              # first maximum: the lower label index on a tie
+            mine = cand.any(0)[None, :] & (chosen[None, :] == np.arange(n_lab)[:, None])
+            score = np.where(mine, iou, -1.0)
+            winner = np.where(mine.any(1), score.argmax(1), -1)       # first maximum: the lower detection index on a tie
+        hit = winner >= 0
+        np.add.at(self.matrix, (det_cls[winner[hit]], gt_cls[hit]), 1)
+        np.add.at(self.matrix, (nc, gt_cls[~hit]), 1)
+        if hit.any():
+            free = np.ones(n_det, dtype=bool)
+            free[winner[hit]] = False
+            np.add.at(self.matrix, (det_cls[free], nc), 1)
+
+    def tp_fp(self):
+        tp = self.matrix.diagonal()
+        fp = self.matrix.sum(1) - tp
+        return (tp[:-1], fp[:-1]) if self.task == "detect" else (tp, fp)
+
+    def print(self):
+        for row in self.matrix:
+            LOGGER.info(" ".join(map(str, row)))
 
 
 OKS_SIGMA = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0   # metrics.py:15

@@ -682,6 +682,34 @@ int dy_cls_topk(const void* scores, int64_t ld, int dtype, int B, int nc, int k,
  * Integer atomics.  A row whose label is outside [0, nc) is not counted. */
 int dy_cls_metrics_update(const int32_t* idx, int k, const int64_t* cls, int B, int nc, int64_t* counts, int32_t* confusion, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ validation matching
+ * The per-image bookkeeping of DetectionValidator.update_metrics (U/models/yolo/detect/val.py:72-116) for a whole batch: one
+ * workgroup per image, nothing read back.
+ *  dy_val_box_match: replaces scale_boxes on predictions and labels (U/utils/ops.py:95-125), box_iou (U/utils/metrics.py:52-72),
+ *                    `_process_batch` (val.py:151-174) and ConfusionMatrix.process_batch (metrics.py:209-253).
+ *    det [B, max_det, ld] f32 rows (x1,y1,x2,y2,conf,cls,...) and ocnt [B] as dy_nms_greedy leaves them (ld >= 6);
+ *    lcls [L] f32, lxywh [L, 4] f32 normalised, loff [B + 1] int32: the batch's labels sorted by image; (H, W) the network input;
+ *    rec [B, 5] f32 = (gain, pad_x, pad_y, h0, w0) per image, filled as scale_boxes computes them; iouv [T] f32, T <= 16.
+ *    -> correct u8 [B, max_det, T] (rows >= ocnt[b] zero), predn f32 [B, max_det, 4] and tboxn f32 [L, 4] native-space boxes,
+ *       confusion int32 [nc + 1, nc + 1] [predicted][true] accumulated with integer atomics (NULL: not filled; detections with
+ *       conf > conf_thres, pairs with IoU > iou_thres, both strict; background = nc).  All arithmetic f32 in the host order.
+ *    `correct` is the rule of engine/validator.match_from_iou: at threshold k the candidates are the equal-class pairs with
+ *    IoU >= iouv[k]; a detection keeps the label it overlaps most (tie: higher label index), a label the lowest-index detection.
+ *    single_cls: every detection class reads as 0.
+ *  dy_val_iou_match: the same rule on precomputed IoU matrices (mask IoU, U/models/yolo/segment/val.py:131-166; OKS,
+ *                    U/models/yolo/pose/val.py:110-141): iou = the [M_b, N_b] f32 matrices of the batch one after another
+ *                    (row-major, M_b = loff[b+1] - loff[b], N_b = ocnt[b]), moff [B] int64 their element offsets.
+ *  workspace: B * max_det * 5 int32 when max_det * 20 bytes exceed 40 KiB (the per-detection state then does not fit in LDS),
+ *             else it may be NULL.  Labels per image are not limited.  Label offsets outside [0, L] and a matrix that does not lie
+ *             inside the iou_numel elements of `iou` read as an image without labels. */
+int dy_val_box_match(const float* det, int ld, const int* ocnt, int B, int max_det, const float* lcls, const float* lxywh,
+                     const int* loff, int L, int H, int W, const float* rec, const float* iouv, int T, int single_cls, float conf_thres,
+                     float iou_thres, int nc, uint8_t* correct, float* predn, float* tboxn, int32_t* confusion, void* workspace,
+                     void* stream);
+int dy_val_iou_match(const float* iou, int64_t iou_numel, const int64_t* moff, const float* det, int ld, const int* ocnt, int B,
+                     int max_det, const float* lcls, const int* loff, int L, const float* iouv, int T, int single_cls, uint8_t* correct,
+                     void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
