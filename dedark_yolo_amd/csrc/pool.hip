@@ -367,6 +367,10 @@ extern "C" int dy_asff_fuse_fwd(const void* x0, int64_t ld0, const void* x1, int
   return 0;
 }
 
+// dlogits is [pixels][lddl] in the compute dtype.  Columns [0, 3) receive the gradient of the logits (column 2 is written as 0 in the
+// two-level mode, and not at all when lddl == 2); columns [3, min(lddl, 8)) are written as 0, so that the channel-padded buffer of
+// the weight_levels conv (4 or 8 wide) carries no garbage into its backward; columns >= 8 are never touched.  dx_k is written, or
+// added to what it holds when acc_k is set; dx2 / acc2 are ignored in the two-level mode (x2 == NULL).
 extern "C" int dy_asff_fuse_bwd(const void* dout, int64_t lddo, const void* x0, int64_t ld0, const void* x1, int64_t ld1,
                                 const void* x2, int64_t ld2, const void* logits, int64_t ldl, void* dx0, int64_t ldd0, void* dx1,
                                 int64_t ldd1, void* dx2, int64_t ldd2, void* dlogits, int64_t lddl, int64_t pixels, int C,

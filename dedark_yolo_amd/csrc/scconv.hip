@@ -430,7 +430,8 @@ extern "C" int dy_sru_bwd(const void* x, int64_t x_ld, const void* dy, int64_t d
   if (int e = dy_check_view("dy_sru_bwd(dy)", dy, dy_ld, C, dtype)) return e;
   if (int e = dy_check_view("dy_sru_bwd(dx)", dx, dx_ld, C, dtype)) return e;
   const int ve = dy_vec_elems(dtype);
-  DY_CHECK(moments && gamma && beta && red && groups > 0 && groups <= 64 && C % groups == 0 && (C / 2) % ve == 0, "dy_sru_bwd: bad args");
+  DY_CHECK(moments && gamma && beta && red && groups > 0 && groups <= 64 && C % groups == 0 && (C / 2) % ve == 0 && HW * (C / groups) > 1,
+           "dy_sru_bwd: bad args");
   const dim3 g = grid_for(HW, N, C / 2 / ve);
   const size_t shm = (size_t)NT * 2 * ve * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
