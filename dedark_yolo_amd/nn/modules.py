@@ -17,7 +17,8 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "RFBblock", "DFL", "Detect",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
+           "SC_Conv3_C2f", "Conv3_SC_C2f", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
 
@@ -743,8 +744,12 @@ class SCConv(DyModule):
 
     def __init__(self, op_channel, group_num=4, gate_treshold=0.5, alpha=1 / 2, squeeze_radio=2, group_size=2, group_kernel_size=3):
         super().__init__()
-        if op_channel % 64 != 0:
-            raise NotImplementedError("SCConv: channel count must be a multiple of 64 (16-byte channel vectors of the C/8 group slices)")
+        if op_channel % 16 != 0 or not 16 <= op_channel <= 2048:
+            raise NotImplementedError("SCConv: channel count must be a multiple of 16 in 16..2048 (C/8 input channels per GWC group, whole "
+                                      "16-byte vectors of the SRU halves)")
+        # C % 64 == 0 (MFRU's widths): the CRU is composed of the generic conv routes on 16-byte channel slices.  Any other width has
+        # slices of 2 / 6 / 10 ... channels: the CRU convolutions run on the dy_cru_conv_* kernels (ops.cru_conv_forward).
+        self._cru = op_channel % 64 != 0
         self.SRU = SRU(op_channel, group_num=group_num, gate_treshold=gate_treshold)
         self.CRU = CRU(op_channel, alpha=alpha, squeeze_radio=squeeze_radio, group_size=group_size, group_kernel_size=group_kernel_size)
         self.c = op_channel
@@ -764,7 +769,8 @@ class SCConv(DyModule):
                 ops.register_pack_view(w)
         return c[1], c[2]
 
-    def _fwd(self, tape, x):
+    def _fwd(self, tape, x, out=None):
+        """out: optional NHWC view the result is written into (Conv3_SC_Bottleneck inside a C2f buffer)"""
         B, C_, H, W = x.shape
         if C_ != self.c:
             raise RuntimeError(f"SCConv: expected {self.c} channels, got {C_}")
@@ -777,6 +783,26 @@ class SCConv(DyModule):
              float(gn.eps), did, st)
         h, q, e = C_ // 2, C_ // 4, C_ // 8
         buf = empty_nhwc(B, 2 * C_, H, W, dt, dev)                       # cat(Y1 [C], PWC2(low) [3C/4], low [C/4])
+        if self._cru:
+            wv = bv = None
+            sq1 = ops.cru_conv_forward(tape, y[:, :h], None, None, cru.squeeze1.weight)
+            low = ops.cru_conv_forward(tape, y[:, h:], None, None, cru.squeeze2.weight, out=buf[:, 2 * C_ - q:])
+            ops.cru_conv_forward(tape, sq1, cru.GWC.weight, cru.GWC.bias, cru.PWC1.weight, G=2, out=buf[:, :C_])      # Y1, one accumulator
+            ops.cru_conv_forward(tape, low, None, None, cru.PWC2.weight, out=buf[:, C_:2 * C_ - q])
+        else:
+            wv, bv = self._composed_cru_fwd(tape, y, buf)
+        mom2 = torch.zeros((B, 2 * C_, 2), dtype=torch.float64, device=dev)
+        call("dy_chan_moments", ptr(buf), ld_of(buf), B, H * W, 2 * C_, ptr(mom2), did, st)
+        res = out if out is not None else empty_nhwc(B, C_, H, W, dt, dev)
+        call("dy_cru_fuse_fwd", ptr(buf), ld_of(buf), ptr(res), ld_of(res), B, H * W, C_, ptr(mom2), did, st)
+        if tape is not None:
+            tape.push(dict(x=x, mom=mom, buf=buf, mom2=mom2, views=(wv, bv)))
+        return res
+
+    def _composed_cru_fwd(self, tape, y, buf):
+        cru = self.CRU
+        C_ = self.c
+        h, q, e = C_ // 2, C_ // 4, C_ // 8
         kw = dict(shared=True)
         sq1 = conv_forward(tape, y[:, :h], cru.squeeze1.weight, None, None, ACT_NONE, 1, 0, 1, False, **kw)
         sq2 = conv_forward(tape, y[:, h:], cru.squeeze2.weight, None, None, ACT_NONE, 1, 0, 1, False, out=buf[:, 2 * C_ - q:], **kw)
@@ -786,13 +812,7 @@ class SCConv(DyModule):
         pw1 = conv_forward(tape, sq1, cru.PWC1.weight, None, None, ACT_NONE, 1, 0, 1, False, **kw)
         copy2d(pw1, buf[:, :C_], accumulate=True)                        # Y1 = GWC(up) + PWC1(up)
         conv_forward(tape, sq2, cru.PWC2.weight, None, None, ACT_NONE, 1, 0, 1, False, out=buf[:, C_:2 * C_ - q], **kw)
-        mom2 = torch.zeros((B, 2 * C_, 2), dtype=torch.float64, device=dev)
-        call("dy_chan_moments", ptr(buf), ld_of(buf), B, H * W, 2 * C_, ptr(mom2), did, st)
-        res = empty_nhwc(B, C_, H, W, dt, dev)
-        call("dy_cru_fuse_fwd", ptr(buf), ld_of(buf), ptr(res), ld_of(res), B, H * W, C_, ptr(mom2), did, st)
-        if tape is not None:
-            tape.push(dict(x=x, mom=mom, buf=buf, mom2=mom2, views=(wv, bv)))
-        return res
+        return wv, bv
 
     def _bwd(self, tape, dres, needs=(True,)):
         s = tape.pop()
@@ -804,6 +824,27 @@ class SCConv(DyModule):
         dbuf = empty_nhwc(B, 2 * C_, H, W, dt, dev)
         ds = torch.zeros((B, 2 * C_, 2), dtype=torch.float64, device=dev)
         call("dy_cru_fuse_bwd", ptr(buf), ld_of(buf), ptr(dres), ld_of(dres), ptr(dbuf), ld_of(dbuf), B, H * W, C_, ptr(mom2), ptr(ds), did, st)
+        dy = empty_nhwc(B, C_, H, W, dt, dev)
+        if self._cru:
+            ops.cru_conv_backward(tape, dbuf[:, C_:2 * C_ - q], dx_out=dbuf[:, 2 * C_ - q:], accumulate=True)     # PWC2: d low' += ...
+            dsq1 = ops.cru_conv_backward(tape, dbuf[:, :C_])                                           # GWC^T + PWC1^T, one accumulator
+            ops.cru_conv_backward(tape, dbuf[:, 2 * C_ - q:], dx_out=dy[:, h:])                        # squeeze2
+            ops.cru_conv_backward(tape, dsq1, dx_out=dy[:, :h])                                        # squeeze1
+        else:
+            self._composed_cru_bwd(tape, dbuf, dy, wv, bv)
+        dx = empty_nhwc(B, C_, H, W, dt, dev)
+        red = torch.zeros((B, C_, 2), dtype=torch.float64, device=dev)
+        call("dy_sru_bwd", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(dx), ld_of(dx), B, H * W, C_, gn.group_num, ptr(mom), ptr(gn.weight),
+             ptr(gn.bias), float(gn.eps), ptr(red), did, st)
+        tot = red.sum(0).float()
+        ops._add_pgrad(tape, gn.weight, tot[:, 1].reshape(C_, 1, 1))
+        ops._add_pgrad(tape, gn.bias, tot[:, 0].reshape(C_, 1, 1))
+        return dx
+
+    def _composed_cru_bwd(self, tape, dbuf, dy, wv, bv):
+        cru = self.CRU
+        C_ = self.c
+        h, q, e = C_ // 2, C_ // 4, C_ // 8
         conv_backward(tape, dbuf[:, C_:2 * C_ - q], dx_out=dbuf[:, 2 * C_ - q:], accumulate=True)       # PWC2: d low' += ...
         dsq1 = conv_backward(tape, dbuf[:, :C_])                                                       # PWC1
         gw = torch.empty_like(cru.GWC.weight)
@@ -814,17 +855,8 @@ class SCConv(DyModule):
             gb[j * h:(j + 1) * h].copy_(tape.pgrads.pop(bv[j]).view(h))
         ops._add_pgrad(tape, cru.GWC.weight, gw)
         ops._add_pgrad(tape, cru.GWC.bias, gb)
-        dy = empty_nhwc(B, C_, H, W, dt, dev)
         conv_backward(tape, dbuf[:, 2 * C_ - q:], dx_out=dy[:, h:])                                    # squeeze2
         conv_backward(tape, dsq1, dx_out=dy[:, :h])                                                    # squeeze1
-        dx = empty_nhwc(B, C_, H, W, dt, dev)
-        red = torch.zeros((B, C_, 2), dtype=torch.float64, device=dev)
-        call("dy_sru_bwd", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(dx), ld_of(dx), B, H * W, C_, gn.group_num, ptr(mom), ptr(gn.weight),
-             ptr(gn.bias), float(gn.eps), ptr(red), did, st)
-        tot = red.sum(0).float()
-        ops._add_pgrad(tape, gn.weight, tot[:, 1].reshape(C_, 1, 1))
-        ops._add_pgrad(tape, gn.bias, tot[:, 0].reshape(C_, 1, 1))
-        return dx
 
 
 def _flush_shared_grads(tape):
@@ -834,6 +866,118 @@ def _flush_shared_grads(tape):
         gd = ops._grad_dst(p)
         if gd is not None:
             gd.copy_(tape.pgrads.pop(p).view_as(gd))
+
+
+class _SCBottleneckBase(DyModule):
+    """SandCRblock(x) [+ x] with SandCRblock = (SCConv, conv) or (conv, SCConv): the bottlenecks of the SCConv C2f family (reference
+    block.py:610-700).  The conv is a Conv (BatchNorm + SiLU; the shortcut rides on its BatchNorm pass as in Bottleneck) or a plain
+    nn.Conv2d with bias.  SCConv's gradients are collected on the tape and flushed to their slots like MFRU's."""
+    _sc_first = True
+
+    def _make(self, c1, c2, shortcut, g, conv):
+        if g != 1:
+            raise NotImplementedError("grouped convolution is outside the Dedark-YOLO hot path")
+        self.SandCRblock = nn.Sequential(SCConv(c1), conv) if self._sc_first else nn.Sequential(conv, SCConv(c2))
+        self.add = shortcut and c1 == c2
+
+    def _fwd(self, tape, x, out=None):
+        a, b = self.SandCRblock
+        res = x if self.add else None
+        if not self._sc_first:                                    # Conv -> SCConv: the CRU tail writes into `out`, the shortcut is added in place
+            y = b._fwd(tape, a._fwd(tape, x), out=out)
+            if res is not None:
+                copy2d(res, y, accumulate=True)
+                ops.emu_round(y)
+            return y
+        t = a._fwd(tape, x)
+        if isinstance(b, Conv):
+            return b._fwd(tape, t, out=out, residual=res)
+        y = plain_conv_fwd(tape, b, t, out=out)
+        if res is not None:
+            copy2d(res, y, accumulate=True)
+            ops.emu_round(y)
+        return y
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        a, b = self.SandCRblock
+        if not self._sc_first:
+            dt = b._bwd(tape, dy)
+            _flush_shared_grads(tape)
+            return a._bwd(tape, dt, dx_out=dx_out, accumulate=accumulate, add_src=dy if self.add else None)
+        dt = b._bwd(tape, dy) if isinstance(b, Conv) else conv_backward(tape, dy)
+        dx = a._bwd(tape, dt)                                     # SRU backward writes a buffer of its own
+        _flush_shared_grads(tape)
+        if self.add:
+            copy2d(dy, dx, accumulate=True)
+            ops.emu_round(dx)
+        if dx_out is None:
+            return dx
+        copy2d(dx, dx_out, accumulate=accumulate)
+        if accumulate:
+            ops.emu_round(dx_out)
+        return dx_out
+
+class SCConvBottleneck(_SCBottleneckBase):
+    """SCConv -> Conv 1x1 [+ x] (reference block.py:610-627)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        self._make(c1, c2, shortcut, g, Conv(c1=c1, c2=c2, k=1, s=1))
+
+
+class SC_PW_Bottleneck(_SCBottleneckBase):
+    """SCConv -> nn.Conv2d 1x1 with bias, no BatchNorm [+ x] (reference block.py:630-645)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        self._make(c1, c2, shortcut, g, nn.Conv2d(c1, c2, 1, 1, autopad(1, None, 1), groups=g, bias=True))
+
+
+class SC_Conv3_Bottleneck(_SCBottleneckBase):
+    """SCConv -> Conv 3x3 [+ x] (reference block.py:648-662)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        self._make(c1, c2, shortcut, g, Conv(c1=c1, c2=c2, k=3, s=1, p=autopad(3, d=1), g=g))
+
+
+class Conv3_SC_Bottleneck(_SCBottleneckBase):
+    """Conv 3x3 -> SCConv [+ x] (reference block.py:684-700)."""
+    _sc_first = False
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__()
+        self._make(c1, c2, shortcut, g, Conv(c1=c1, c2=c2, k=3, s=1, p=autopad(3, d=1), g=g))
+
+
+class _SCC2fBase(C2f):
+    """C2f whose blocks are one of the SCConv bottlenecks (reference block.py:418-459): C2f's buffer-slice forward and backward as
+    they are."""
+    _block = None
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(self._block(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
+
+
+class SCC2f(_SCC2fBase):
+    """C2f of SCConvBottleneck (reference block.py:418-426)."""
+    _block = SCConvBottleneck
+
+
+class SC_PW_C2f(_SCC2fBase):
+    """C2f of SC_PW_Bottleneck (reference block.py:429-437)."""
+    _block = SC_PW_Bottleneck
+
+
+class SC_Conv3_C2f(_SCC2fBase):
+    """C2f of SC_Conv3_Bottleneck (reference block.py:440-448)."""
+    _block = SC_Conv3_Bottleneck
+
+
+class Conv3_SC_C2f(_SCC2fBase):
+    """C2f of Conv3_SC_Bottleneck (reference block.py:451-459)."""
+    _block = Conv3_SC_Bottleneck
 
 
 class MFRU(DyModule):

@@ -16,9 +16,11 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, Classify, Concat, Conv, DWConv, Detect, DyModule, FasterC2f, FasterC2f_N,
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
+                      DyModule, FasterC2f, FasterC2f_N,
                       GhostBottleneck, GhostConv, MFRU,
-                      PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SPPF, Segment, Tape, Upsample,
+                      PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
+                      SC_PW_C2f, SPPF, Segment, Tape, Upsample,
                       lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
@@ -32,7 +34,9 @@ _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Det
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
                  Segment=Segment, Pose=Pose, Classify=Classify,
-                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost)
+                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost,
+                 SCC2f=SCC2f, SC_PW_C2f=SC_PW_C2f, SC_Conv3_C2f=SC_Conv3_C2f, Conv3_SC_C2f=Conv3_SC_C2f, SCConvBottleneck=SCConvBottleneck,
+                 SC_PW_Bottleneck=SC_PW_Bottleneck, SC_Conv3_Bottleneck=SC_Conv3_Bottleneck, Conv3_SC_Bottleneck=Conv3_SC_Bottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
 
 
@@ -98,6 +102,8 @@ _RULES = {
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
     PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
     GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f,   # tasks.py:856-874
+    SCC2f: _rule_c2f, SC_PW_C2f: _rule_c2f, SC_Conv3_C2f: _rule_c2f, Conv3_SC_C2f: _rule_c2f,                         # tasks.py:744-752, 857-871
+    SCConvBottleneck: _rule_conv_like, SC_PW_Bottleneck: _rule_conv_like, SC_Conv3_Bottleneck: _rule_conv_like, Conv3_SC_Bottleneck: _rule_conv_like,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
     AsffTribeLevel: lambda r: (r.args, 512 if r.args[0] in (0, 1) else 256, r.repeats),       # tasks.py:892-896
@@ -112,7 +118,7 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):

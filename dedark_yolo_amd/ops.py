@@ -867,6 +867,96 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
     return dx
 
 
+# ------------------------------------------------------------------------------------------------ CRU convolutions
+def _cru_packed(w3, w1, G, transposed, dtype):
+    """MFMA operand image of a CRU conv's weights (dy_cru_conv_pack), cached on the 1x1 weight and re-packed when either weight
+    changed (optimizer step, load_state_dict)."""
+    GN, C1 = w1.shape[0], w1.shape[1]
+    C3 = 0 if w3 is None else w3.shape[1]
+    cache = w1.__dict__.setdefault("_dy_cru_pack", {})
+    key = (bool(transposed), dtype)
+    tag = (_weights_epoch, w1._version, w1.data_ptr(), None if w3 is None else (w3._version, w3.data_ptr()))
+    hit = cache.get(key)
+    if hit is not None and hit[0] == tag:
+        return hit[1]
+    out = hit[1] if hit is not None else torch.empty(GN * (9 * C3 + C1), dtype=dtype, device=w1.device)
+    call("dy_cru_conv_pack", None if w3 is None else ptr(_w32(w3)), ptr(_w32(w1)), ptr(out), G, GN // G, C3, C1, 1 if transposed else 0,
+         dt_id(dtype), stream())
+    cache[key] = (tag, out)
+    return out
+
+
+def _cru_dims(x, w3, bias, w1, G):
+    GN, C1 = w1.shape[0], w1.shape[1]
+    C3 = 0 if w3 is None else w3.shape[1]
+    if (tuple(w1.shape[2:]) != (1, 1) or GN % G or x.shape[1] != C1 or (bias is not None and tuple(bias.shape) != (GN,))
+            or (w3 is not None and (tuple(w3.shape) != (GN, C3, 3, 3) or G * C3 != C1)) or (w3 is None and G != 1)):
+        raise RuntimeError(f"cru_conv: weights {None if w3 is None else tuple(w3.shape)} / {tuple(w1.shape)} in {G} groups do not fit "
+                           f"{x.shape[1]} channels")
+    return GN // G, C3, C1
+
+
+def cru_conv_forward(tape, x, w3, bias, w1, G=1, out=None):
+    """One CRU convolution (dy_cru_conv_fwd): out = conv3x3(x, w3, groups=G, pad 1) + bias + conv1x1(x, w1) in one accumulator, or
+    the plain 1x1 when w3 is None.  x / out: NHWC views of exactly w1.shape[1] / w1.shape[0] channels, any channel offset inside a
+    wider buffer (only those lanes are touched)."""
+    B, _, H, W = x.shape
+    N, C3, C1 = _cru_dims(x, w3, bias, w1, G)
+    y = out if out is not None else empty_nhwc(B, G * N, H, W, x.dtype, x.device)
+    if tuple(y.shape) != (B, G * N, H, W) or y.dtype != x.dtype:
+        raise RuntimeError("cru_conv_forward: out must be an NHWC view of the result's shape and dtype")
+    wp = _cru_packed(w3, w1, G, False, x.dtype)
+    es = x.element_size()
+    _C._prof is not None and _C.set_meta(kind="cru_fwd", shape=f"{G}x{N} <- 9x{C3}+{C1} in {B}x{H}x{W}", dtype=str(x.dtype),
+                                         flops=2.0 * B * H * W * G * N * (9 * C3 + C1), bytes=float(B * H * W * (C1 + G * N) * es))
+    call("dy_cru_conv_fwd", ptr(x), ld_of(x), ptr(wp), None if bias is None else ptr(_w32(bias)), ptr(y), ld_of(y), B, H, W, G, N, C3, C1,
+         dt_id(x.dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        tape.push((x, w3, bias, w1, G))
+    return y
+
+
+def cru_conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False):
+    """Backward of the matching cru_conv_forward (pops its context): the weight / bias gradients (deterministic, f32) are filed on
+    the tape (_add_pgrad: a parameter used twice per step adds up) and dx = [dx_out +] the gather-form data gradient."""
+    x, w3, bias, w1, G = tape.pop()
+    B, _, H, W = x.shape
+    N, C3, C1 = _cru_dims(x, w3, bias, w1, G)
+    dtype, dev, st = x.dtype, x.device, stream()
+    es = x.element_size()
+    if tuple(dy.shape) != (B, G * N, H, W) or dy.dtype != dtype:
+        raise RuntimeError("cru_conv_backward: gradient does not match the forward's output")
+    want = [p is not None and p.requires_grad for p in (w3, bias, w1)]
+    if any(want):
+        g3 = torch.empty(w3.shape, dtype=torch.float32, device=dev) if want[0] else None
+        gb = torch.empty(bias.shape, dtype=torch.float32, device=dev) if want[1] else None
+        g1 = torch.empty(w1.shape, dtype=torch.float32, device=dev) if want[2] else None
+        scratch = wgrad_scratch(dev, tag=st)
+        _C._prof is not None and _C.set_meta(kind="cru_wgrad", shape=f"{G}x{N} <- 9x{C3}+{C1} in {B}x{H}x{W}", dtype=str(dtype),
+                                             flops=2.0 * B * H * W * G * N * (9 * C3 + C1), bytes=float(B * H * W * (C1 + G * N) * es))
+        call("dy_cru_conv_wgrad", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(g3), ptr(gb), ptr(g1), B, H, W, G, N, C3, C1, ptr(scratch),
+             scratch.numel(), dt_id(dtype), st)
+        for p, g in ((w3, g3), (bias, gb), (w1, g1)):
+            if g is not None:
+                _add_pgrad(tape, p, g)
+    if not need_dx:
+        return None
+    if dx_out is None:
+        dx, accumulate = empty_nhwc(B, C1, H, W, dtype, dev), False
+    else:
+        dx = dx_out
+        if tuple(dx.shape) != (B, C1, H, W) or dx.dtype != dtype:
+            raise RuntimeError("cru_conv_backward: dx_out must be an NHWC view of the input's shape and dtype")
+    wp = _cru_packed(w3, w1, G, True, dtype)
+    _C._prof is not None and _C.set_meta(kind="cru_dgrad", shape=f"{G}x{N} <- 9x{C3}+{C1} in {B}x{H}x{W}", dtype=str(dtype),
+                                         flops=2.0 * B * H * W * G * N * (9 * C3 + C1),
+                                         bytes=float(B * H * W * ((2 if accumulate else 1) * C1 + G * N) * es))
+    call("dy_cru_conv_dgrad", ptr(dy), ld_of(dy), ptr(wp), ptr(dx), ld_of(dx), B, H, W, G, N, C3, C1, 1 if accumulate else 0, dt_id(dtype), st)
+    emu_round(dx)
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ depthwise conv
 def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
     """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.

@@ -211,7 +211,9 @@ _REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("Conv", "Concat", "
                                                               "DWConv")})
 _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bottleneck", "SPPF", "DFL", "AsffTribeLevel", "AsffDoubLevel", "MFRU",
                                                                "RFBblock", "FasterC2f_N", "FasterC2f", "PconvBottleneck_n",
-                                                               "PconvBottleneck", "GhostBottleneck", "C3", "C3Ghost")})
+                                                               "PconvBottleneck", "GhostBottleneck", "C3", "C3Ghost", "SCC2f", "SC_PW_C2f",
+                                                               "SC_Conv3_C2f", "Conv3_SC_C2f", "SCConvBottleneck", "SC_PW_Bottleneck",
+                                                               "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
@@ -241,6 +243,8 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "PconvBottleneck": ("add",), "Proto": (), "Segment": ("nc", "nl", "reg_max", "no", "stride", "nm", "npr"),
               "Pose": ("nc", "nl", "reg_max", "no", "stride", "kpt_shape", "nk"),
               "GhostConv": (), "DWConv": (), "GhostBottleneck": (), "C3": (), "C3Ghost": (),
+              "SCC2f": ("c",), "SC_PW_C2f": ("c",), "SC_Conv3_C2f": ("c",), "Conv3_SC_C2f": ("c",), "SCConvBottleneck": ("add",),
+              "SC_PW_Bottleneck": ("add",), "SC_Conv3_Bottleneck": ("add",), "Conv3_SC_Bottleneck": ("add",),
               "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}

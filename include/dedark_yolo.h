@@ -322,6 +322,28 @@ int dy_cru_fuse_fwd(const void* o, int64_t o_ld, void* res, int64_t r_ld, int N,
 /* its backward: dout [.., 2C] (written); ds[n][k][2] scratch (zeroed by the caller; slot 0 = sum_pixels dres[c(k)] o[k]). */
 int dy_cru_fuse_bwd(const void* o, int64_t o_ld, const void* dres, int64_t d_ld, void* dout, int64_t do_ld, int N, int64_t HW, int C,
                     const double* moments, double* ds, int dtype, void* stream);
+/* ------------------------------------------------------------------------------------ CRU convolutions (SCConv C2f family)
+ * The convolutions of CRU.forward (U/nn/modules/conv.py:406-417) at any width C % 16 == 0.  One "CRU conv" over NHWC views of
+ * M = B*H*W pixels, G groups (1 or 2) of N output channels:
+ *   y[m][g N + n] = bias[g N + n] + sum_{tap < 9, ci < C3} x[m + off(tap)][g C3 + ci] w3[g N + n][ci][tap] + sum_{c < C1} x[m][c] w1[g N + n][c]
+ * (3x3 pad 1 stride 1; C3 == 0: a plain 1x1 with G == 1; C3 > 0: G C3 == C1).  Y1 = GWC(up') + PWC1(up') is (G, N, C3, C1) =
+ * (2, C/2, C/8, C/4) in one accumulator; squeeze1 / squeeze2 / PWC2 are C3 == 0.  x has C1 channels, y has G N; exactly those lanes
+ * of a pixel are read / written (element alignment is enough), so both may be channel slices of wider buffers with live neighbours.
+ * w3: f32 [G N][C3][3][3], w1: f32 [G N][C1], bias: f32 [G N] or NULL (the state_dict layouts).
+ * wp: G N (9 C3 + C1) elements of dtype, 16-byte aligned: the MFMA operand image of (w3, w1); transposed = 1 packs the data
+ * gradient's (input <-> output, taps flipped) image. */
+int dy_cru_conv_pack(const float* w3, const float* w1, void* wp, int G, int N, int C3, int C1, int transposed, int dtype, void* stream);
+/* wp = dy_cru_conv_pack(transposed = 0) */
+int dy_cru_conv_fwd(const void* x, int64_t x_ld, const void* wp, const float* bias, void* y, int64_t y_ld, int B, int H, int W, int G, int N,
+                    int C3, int C1, int dtype, void* stream);
+/* dx [.., C1] = [dx +] GWC^T(dy) + PWC1^T(dy), gather form; wp = dy_cru_conv_pack(transposed = 1) */
+int dy_cru_conv_dgrad(const void* dy, int64_t dy_ld, const void* wp, void* dx, int64_t dx_ld, int B, int H, int W, int G, int N, int C3,
+                      int C1, int accumulate, int dtype, void* stream);
+/* dw3 / db / dw1 (each nullable; overwrite, f32, the layouts above).  Deterministic: the pixels are split into ranges by the
+ * shape and scratch_elems alone, partial tiles go to `scratch` (>= G N (9 C3 + C1 + 1) floats; more allows more ranges) and a second
+ * launch adds them in range order; no atomics */
+int dy_cru_conv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw3, float* db, float* dw1, int B, int H, int W,
+                      int G, int N, int C3, int C1, float* scratch, int64_t scratch_elems, int dtype, void* stream);
 /* CIoU of n box pairs, xyxy f32 (reference ultralytics/utils/metrics.py:75-128 bbox_iou(b1, b2, xywh=False, CIoU=True): eps added to
  * h only, alpha constant in the backward); grad_b1 (nullable) [n,4] = d out[i] / d b1[i]. */
 int dy_bbox_ciou(const float* b1, const float* b2, int64_t n, float* out, float* grad_b1, void* stream);
