@@ -138,6 +138,8 @@ _SIGS = {
     "dy_cru_conv_fwd": [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_cru_conv_dgrad": [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_cru_conv_wgrad": [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
+    "dy_attn_fwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, i32, vp],
+    "dy_attn_bwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp],
     "dy_bbox_ciou": [vp, vp, i64, vp, vp, vp],
     "dy_bbox_iou": [vp, vp, i64, i32, i32, f32, vp, vp, vp],
     "dy_aug_resize_u8": [vp, i32, i32, i64, vp, i32, i32, i64, vp],

@@ -107,7 +107,7 @@ class FlatState:
                     if not p.requires_grad or id(p) in seen:
                         continue
                     seen.add(id(p))
-                    g = 2 if name == "bias" else (1 if isinstance(mod, bn_types) else 0)     # trainer.py:626-634
+                    g = 2 if "bias" in name else (1 if isinstance(mod, bn_types) else 0)     # trainer.py:638-646 (ma.in_proj_bias too)
                     n = p.numel()
                     slots.append((p, off, n, g))
                     off += ops.round_up(n, 4)

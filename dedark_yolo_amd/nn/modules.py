@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "TransformerLayer", "TransformerBlock", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
            "SC_Conv3_C2f", "Conv3_SC_C2f", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
@@ -470,6 +470,165 @@ class C3Ghost(C3):
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__(c1, c2, n, shortcut, g, e)
         self.m = nn.Sequential(*(GhostBottleneck(self._c, self._c) for _ in range(n)))
+
+
+class _ParamRows:
+    """Rows [r0, r1) of a parameter as the gradient owner (and bias) of one conv: nn.MultiheadAttention keeps its three in-projections
+    in ONE in_proj_weight [3C, C] / in_proj_bias [3C], each of which runs as a 1x1 conv of its own.  ops' gradient sinks see an object
+    with the parameter's flags and, under the trainer's direct gradient placement, the rows of its .grad: the weight / bias gradient
+    kernels write them in place.  Without direct placement the three results are filed under these objects on the tape and
+    TransformerLayer._bwd joins them into the parameter's gradient."""
+
+    def __init__(self, p, r0, r1):
+        self.p, self.r0, self.r1 = p, r0, r1
+        self.shape = torch.Size((r1 - r0, *p.shape[1:]))
+
+    requires_grad = property(lambda self: self.p.requires_grad)
+    _dy_direct = property(lambda self: getattr(self.p, "_dy_direct", False))
+    grad = property(lambda self: None if self.p.grad is None else self.p.grad[self.r0:self.r1])
+
+    def detach(self):
+        return self.p.detach()[self.r0:self.r1]
+
+
+class TransformerLayer(DyModule):
+    """x = ma(q(x), k(x), v(x)) + x; x = fc2(fc1(x)) + x over the pixels of an NHWC map, which already is the token matrix
+    [B, L = H W, C] (reference ultralytics/nn/modules/transformer.py:100-117; no LayerNorm).  nn.Linear / nn.MultiheadAttention hold
+    the parameters under the reference's names; every Linear runs as a 1x1 conv (nine per layer: q / k / v, the three in-projections
+    with bias writing Q | K | V into the slices of one buffer, out_proj with bias, fc1, fc2), softmax(Q K^T / sqrt(D)) V is
+    ops.attn_forward.  Both residuals are added by the conv's own dy_copy2d(accumulate) pass; in backward the fan-outs of x and of
+    the attention output add through add_src / accumulate."""
+
+    def __init__(self, c, num_heads):
+        super().__init__()
+        if c % num_heads or (c // num_heads) % 8 or not 8 <= c // num_heads <= 128:
+            raise NotImplementedError(f"TransformerLayer: head dim {c}/{num_heads} is outside the attention kernels' rule D % 8 == 0, 8 <= D <= 128")
+        self.q = nn.Linear(c, c, bias=False)
+        self.k = nn.Linear(c, c, bias=False)
+        self.v = nn.Linear(c, c, bias=False)
+        self.ma = nn.MultiheadAttention(embed_dim=c, num_heads=num_heads)
+        self.fc1 = nn.Linear(c, c, bias=False)
+        self.fc2 = nn.Linear(c, c, bias=False)
+        self._c, self._heads = c, num_heads
+
+    def _views(self):
+        """The weights as [c, c, 1, 1] conv weights (the view OBJECTS are kept: the packed-weight caches live on them) and the row
+        proxies of the in-projection; rebuilt when the parameters moved."""
+        key = tuple(p.data_ptr() for p in (self.q.weight, self.ma.in_proj_weight, self.ma.in_proj_bias, self.fc2.weight))
+        c = self.__dict__.get("_view_cache")
+        if c is None or c[0] != key:
+            C_ = self._c
+            v = {n: getattr(self, n).weight.detach().view(C_, C_, 1, 1) for n in ("q", "k", "v", "fc1", "fc2")}
+            v["out"] = self.ma.out_proj.weight.detach().view(C_, C_, 1, 1)
+            wi, bi = self.ma.in_proj_weight, self.ma.in_proj_bias
+            for i in range(3):
+                v[f"in{i}"] = wi.detach()[i * C_:(i + 1) * C_].view(C_, C_, 1, 1)
+                v[f"own{i}"] = _ParamRows(wi, i * C_, (i + 1) * C_)
+                v[f"bias{i}"] = _ParamRows(bi, i * C_, (i + 1) * C_)
+            for t in v.values():
+                if torch.is_tensor(t):
+                    ops.register_pack_view(t)
+            c = (key, v)
+            self.__dict__["_view_cache"] = c
+        return c[1]
+
+    def _fwd(self, tape, x, out=None):
+        if self.ma.dropout:
+            raise NotImplementedError("TransformerLayer: attention dropout > 0 is not implemented")
+        v, C_ = self._views(), self._c
+        B, _, H, W = x.shape
+        lin = lambda t, w, owner, bias=None, out=None, residual=None: conv_forward(tape, t, w, bias, None, ACT_NONE, 1, 0, 1, False, out=out,
+                                                                                   residual=residual, owner=owner)
+        qkv = empty_nhwc(B, 3 * C_, H, W, x.dtype, x.device)
+        for i, n in enumerate(("q", "k", "v")):
+            t = lin(x, v[n], getattr(self, n).weight)
+            lin(t, v[f"in{i}"], v[f"own{i}"], bias=v[f"bias{i}"], out=qkv[:, i * C_:(i + 1) * C_])
+        a = ops.attn_forward(tape, qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], self._heads)
+        x1 = lin(a, v["out"], self.ma.out_proj.weight, bias=self.ma.out_proj.bias, residual=x)
+        t = lin(x1, v["fc1"], self.fc1.weight)
+        return lin(t, v["fc2"], self.fc2.weight, out=out, residual=x1)
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        C_ = self._c
+        dt = conv_backward(tape, dy)                                       # fc2
+        dx1 = conv_backward(tape, dt, add_src=dy)                          # fc1; + the second residual
+        da = conv_backward(tape, dx1)                                      # out_proj
+        g = ops.attn_backward(tape, da)                                    # dQ | dK | dV
+        dx = None
+        for i in (2, 1, 0):
+            dt = conv_backward(tape, g[:, i * C_:(i + 1) * C_])            # in-projection i
+            if dx is None:
+                dx = conv_backward(tape, dt, add_src=dx1)                  # v; + the first residual
+            else:
+                conv_backward(tape, dt, dx_out=dx, accumulate=True)        # k, q: x feeds all three
+        v = self._views()
+        for own, p in ((("own0", "own1", "own2"), self.ma.in_proj_weight), (("bias0", "bias1", "bias2"), self.ma.in_proj_bias)):
+            parts = [tape.pgrads.pop(v[o], None) for o in own]
+            if parts[0] is not None:                                       # no direct placement: the three row blocks -> the parameter
+                ops._add_pgrad(tape, p, torch.cat([t.reshape(C_, -1) for t in parts]).reshape(p.shape))
+        return dx
+
+
+class TransformerBlock(DyModule):
+    """Optional Conv, p + linear(p) (the learnable position embedding) and num_layers TransformerLayers (reference
+    transformer.py:120-139).  The reference's flatten / permute to [L, B, C] and back are the identity on an NHWC map."""
+
+    def __init__(self, c1, c2, num_heads, num_layers):
+        super().__init__()
+        self.conv = None
+        if c1 != c2:
+            self.conv = Conv(c1, c2)
+        self.linear = nn.Linear(c2, c2)
+        self.tr = nn.Sequential(*(TransformerLayer(c2, num_heads) for _ in range(num_layers)))
+        self.c2 = c2
+
+    # C3._fwd / _bwd walk `m` as a sequence of blocks: as C3TR's m this module is a sequence of one
+    def __len__(self):
+        return 1
+
+    def __iter__(self):
+        return iter((self,))
+
+    def __getitem__(self, i):
+        return (self,)[i]
+
+    def _linear_view(self):
+        w = self.linear.weight
+        c = self.__dict__.get("_lin_view_cache")
+        if c is None or c[0] != w.data_ptr():
+            c = (w.data_ptr(), w.detach().view(w.shape[0], w.shape[1], 1, 1))
+            self.__dict__["_lin_view_cache"] = c
+            ops.register_pack_view(c[1])
+        return c[1]
+
+    def _fwd(self, tape, x, out=None):
+        if self.conv is not None:
+            x = self.conv._fwd(tape, x)
+        n = len(self.tr)
+        x = conv_forward(tape, x, self._linear_view(), self.linear.bias, None, ACT_NONE, 1, 0, 1, False, out=out if n == 0 else None, residual=x,
+                         owner=self.linear.weight)
+        for i, m in enumerate(self.tr):
+            x = m._fwd(tape, x, out=out if i == n - 1 else None)
+        return x
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        for m in reversed(self.tr):
+            dy = m._bwd(tape, dy)
+        dx = conv_backward(tape, dy, add_src=dy)                           # p + linear(p)
+        if self.conv is not None:
+            return self.conv._bwd(tape, dx, needs=needs)
+        return dx
+
+
+class C3TR(C3):
+    """C3 whose m is a TransformerBlock of n layers and 4 heads (reference block.py:515-522)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        c_ = int(c2 * e)
+        if c_ % 32:
+            raise NotImplementedError(f"C3TR: the hidden width int(c2 * e) = {c_} must be a multiple of 32 (4 heads of a head dim D % 8 == 0)")
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = TransformerBlock(c_, c_, 4, n)
 
 
 class PConv(DyModule):

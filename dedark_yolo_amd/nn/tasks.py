@@ -16,7 +16,7 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
+from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
                       DyModule, FasterC2f, FasterC2f_N,
                       GhostBottleneck, GhostConv, MFRU,
                       PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
@@ -34,7 +34,7 @@ _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Det
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
                  Segment=Segment, Pose=Pose, Classify=Classify,
-                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost,
+                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost, C3TR=C3TR,
                  SCC2f=SCC2f, SC_PW_C2f=SC_PW_C2f, SC_Conv3_C2f=SC_Conv3_C2f, Conv3_SC_C2f=Conv3_SC_C2f, SCConvBottleneck=SCConvBottleneck,
                  SC_PW_Bottleneck=SC_PW_Bottleneck, SC_Conv3_Bottleneck=SC_Conv3_Bottleneck, Conv3_SC_Bottleneck=Conv3_SC_Bottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
@@ -101,7 +101,7 @@ _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
     PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
-    GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f,   # tasks.py:856-874
+    GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f, C3TR: _rule_c2f,   # tasks.py:856-874
     SCC2f: _rule_c2f, SC_PW_C2f: _rule_c2f, SC_Conv3_C2f: _rule_c2f, Conv3_SC_C2f: _rule_c2f,                         # tasks.py:744-752, 857-871
     SCConvBottleneck: _rule_conv_like, SC_PW_Bottleneck: _rule_conv_like, SC_Conv3_Bottleneck: _rule_conv_like, Conv3_SC_Bottleneck: _rule_conv_like,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),

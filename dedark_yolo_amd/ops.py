@@ -957,6 +957,55 @@ def cru_conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False):
     return dx
 
 
+# ------------------------------------------------------------------------------------------------ fused attention
+def _attn_dims(who, q, k, v, heads):
+    B, Cc, H, W = q.shape
+    if tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise RuntimeError(f"{who}: q, k and v must be NHWC views of one shape and dtype")
+    if heads < 1 or Cc % heads:
+        raise RuntimeError(f"{who}: {Cc} channels do not split into {heads} heads")
+    return B, Cc, H, W, H * W, Cc // heads
+
+
+def attn_forward(tape, q, k, v, heads, out=None):
+    """softmax(Q K^T / sqrt(D)) V over the pixels of a map (dy_attn_fwd; reference transformer.py:115, torch's
+    multi_head_attention_forward between in-projection and out_proj).  q / k / v / out: NHWC views [B, C, H, W] = token matrices
+    [B, L = H W, C], normally the three channel slices of one [B, 3C, H, W] buffer; head h = channels [h D, (h + 1) D).  With a
+    tape the log-sum-exp is kept for attn_backward."""
+    B, Cc, H, W, L, D = _attn_dims("attn_forward", q, k, v, heads)
+    o = out if out is not None else empty_nhwc(B, Cc, H, W, q.dtype, q.device)
+    if tuple(o.shape) != (B, Cc, H, W) or o.dtype != q.dtype:
+        raise RuntimeError("attn_forward: out must be an NHWC view of q's shape and dtype")
+    lse = torch.empty(B * heads * L, dtype=torch.float32, device=q.device) if tape is not None else None
+    _C._prof is not None and _C.set_meta(kind="attn_fwd", shape=f"{heads}x{D} L={L} B={B}", dtype=str(q.dtype), flops=4.0 * B * heads * L * L * D,
+                                         bytes=float(4 * B * L * Cc * q.element_size()))
+    call("dy_attn_fwd", ptr(q), ld_of(q), ptr(k), ld_of(k), ptr(v), ld_of(v), ptr(o), ld_of(o), ptr(lse), B, L, heads, D, D ** -0.5,
+         dt_id(q.dtype), stream())
+    emu_round(o)
+    if tape is not None:
+        tape.push((q, k, v, o, lse, heads))
+    return o
+
+
+def attn_backward(tape, dy, out=None):
+    """Backward of the matching attn_forward (pops its context; dy_attn_bwd, deterministic).  Returns the [B, 3C, H, W] NHWC buffer
+    dQ | dK | dV (`out` when given): the in-projections' data gradients read its three slices in place."""
+    q, k, v, o, lse, heads = tape.pop()
+    B, Cc, H, W, L, D = _attn_dims("attn_backward", q, k, v, heads)
+    if tuple(dy.shape) != (B, Cc, H, W) or dy.dtype != q.dtype:
+        raise RuntimeError("attn_backward: gradient does not match the forward's output")
+    g = out if out is not None else empty_nhwc(B, 3 * Cc, H, W, q.dtype, q.device)
+    if tuple(g.shape) != (B, 3 * Cc, H, W) or g.dtype != q.dtype:
+        raise RuntimeError("attn_backward: out must be an NHWC view of [B, 3C, H, W] in q's dtype")
+    dq, dk, dv = g[:, :Cc], g[:, Cc:2 * Cc], g[:, 2 * Cc:]
+    _C._prof is not None and _C.set_meta(kind="attn_bwd", shape=f"{heads}x{D} L={L} B={B}", dtype=str(q.dtype), flops=14.0 * B * heads * L * L * D,
+                                         bytes=float(8 * B * L * Cc * q.element_size()))
+    call("dy_attn_bwd", ptr(q), ld_of(q), ptr(k), ld_of(k), ptr(v), ld_of(v), ptr(o), ld_of(o), ptr(dy), ld_of(dy), ptr(lse), ptr(dq), ld_of(dq),
+         ptr(dk), ld_of(dk), ptr(dv), ld_of(dv), B, L, heads, D, D ** -0.5, dt_id(q.dtype), stream())
+    emu_round(g)
+    return g
+
+
 # ------------------------------------------------------------------------------------------------ depthwise conv
 def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
     """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.

@@ -215,6 +215,8 @@ _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bott
                                                                "SC_Conv3_C2f", "Conv3_SC_C2f", "SCConvBottleneck", "SC_PW_Bottleneck",
                                                                "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
+_REF_HOME.update({"C3TR": "ultralytics.nn.modules.block", "TransformerLayer": "ultralytics.nn.modules.transformer",
+                  "TransformerBlock": "ultralytics.nn.modules.transformer"})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
 # the front-end's filter objects (ultralytics/nn/modules/filtersB.py, filter_cfg.py:17-75): parameter-free modules holding these
@@ -245,6 +247,7 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "GhostConv": (), "DWConv": (), "GhostBottleneck": (), "C3": (), "C3Ghost": (),
               "SCC2f": ("c",), "SC_PW_C2f": ("c",), "SC_Conv3_C2f": ("c",), "Conv3_SC_C2f": ("c",), "SCConvBottleneck": ("add",),
               "SC_PW_Bottleneck": ("add",), "SC_Conv3_Bottleneck": ("add",), "Conv3_SC_Bottleneck": ("add",),
+              "C3TR": (), "TransformerLayer": (), "TransformerBlock": ("c2",),      # (torch's Linear / MultiheadAttention are torch_leaf children)
               "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}
@@ -419,6 +422,9 @@ class _RefWriter:
             kids["sigomid"] = self.torch_leaf(nn.Sigmoid(), "")
         elif name == "CRU":
             kids["advavg"] = self.torch_leaf(nn.AdaptiveAvgPool2d(1), "")
+        elif name == "TransformerBlock" and mod.conv is None:     # `self.conv = None` stays a plain attribute there (transformer.py:126)
+            state["conv"] = None
+            kids.pop("conv", None)
         elif name == "PConv":                             # the constructor binds the split_cat forward per instance (conv.py:169-172)
             state["forward"] = _RefMethod(obj, "forward_split_cat")
         elif name in ("Detect", "AsffDetect", "Segment", "Pose"):

@@ -344,6 +344,24 @@ int dy_cru_conv_dgrad(const void* dy, int64_t dy_ld, const void* wp, void* dx, i
  * launch adds them in range order; no atomics */
 int dy_cru_conv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw3, float* db, float* dw1, int B, int H, int W,
                       int G, int N, int C3, int C1, float* scratch, int64_t scratch_elems, int dtype, void* stream);
+/* ------------------------------------------------------------------------------------ fused multi-head attention (C3TR family)
+ * The nn.MultiheadAttention call of TransformerLayer.forward (U/nn/modules/transformer.py:109,115; torch's
+ * multi_head_attention_forward between its in-projection and out_proj, no masks, dropout 0):
+ *   O[b, i, h D + c] = sum_j softmax_j(scale * Q[b, i, h, :] . K[b, j, h, :]) * V[b, j, h D + c]
+ * q / k / v / o: token-major views [B L][ld] of the dtype, head h = channels [h D, (h + 1) D); exactly the H D channels of a token
+ * are read / written (element alignment is enough), so the views may be channel slices of one [B, L, 3 C] buffer with live
+ * neighbours.  L >= 1, H >= 1, D % 8 == 0, 8 <= D <= 128; anything else is an argument error.
+ * lse (nullable; training): f32 [B][H][L], log sum_j exp(scale * Q.K_j).  Softmax statistics are f32; in the 16-bit dtypes P is
+ * rounded to the dtype before P V. */
+int dy_attn_fwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o, int64_t o_ld, float* lse, int B,
+                int L, int H, int D, float scale, int dtype, void* stream);
+/* backward of dy_attn_fwd in the flash form (P = exp(scale S - lse) recomputed per tile, no L x L tensor in global memory):
+ * delta_i = sum_c dO_ic O_ic per head, dV = P^T dO, dS = P o (dO V^T - delta), dQ = scale dS K, dK = scale dS^T Q.  dq / dk / dv
+ * (overwritten) follow the view rules above.  Deterministic: dQ is summed by the workgroup that owns the query tile, dK / dV by the
+ * one that owns the key tile; no atomics, no hand-off between workgroups. */
+int dy_attn_bwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o, int64_t o_ld,
+                const void* dout, int64_t do_ld, const float* lse, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld, void* dv, int64_t dv_ld,
+                int B, int L, int H, int D, float scale, int dtype, void* stream);
 /* CIoU of n box pairs, xyxy f32 (reference ultralytics/utils/metrics.py:75-128 bbox_iou(b1, b2, xywh=False, CIoU=True): eps added to
  * h only, alpha constant in the backward); grad_b1 (nullable) [n,4] = d out[i] / d b1[i]. */
 int dy_bbox_ciou(const float* b1, const float* b2, int64_t n, float* out, float* grad_b1, void* stream);
