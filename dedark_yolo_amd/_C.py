@@ -64,6 +64,8 @@ class SegDesc(C.Structure):
 
 
 BIAS_GRAD_CHUNKS = 2048      # DY_BIAS_GRAD_CHUNKS
+LN_MAX_C = 2048              # DY_LN_MAX_C
+LN_MAX_PARTS = 512           # DY_LN_MAX_PARTS
 
 POSE_MAX_LEVELS = 4          # DY_POSE_MAX_LEVELS
 
@@ -140,6 +142,11 @@ _SIGS = {
     "dy_cru_conv_wgrad": [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp],
     "dy_attn_fwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, i32, vp],
     "dy_attn_bwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp],
+    "dy_add_layernorm_fwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32, f32, i32, vp],
+    "dy_add_layernorm_bwd": [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, i64, i64, i32, i32, vp],
+    "dy_gelu_fwd": [vp, i64, vp, i64, i64, i32, i32, vp],
+    "dy_gelu_bwd": [vp, i64, vp, i64, vp, i64, i64, i32, i32, vp],
+    "dy_add_pos": [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp],
     "dy_bbox_ciou": [vp, vp, i64, vp, vp, vp],
     "dy_bbox_iou": [vp, vp, i64, i32, i32, f32, vp, vp, vp],
     "dy_aug_resize_u8": [vp, i32, i32, i64, vp, i32, i32, i64, vp],

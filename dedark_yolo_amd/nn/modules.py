@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "TransformerLayer", "TransformerBlock", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "TransformerLayer", "TransformerBlock", "TransformerEncoderLayer", "AIFI", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
            "SC_Conv3_C2f", "Conv3_SC_C2f", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
@@ -629,6 +629,137 @@ class C3TR(C3):
             raise NotImplementedError(f"C3TR: the hidden width int(c2 * e) = {c_} must be a multiple of 32 (4 heads of a head dim D % 8 == 0)")
         super().__init__(c1, c2, n, shortcut, g, e)
         self.m = TransformerBlock(c_, c_, 4, n)
+
+
+class TransformerEncoderLayer(DyModule):
+    """The post-norm encoder layer over the pixels of an NHWC map = the token matrix [B, L = H W, C] (reference
+    ultralytics/nn/modules/transformer.py:20-67, forward_post):
+        q = k = src + pos; src = norm1(src + ma(q, k, src)); src = norm2(src + fc2(gelu(fc1(src))))
+    Real nn.MultiheadAttention / nn.Linear / nn.LayerNorm objects hold the parameters under the reference's names.  Six 1x1 convs
+    (the three in-projections with bias writing Q | K | V into the slices of one buffer, out_proj, fc1, fc2, all with bias),
+    ops.attn_forward, ops.add_pos, ops.gelu_forward and two ops.add_layernorm_forward: each residual add is fused into its
+    LayerNorm, the position table is a constant.  Called on a map this class adds no position term (the reference's pos=None)."""
+
+    def __init__(self, c1, cm=2048, num_heads=8, dropout=0.0, act=nn.GELU(), normalize_before=False):
+        super().__init__()
+        who = type(self).__name__
+        if normalize_before:
+            raise NotImplementedError(f"{who}: normalize_before=True (forward_pre) is not implemented")
+        if dropout:
+            raise NotImplementedError(f"{who}: dropout > 0 is not implemented")
+        if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
+            raise NotImplementedError(f"{who}: only the exact nn.GELU() activation is implemented, got {act!r}")
+        if c1 % num_heads or (c1 // num_heads) % 8 or not 8 <= c1 // num_heads <= 128:
+            raise NotImplementedError(f"{who}: head dim {c1}/{num_heads} is outside the attention kernels' rule D % 8 == 0, 8 <= D <= 128")
+        if cm % 4 or not 4 <= c1 <= 2048:
+            raise NotImplementedError(f"{who}: c1 = {c1} must be at most 2048 (the LayerNorm kernels) and cm = {cm} a multiple of 4")
+        self.ma = nn.MultiheadAttention(c1, num_heads, dropout=dropout, batch_first=True)
+        self.fc1 = nn.Linear(c1, cm)
+        self.fc2 = nn.Linear(cm, c1)
+        self.norm1 = nn.LayerNorm(c1)
+        self.norm2 = nn.LayerNorm(c1)
+        self.dropout = nn.Dropout(dropout)
+        self.dropout1 = nn.Dropout(dropout)
+        self.dropout2 = nn.Dropout(dropout)
+        self.act = act
+        self.normalize_before = normalize_before
+        self._c, self._cm, self._heads = c1, cm, num_heads
+
+    def _views(self):
+        """The Linear weights as [out, in, 1, 1] conv weights (the view OBJECTS are kept: the packed-weight caches live on them) and
+        the row proxies of the in-projection; rebuilt when the parameters moved."""
+        key = tuple(p.data_ptr() for p in (self.ma.in_proj_weight, self.ma.in_proj_bias, self.ma.out_proj.weight, self.fc1.weight, self.fc2.weight))
+        c = self.__dict__.get("_view_cache")
+        if c is None or c[0] != key:
+            C_ = self._c
+            v = {"out": self.ma.out_proj.weight.detach().view(C_, C_, 1, 1), "fc1": self.fc1.weight.detach().view(self._cm, C_, 1, 1),
+                 "fc2": self.fc2.weight.detach().view(C_, self._cm, 1, 1)}
+            wi, bi = self.ma.in_proj_weight, self.ma.in_proj_bias
+            for i in range(3):
+                v[f"in{i}"] = wi.detach()[i * C_:(i + 1) * C_].view(C_, C_, 1, 1)
+                v[f"own{i}"] = _ParamRows(wi, i * C_, (i + 1) * C_)
+                v[f"bias{i}"] = _ParamRows(bi, i * C_, (i + 1) * C_)
+            for t in v.values():
+                if torch.is_tensor(t):
+                    ops.register_pack_view(t)
+            c = (key, v)
+            self.__dict__["_view_cache"] = c
+        return c[1]
+
+    def _pos(self, x):
+        return None
+
+    def _check(self):
+        who = type(self).__name__
+        if self.normalize_before:
+            raise NotImplementedError(f"{who}: normalize_before=True (forward_pre) is not implemented")
+        if self.ma.dropout or self.dropout.p or self.dropout1.p or self.dropout2.p:
+            raise NotImplementedError(f"{who}: dropout > 0 is not implemented")
+        if not isinstance(self.act, nn.GELU) or getattr(self.act, "approximate", "none") != "none":
+            raise NotImplementedError(f"{who}: only the exact nn.GELU() activation is implemented, got {self.act!r}")
+
+    def forward(self, x, src_mask=None, src_key_padding_mask=None, pos=None, out=None):
+        if src_mask is not None or src_key_padding_mask is not None:
+            raise NotImplementedError(f"{type(self).__name__}: attention masks and key-padding masks are not implemented")
+        if pos is not None:
+            raise NotImplementedError(f"{type(self).__name__}: an explicit position tensor is not implemented (AIFI builds its own table)")
+        return super().forward(x, out=out)
+
+    def _fwd(self, tape, x, out=None):
+        self._check()
+        v, C_ = self._views(), self._c
+        B, _, H, W = x.shape
+        lin = lambda t, w, owner, bias, out=None: conv_forward(tape, t, w, bias, None, ACT_NONE, 1, 0, 1, False, out=out, owner=owner)
+        pos = self._pos(x)
+        p = x if pos is None else ops.add_pos(x, pos)
+        qkv = empty_nhwc(B, 3 * C_, H, W, x.dtype, x.device)
+        for i in range(3):
+            lin(p if i < 2 else x, v[f"in{i}"], v[f"own{i}"], v[f"bias{i}"], out=qkv[:, i * C_:(i + 1) * C_])
+        a = ops.attn_forward(tape, qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], self._heads)
+        s2 = lin(a, v["out"], self.ma.out_proj.weight, self.ma.out_proj.bias)
+        x1 = ops.add_layernorm_forward(tape, x, s2, self.norm1)
+        u = lin(x1, v["fc1"], self.fc1.weight, self.fc1.bias)
+        t = ops.gelu_forward(tape, u)
+        s3 = lin(t, v["fc2"], self.fc2.weight, self.fc2.bias)
+        return ops.add_layernorm_forward(tape, x1, s3, self.norm2, out=out)
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        C_ = self._c
+        dz2 = ops.add_layernorm_backward(tape, dy)                         # norm2: the gradient of x1 (residual) and of fc2's output
+        dt = conv_backward(tape, dz2)                                      # fc2
+        du = ops.gelu_backward(tape, dt)
+        dx1 = conv_backward(tape, du, add_src=dz2)                         # fc1; + the second residual
+        dz1 = ops.add_layernorm_backward(tape, dx1)                        # norm1: the gradient of src (residual) and of out_proj's output
+        da = conv_backward(tape, dz1)                                      # out_proj
+        g = ops.attn_backward(tape, da)                                    # dQ | dK | dV
+        dx = conv_backward(tape, g[:, 2 * C_:], add_src=dz1)               # V's in-projection reads src; + the first residual
+        for i in (1, 0):                                                   # K, Q read src + pos: the table gets no gradient
+            conv_backward(tape, g[:, i * C_:(i + 1) * C_], dx_out=dx, accumulate=True)
+        v = self._views()
+        for own, p in ((("own0", "own1", "own2"), self.ma.in_proj_weight), (("bias0", "bias1", "bias2"), self.ma.in_proj_bias)):
+            parts = [tape.pgrads.pop(v[o], None) for o in own]
+            if parts[0] is not None:                                       # no direct placement: the three row blocks -> the parameter
+                ops._add_pgrad(tape, p, torch.cat([t.reshape(C_, -1) for t in parts]).reshape(p.shape))
+        return dx
+
+
+class AIFI(TransformerEncoderLayer):
+    """TransformerEncoderLayer on a [B, C, H, W] map with the fixed 2D sine-cosine position table added to the queries and keys
+    (reference transformer.py:70-97).  The table is the reference's build_2d_sincos_position_embedding(w, h, C), built on the host
+    and cached per (w, h, C, dtype, device) (ops.pos_table): its row p holds (iw, ih) = (p // H, p % H) while token p is the pixel
+    (p // W, p % W) -- on a non-square map the two disagree, and the reference trains that way."""
+
+    def __init__(self, c1, cm=2048, num_heads=8, dropout=0, act=nn.GELU(), normalize_before=False):
+        if c1 % 4:
+            raise ValueError("Embed dimension must be divisible by 4 for 2D sin-cos position embedding")
+        super().__init__(c1, cm, num_heads, dropout, act, normalize_before)
+
+    def _pos(self, x):
+        return ops.pos_table(x.shape[3], x.shape[2], self._c, x.dtype, x.device)
+
+    @staticmethod
+    def build_2d_sincos_position_embedding(w, h, embed_dim=256, temperature=10000.0):
+        return ops.sincos_pos_table(w, h, embed_dim, temperature)[None]
 
 
 class PConv(DyModule):

@@ -16,11 +16,11 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
+from .modules import (AIFI, AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
                       DyModule, FasterC2f, FasterC2f_N,
                       GhostBottleneck, GhostConv, MFRU,
                       PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
-                      SC_PW_C2f, SPPF, Segment, Tape, Upsample,
+                      SC_PW_C2f, SPPF, Segment, Tape, TransformerEncoderLayer, Upsample,
                       lowlight_recovery)
 
 # One autograd node for the whole layer graph (training): the plan walks its nodes forwards with one Tape per module and backwards in
@@ -35,6 +35,7 @@ _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Det
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
                  Segment=Segment, Pose=Pose, Classify=Classify,
                  GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost, C3TR=C3TR,
+                 AIFI=AIFI, TransformerEncoderLayer=TransformerEncoderLayer,
                  SCC2f=SCC2f, SC_PW_C2f=SC_PW_C2f, SC_Conv3_C2f=SC_Conv3_C2f, Conv3_SC_C2f=Conv3_SC_C2f, SCConvBottleneck=SCConvBottleneck,
                  SC_PW_Bottleneck=SC_PW_Bottleneck, SC_Conv3_Bottleneck=SC_Conv3_Bottleneck, Conv3_SC_Bottleneck=Conv3_SC_Bottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
@@ -74,7 +75,7 @@ def yaml_model_load(path):
 # (constructor arguments, output channels, module repeats), and the rows are compiled ONCE into a flat execution plan
 # (GraphPlan: per node its source nodes and the node after which its output is dead), which forward passes just walk.
 class _Row:
-    __slots__ = ("index", "src", "repeats", "kind", "args", "ch_in", "nc", "width", "max_ch")
+    __slots__ = ("index", "src", "repeats", "yaml_repeats", "kind", "args", "ch_in", "nc", "width", "max_ch")
 
 
 def _scaled_width(c, row):
@@ -97,6 +98,12 @@ def _rule_segment(row):                   # tasks.py:897-900: append the input w
     return args, row.ch_in[0], row.repeats
 
 
+def _rule_aifi(row):                      # tasks.py `elif m is AIFI: args = [ch[f], *args]`; cm / heads are not width-scaled
+    if row.yaml_repeats != 1:             # a depth-scaled stack of encoder layers: only the single layer is built and tested
+        raise NotImplementedError(f"AIFI row {row.index}: repeats = {row.yaml_repeats} (a stack of encoder layers) is not implemented, write one row per layer")
+    return [row.ch_in[0], *row.args], row.ch_in[0], 1
+
+
 _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
@@ -104,6 +111,7 @@ _RULES = {
     GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f, C3TR: _rule_c2f,   # tasks.py:856-874
     SCC2f: _rule_c2f, SC_PW_C2f: _rule_c2f, SC_Conv3_C2f: _rule_c2f, Conv3_SC_C2f: _rule_c2f,                         # tasks.py:744-752, 857-871
     SCConvBottleneck: _rule_conv_like, SC_PW_Bottleneck: _rule_conv_like, SC_Conv3_Bottleneck: _rule_conv_like, Conv3_SC_Bottleneck: _rule_conv_like,
+    AIFI: _rule_aifi,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
     AsffTribeLevel: lambda r: (r.args, 512 if r.args[0] in (0, 1) else 256, r.repeats),       # tasks.py:892-896
@@ -118,7 +126,7 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample)      # (C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample, TransformerEncoderLayer)      # (TransformerEncoderLayer covers AIFI, C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):
@@ -334,7 +342,7 @@ def parse_model(d, ch, verbose=False):
         row = _Row()
         row.index, row.src, row.kind, row.nc, row.width, row.max_ch = index, src, kind, nc, width, max_ch
         row.args = [nc if a == "nc" else d.get("kpt_shape") if a == "kpt_shape" else _literal(a, ast) for a in args]
-        row.repeats = max(round(repeats * depth), 1) if repeats > 1 else repeats
+        row.repeats, row.yaml_repeats = (max(round(repeats * depth), 1) if repeats > 1 else repeats), repeats
         rel = [src] if isinstance(src, int) else list(src)
         row.ch_in = [(widths[j] if widths else ch) if j == -1 else widths[j] for j in rel]
         ctor_args, c_out, n_mod = _RULES.get(cls, _PASS_THROUGH)(row)

@@ -1006,6 +1006,137 @@ def attn_backward(tape, dy, out=None):
     return g
 
 
+# ------------------------------------------------------------------------------------------------ transformer encoder layer
+def _same_view(who, ref, *others):
+    for t in others:
+        if t is not None and (tuple(t.shape) != tuple(ref.shape) or t.dtype != ref.dtype):
+            raise RuntimeError(f"{who}: every operand must be an NHWC view of one shape and dtype")
+
+
+def ln_parts(rows, C_):
+    """workgroups (= dgamma / dbeta partials) of dy_add_layernorm_bwd, the launcher's own rule (include/dedark_yolo.h)"""
+    per = 1 if C_ > 1024 else 4
+    return max(1, min(_C.LN_MAX_PARTS, (rows + per - 1) // per))
+
+
+def add_layernorm_forward(tape, a, b, norm, out=None):
+    """y = LayerNorm(a + b) over the channels of every pixel (dy_add_layernorm_fwd; reference transformer.py:46-47, 49-50: the
+    residual add and nn.LayerNorm in one pass, a + b never stored).  a / b / out: NHWC views [B, C, H, W]; b may be None.  norm: the
+    nn.LayerNorm that owns weight, bias and eps.  With a tape the rows' (mean, rstd) are kept for add_layernorm_backward."""
+    B, Cc, H, W = a.shape
+    _same_view("add_layernorm_forward", a, b, out)
+    if tuple(norm.normalized_shape) != (Cc,) or norm.weight is None or norm.bias is None:
+        raise RuntimeError(f"add_layernorm_forward: the LayerNorm must be affine over the {Cc} channels")
+    y = out if out is not None else empty_nhwc(B, Cc, H, W, a.dtype, a.device)
+    rows = B * H * W
+    stats = torch.empty(rows * 2, dtype=torch.float32, device=a.device) if tape is not None else None
+    _C._prof is not None and _C.set_meta(kind="add_layernorm_fwd", shape=f"{Cc}ch {rows}px", dtype=str(a.dtype), flops=0.0,
+                                         bytes=float((3 if b is not None else 2) * rows * Cc * a.element_size()))
+    call("dy_add_layernorm_fwd", ptr(a), ld_of(a), ptr(b), ld_of(b) if b is not None else 0, ptr(norm.weight), ptr(norm.bias), ptr(y), ld_of(y),
+         ptr(stats), rows, Cc, norm.eps, dt_id(a.dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        tape.push((a, b, stats, norm))
+    return y
+
+
+def add_layernorm_backward(tape, dy, dz_out=None, accumulate=False):
+    """Backward of the matching add_layernorm_forward (pops its context; dy_add_layernorm_bwd, deterministic).  Returns dz, the
+    gradient of a and of b alike (`dz_out` when given; accumulate: added into it); norm.weight / norm.bias get their gradients."""
+    a, b, stats, norm = tape.pop()
+    B, Cc, H, W = a.shape
+    _same_view("add_layernorm_backward", a, dy, dz_out)
+    dz = dz_out if dz_out is not None else empty_nhwc(B, Cc, H, W, a.dtype, a.device)
+    rows, dev = B * H * W, a.device
+    need = norm.weight.requires_grad or norm.bias.requires_grad
+    gw = gb = scratch = None
+    direct = False
+    if need:
+        gb_ = _grad_dst(norm.bias)
+        gw, direct = _grad_sink(norm.weight, (2, Cc), dev, gb_ is None)       # direct only when both can (as _bn_backward)
+        gw, gb = (gw, gb_) if direct else (gw[0], gw[1])
+        scratch = torch.empty(ln_parts(rows, Cc) * 2 * Cc, dtype=torch.float32, device=dev)
+    _C._prof is not None and _C.set_meta(kind="add_layernorm_bwd", shape=f"{Cc}ch {rows}px", dtype=str(a.dtype), flops=0.0,
+                                         bytes=float((4 if b is not None else 3) * rows * Cc * a.element_size()))
+    call("dy_add_layernorm_bwd", ptr(a), ld_of(a), ptr(b), ld_of(b) if b is not None else 0, ptr(stats), ptr(norm.weight), ptr(dy), ld_of(dy),
+         ptr(dz), ld_of(dz), 1 if (accumulate and dz_out is not None) else 0, ptr(gw), ptr(gb), ptr(scratch),
+         0 if scratch is None else scratch.numel(), rows, Cc, dt_id(a.dtype), stream())
+    emu_round(dz)
+    if need and not direct:
+        _add_pgrad(tape, norm.weight, gw)
+        _add_pgrad(tape, norm.bias, gb)
+    return dz
+
+
+def gelu_forward(tape, u, out=None):
+    """y = 0.5 u (1 + erf(u / sqrt 2)), nn.GELU()'s default (dy_gelu_fwd; reference transformer.py:48).  With a tape the
+    pre-activation u is kept for gelu_backward."""
+    B, Cc, H, W = u.shape
+    _same_view("gelu_forward", u, out)
+    y = out if out is not None else empty_nhwc(B, Cc, H, W, u.dtype, u.device)
+    _C._prof is not None and _C.set_meta(kind="gelu_fwd", shape=f"{Cc}ch {B * H * W}px", dtype=str(u.dtype), flops=0.0,
+                                         bytes=float(2 * B * H * W * Cc * u.element_size()))
+    call("dy_gelu_fwd", ptr(u), ld_of(u), ptr(y), ld_of(y), B * H * W, Cc, dt_id(u.dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        tape.push(u)
+    return y
+
+
+def gelu_backward(tape, dy, out=None):
+    """du = dy (Phi(u) + u phi(u)) of the matching gelu_forward (pops its context; dy_gelu_bwd)"""
+    u = tape.pop()
+    B, Cc, H, W = u.shape
+    _same_view("gelu_backward", u, dy, out)
+    du = out if out is not None else empty_nhwc(B, Cc, H, W, u.dtype, u.device)
+    _C._prof is not None and _C.set_meta(kind="gelu_bwd", shape=f"{Cc}ch {B * H * W}px", dtype=str(u.dtype), flops=0.0,
+                                         bytes=float(3 * B * H * W * Cc * u.element_size()))
+    call("dy_gelu_bwd", ptr(u), ld_of(u), ptr(dy), ld_of(dy), ptr(du), ld_of(du), B * H * W, Cc, dt_id(u.dtype), stream())
+    emu_round(du)
+    return du
+
+
+def sincos_pos_table(w, h, c, temperature=10000.0):
+    """The reference's AIFI.build_2d_sincos_position_embedding(w, h, c) (transformer.py:83-97) restated: f32 [w h, c] on the CPU.
+    Its meshgrid is indexing='ij' over (grid_w, grid_h), so row p holds (iw, ih) = (p // h, p % h)."""
+    if c % 4:
+        raise ValueError("Embed dimension must be divisible by 4 for 2D sin-cos position embedding")
+    gw, gh = torch.meshgrid(torch.arange(int(w), dtype=torch.float32), torch.arange(int(h), dtype=torch.float32), indexing="ij")
+    pos_dim = c // 4
+    omega = torch.arange(pos_dim, dtype=torch.float32) / pos_dim
+    omega = 1.0 / (temperature ** omega)
+    ow = gw.flatten()[..., None] @ omega[None]
+    oh = gh.flatten()[..., None] @ omega[None]
+    return torch.cat([torch.sin(ow), torch.cos(ow), torch.sin(oh), torch.cos(oh)], dim=1)
+
+
+_pos_tables = {}
+
+
+def pos_table(w, h, c, dtype, device):
+    """sincos_pos_table in `dtype` on `device`, built once per (w, h, c, dtype, device)"""
+    key = (int(w), int(h), int(c), dtype, str(device))
+    t = _pos_tables.get(key)
+    if t is None:
+        t = _pos_tables[key] = sincos_pos_table(w, h, c).to(dtype).to(device).contiguous()
+    return t
+
+
+def add_pos(x, pos, out=None):
+    """y[b, :, p] = x[b, :, p] + pos[p, :] over the pixels p of an NHWC map (dy_add_pos; reference transformer.py:41); pos: dense
+    [H W, C] table of x's dtype.  The table is a constant: there is no backward."""
+    B, Cc, H, W = x.shape
+    _same_view("add_pos", x, out)
+    if tuple(pos.shape) != (H * W, Cc) or pos.dtype != x.dtype or not pos.is_contiguous():
+        raise RuntimeError("add_pos: pos must be a dense [H W, C] table of x's dtype")
+    y = out if out is not None else empty_nhwc(B, Cc, H, W, x.dtype, x.device)
+    _C._prof is not None and _C.set_meta(kind="add_pos", shape=f"{Cc}ch {B * H * W}px", dtype=str(x.dtype), flops=0.0,
+                                         bytes=float(2 * B * H * W * Cc * x.element_size()))
+    call("dy_add_pos", ptr(x), ld_of(x), ptr(pos), ptr(y), ld_of(y), B, H * W, Cc, dt_id(x.dtype), stream())
+    emu_round(y)
+    return y
+
+
 # ------------------------------------------------------------------------------------------------ depthwise conv
 def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
     """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.

@@ -216,7 +216,8 @@ _REF_HOME.update({n: "ultralytics.nn.modules.block" for n in ("C2", "C2f", "Bott
                                                                "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck")})
 _REF_HOME.update({n: "ultralytics.nn.modules.head" for n in ("Detect", "AsffDetect")})
 _REF_HOME.update({"C3TR": "ultralytics.nn.modules.block", "TransformerLayer": "ultralytics.nn.modules.transformer",
-                  "TransformerBlock": "ultralytics.nn.modules.transformer"})
+                  "TransformerBlock": "ultralytics.nn.modules.transformer", "AIFI": "ultralytics.nn.modules.transformer",
+                  "TransformerEncoderLayer": "ultralytics.nn.modules.transformer"})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
 # the front-end's filter objects (ultralytics/nn/modules/filtersB.py, filter_cfg.py:17-75): parameter-free modules holding these
@@ -248,6 +249,7 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "SCC2f": ("c",), "SC_PW_C2f": ("c",), "SC_Conv3_C2f": ("c",), "Conv3_SC_C2f": ("c",), "SCConvBottleneck": ("add",),
               "SC_PW_Bottleneck": ("add",), "SC_Conv3_Bottleneck": ("add",), "Conv3_SC_Bottleneck": ("add",),
               "C3TR": (), "TransformerLayer": (), "TransformerBlock": ("c2",),      # (torch's Linear / MultiheadAttention are torch_leaf children)
+              "AIFI": ("normalize_before",), "TransformerEncoderLayer": ("normalize_before",),   # (LayerNorm, GELU and the Dropouts are torch_leaf children too)
               "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}

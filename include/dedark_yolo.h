@@ -362,6 +362,33 @@ int dy_attn_fwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const 
 int dy_attn_bwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o, int64_t o_ld,
                 const void* dout, int64_t do_ld, const float* lse, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld, void* dv, int64_t dv_ld,
                 int B, int L, int H, int D, float scale, int dtype, void* stream);
+/* ------------------------------------------------------------------------------------ transformer encoder layer (AIFI family)
+ * The element-wise side of TransformerEncoderLayer.forward_post / AIFI.forward (U/nn/modules/transformer.py:53-62, 88-109).
+ * All views are token matrices [rows][ld] of the dtype, ld >= C, C % 4 == 0; exactly C channels of a row are touched, so a view may
+ * be a channel slice with live neighbours.  16-byte accesses where C, every ld and every base allow, element accesses otherwise.
+ *
+ * y = LayerNorm(a + b) (transformer.py:59-60 `src = src + self.dropout1(src2); src = self.norm1(src)`, :61-62 for norm2):
+ *   z = a + b (b nullable: z = a), y = (z - mean(z)) rsqrt(var(z) + eps) gamma + beta, biased variance of the centred values, f32
+ * statistics; z is never written.  stats (nullable; training): f32 [rows][2] = mean, rstd.  4 <= C <= DY_LN_MAX_C. */
+#define DY_LN_MAX_C 2048
+#define DY_LN_MAX_PARTS 512
+int dy_add_layernorm_fwd(const void* a, int64_t a_ld, const void* b, int64_t b_ld, const float* gamma, const float* beta, void* y,
+                         int64_t y_ld, float* stats, int64_t rows, int C, float eps, int dtype, void* stream);
+/* backward: z^ recomputed from a, b and stats; g = dy gamma, dz = rstd (g - mean(g) - z^ mean(g z^)) is the gradient of a AND of b
+ * (accumulate != 0: added into dz).  dgamma = sum_rows dy z^, dbeta = sum_rows dy (both nullable, together): per-workgroup f32
+ * partials over row ranges fixed by the shape, added by a second kernel in an order fixed by their count; no atomics, identical
+ * bytes on every run.  scratch: 2 C min(DY_LN_MAX_PARTS, ceil(rows / (C > 1024 ? 1 : 4))) floats. */
+int dy_add_layernorm_bwd(const void* a, int64_t a_ld, const void* b, int64_t b_ld, const float* stats, const float* gamma, const void* dy,
+                         int64_t dy_ld, void* dz, int64_t dz_ld, int accumulate, float* dgamma, float* dbeta, float* scratch,
+                         int64_t scratch_elems, int64_t rows, int C, int dtype, void* stream);
+/* exact GELU, nn.GELU()'s default (transformer.py:61 `self.act(self.fc1(src))`): y = 0.5 u (1 + erf(u / sqrt 2));
+ * du = dy (Phi(u) + u phi(u)); f32 arithmetic */
+int dy_gelu_fwd(const void* u, int64_t u_ld, void* y, int64_t y_ld, int64_t pixels, int C, int dtype, void* stream);
+int dy_gelu_bwd(const void* u, int64_t u_ld, const void* dy, int64_t dy_ld, void* du, int64_t du_ld, int64_t pixels, int C, int dtype,
+                void* stream);
+/* y[b][l][c] = x[b][l][c] + pos[l][c] (transformer.py:49-51 with_pos_embed; AIFI.forward :103-105): pos is the dense [L][C] table
+ * in the dtype, built on the host; the sum is taken in f32 and rounded once */
+int dy_add_pos(const void* x, int64_t x_ld, const void* pos, void* y, int64_t y_ld, int B, int L, int C, int dtype, void* stream);
 /* CIoU of n box pairs, xyxy f32 (reference ultralytics/utils/metrics.py:75-128 bbox_iou(b1, b2, xywh=False, CIoU=True): eps added to
  * h only, alpha constant in the backward); grad_b1 (nullable) [n,4] = d out[i] / d b1[i]. */
 int dy_bbox_ciou(const float* b1, const float* b2, int64_t n, float* out, float* grad_b1, void* stream);
