@@ -2,7 +2,8 @@
 GPU, per dispatch route of csrc/: generic implicit GEMM (f32 exact MFMA and bf16), pipelined v2, 3x3 band kernel v3,
 parity-split stride-2 dgrad, direct stem / thin kernels, pipelined weight gradient.  Inputs of the bf16 cases are rounded to
 bf16 before the reference runs, so the difference is output rounding and accumulation order only:
-tolerance 1e-5 * max|ref| (f32) and 1e-2 * max|ref| (bf16)."""
+tolerance 1e-5 * max|ref| (f32) and 1e-2 * max|ref| (bf16); the f32 outputs dW and db also element by element against float64
+(tests/conv_budget_ref.py; per route, with sliced views and accumulating data gradients: tests/test_gpu_conv_budget.py)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -55,6 +56,17 @@ def _case(dtype, B, Cin, Cout, H, W, k, s, p, d=1, routes=None):
             if kern:
                 routes[name] = kern
         _C._prof = None
+    # dW and db are f32 sums of products of rounded operands: besides the scalar bounds of the callers, every element is held to the
+    # f32-accumulation budget of tests/conv_budget_ref.py against float64 (a pixel tail dropped or counted twice, a halo column of the
+    # band weight gradient counted twice: invisible at 1e-2 * max|ref| from 16,384 pixels on)
+    # (not the two shapes whose output exceeds 128 MiB: they are there for the non-temporal epilogue stores of the forward and the
+    #  data gradient, their weight-gradient kernels run on the 12- and 32-image shapes too, and float64 takes 6 to 9 s on them)
+    if gy.numel() * 2 <= (128 << 20):
+        import conv_budget_ref as R
+        refs = R.conv_refs(xr.detach(), wq.detach(), gy.to(dtype), None, s, p, d, which=("dw", "db"))
+        for name, got in (("dw", tape.pgrads[w]), ("db", tape.pgrads[bias])):
+            rep = R.compare(name, got.detach(), *refs[name], R.C_OF[name], torch.float32, gy.numel() // Cout)
+            assert rep.worst <= 1.0, (dtype, (B, Cin, Cout, H, W, k, s, p, d), str(rep))
     return dict(fwd=_err(y, ref), dx=_err(dx, xr2.grad), dw=_err(tape.pgrads[w], wq2.grad), db=_err(tape.pgrads[bias], b2.grad))
 
 
@@ -351,8 +363,9 @@ _WGRAD_BOUND = {torch.float32: 1e-5, torch.bfloat16: 1e-2, torch.float16: 2e-3}
 def test_wgrad_routes_plan_edges(dtype, shape, kernel, min_scratch, own_error):
     """dy_conv2d_wgrad called directly, per route and tile variant, with the default 32 Mi-float scratch and with scratch_elems cut to
     the smallest value at which the route is still taken (the shared split plan's "clamped by what fits" branch): the expected kernel
-    ran, dW is within the file's bounds of F.conv2d's on the rounded operands, and a repeat gives the same bits (the slabs are added in
-    a fixed order).  One float less is "scratch too small" for the routes that plan from the scratch they are given."""
+    ran, dW is within the file's bounds of F.conv2d's on the rounded operands and, element by element, within the f32-accumulation
+    budget of tests/conv_budget_ref.py against float64 (a dropped pixel tail or a K-step counted twice at a split boundary), and a
+    repeat gives the same bits (the slabs are added in a fixed order).  One float less is "scratch too small" for the routes that plan from the scratch they are given."""
     from dedark_yolo_amd import _C, ops
     B, Cin, Cout, H, W, k, s, p = shape
     torch.manual_seed(B * 1000 + Cin + Cout + H)
@@ -362,6 +375,8 @@ def test_wgrad_routes_plan_edges(dtype, shape, kernel, min_scratch, own_error):
     w0 = torch.zeros(Cout, Cin, k, k, device="cuda", requires_grad=True)
     F.conv2d(x.float(), w0, None, s, p).backward(dz.float())
     ref = w0.grad
+    import conv_budget_ref as R                      # ... and element-wise against float64 on the budget of conv_budget_ref.py
+    ref64, S64 = R.conv_refs(x, w0.detach(), dz, None, s, p, 1, which=("dw",))["dw"]
     st = ops.stream()
     scratch = ops.wgrad_scratch(x.device, tag=st)
     assert scratch.numel() == 32 << 20
@@ -381,6 +396,9 @@ def test_wgrad_routes_plan_edges(dtype, shape, kernel, min_scratch, own_error):
         err = _err(gw, ref)
         print(f"{_DTYPE_NAME[dtype]} {shape} scratch_elems={elems}: {sym} err={err:.3g}")
         assert err < _WGRAD_BOUND[dtype], (elems, err)
+        rep = R.compare("dw", gw, ref64, S64, R.C_WGRAD, torch.float32, B * Ho * Wo)
+        print(f"    {rep}")
+        assert rep.worst <= 1.0, (elems, str(rep))
         again, _ = run(elems)
         assert torch.equal(gw, again), elems
     if own_error:
