@@ -1,4 +1,4 @@
-// Host/device math shared by the loss kernels and the CPU-side math harness (tests/test_host_math.py).
+// Host/device math shared by the loss kernels and the CPU-side math harness (tests/test_lossmath_cpu.py).
 // CIoU follows bbox_iou(xywh=False, CIoU=True) of the reference (ultralytics/utils/metrics.py:75-128):
 // eps is added to h only, alpha is a constant in the backward (computed under no_grad).
 #pragma once
@@ -188,8 +188,9 @@ DY_HD inline float dy_dfl_side(const float* x, float t, float* wl_out, int* tl_o
   return (lse - x[tl]) * wl + (lse - x[tl + 1]) * wr;
 }
 
-// BCE-with-logits element (torch formula): (1-t)*x + max(-x,0) + log(exp(-m) + exp(-x-m)), m = max(-x,0)
+// BCE-with-logits element: max(x,0) - x*t + log1p(exp(-|x|)).  Equal to torch's (1-t)*x + m + log(exp(-m) + exp(-x-m)), m = max(-x,0),
+// but that sum rounds 1 + exp(-|x|) to f32 first: at the class logits of a freshly initialised head (-11 .. -14) it loses 1e-2 .. all
+// of the element, and log1p keeps it to a few ulp.
 DY_HD inline float dy_bce(float x, float t) {
-  float m = dy_fmaxf(-x, 0.f);
-  return (1.f - t) * x + m + logf(expf(-m) + expf(-x - m));
+  return dy_fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
 }
