@@ -102,6 +102,10 @@ _SIGS = {
     "dy_bn_act_bwd_reduce": [vp, i64, vp, i64, vp, vp, vp, vp, i32, i32, vp, i64, i32, i32, vp],
     "dy_bn_act_bwd_apply": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, vp],
     "dy_bn_act_bwd_apply_valid": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp],
+    "dy_bn2_act_fwd": [vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, i64, i64, i32, i32, vp],
+    "dy_bn2_act_bwd_workspace": [i64, i32, i32],
+    "dy_bn2_act_bwd": [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64,
+                       i64, i32, i32, vp],
     "dy_maxpool_fwd": [vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_maxpool_bwd": [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "dy_upsample_nearest_fwd": [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp],
@@ -226,7 +230,7 @@ def lib():
         for name, sig in _SIGS.items():
             fn = getattr(L, name)          # AttributeError if the .so does not export a declared symbol
             fn.argtypes = sig
-            fn.restype = C.c_int64 if name == "dy_pack_item_blocks" else C.c_int
+            fn.restype = C.c_int64 if name in ("dy_pack_item_blocks", "dy_bn2_act_bwd_workspace") else C.c_int
         _lib = L
     return _lib
 

@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "TransformerLayer", "TransformerBlock", "TransformerEncoderLayer", "AIFI", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "RepConv", "RepC3","TransformerLayer", "TransformerBlock", "TransformerEncoderLayer", "AIFI", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
            "SC_Conv3_C2f", "Conv3_SC_C2f", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
@@ -470,6 +470,103 @@ class C3Ghost(C3):
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__(c1, c2, n, shortcut, g, e)
         self.m = nn.Sequential(*(GhostBottleneck(self._c, self._c) for _ in range(n)))
+
+
+class RepConv(DyModule):
+    """act(conv1(x) + conv2(x)), conv1 = Conv 3x3 + BatchNorm, conv2 = Conv 1x1 + BatchNorm, both without activation (reference
+    ultralytics/nn/modules/conv.py:193-291).  Training and unfused eval run the two raw convolutions and ONE two-branch
+    BatchNorm + activation kernel (ops.repconv_forward); after fuse_convs() the block is one 3x3 convolution with a bias and the
+    activation in its epilogue.  The BatchNorm identity branch (bn=True), stride, groups, dilation and c1 != c2 are refused."""
+    default_act = nn.SiLU()
+
+    def __init__(self, c1, c2, k=3, s=1, p=1, g=1, d=1, act=True, bn=False, deploy=False):
+        super().__init__()
+        assert k == 3 and p == 1
+        for name, val, only in (("s", s, 1), ("g", g, 1), ("d", d, 1), ("bn", bool(bn), False)):
+            if val != only:
+                raise NotImplementedError(f"RepConv: {name}={val!r} is outside the Dedark-YOLO hot path (only {name}={only!r} is implemented)")
+        if c1 != c2:
+            raise NotImplementedError(f"RepConv: c1={c1} != c2={c2} is outside the Dedark-YOLO hot path")
+        self.g, self.c1, self.c2 = g, c1, c2
+        self.act = self.default_act if act is True else act if isinstance(act, nn.Module) else nn.Identity()
+        self._act = _act_code(self.act)
+        self.bn = None
+        self.conv1 = Conv(c1, c2, k, s, p=p, g=g, act=False)
+        self.conv2 = Conv(c1, c2, 1, s, p=(p - k // 2), g=g, act=False)
+
+    def _fwd(self, tape, x, out=None):
+        if "conv" in self._modules:          # fused (fuse_convs): one 3x3 conv, bias and activation in the epilogue
+            c = self.conv
+            return conv_forward(tape, x, c.weight, c.bias, None, self._act, 1, 1, 1, False, out=out)
+        return ops.repconv_forward(tape, x, self.conv1, self.conv2, self._act, self.training, out=out)
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False, add_src=None):
+        bwd = conv_backward if "conv" in self._modules else ops.repconv_backward
+        return bwd(tape, dy, need_dx=needs[0], dx_out=dx_out, accumulate=accumulate, add_src=add_src)
+
+    def _fuse_bn_tensor(self, branch):
+        """conv.py:241-266 for a Conv branch, in f32: (W gamma / std, beta - running_mean gamma / std)"""
+        w, bn = branch.conv.weight.detach().float(), branch.bn
+        std = (bn.running_var.detach().float() + bn.eps).sqrt()
+        gamma, beta, mean = bn.weight.detach().float(), bn.bias.detach().float(), bn.running_mean.detach().float()
+        return w * (gamma / std).reshape(-1, 1, 1, 1), beta - mean * gamma / std
+
+    def get_equivalent_kernel_bias(self):
+        """conv.py:220-224: the 3x3 kernel and bias of the one convolution that equals both eval-mode branches"""
+        k3, b3 = self._fuse_bn_tensor(self.conv1)
+        k1, b1 = self._fuse_bn_tensor(self.conv2)
+        return k3 + torch.nn.functional.pad(k1, [1, 1, 1, 1]), b3 + b1
+
+    def fuse_convs(self):
+        """conv.py:268-291: replace conv1 / conv2 by `conv`, an nn.Conv2d(c, c, 3, 1, 1, bias=True) holding the equivalent kernel"""
+        if "conv" in self._modules:
+            return
+        kernel, bias = self.get_equivalent_kernel_bias()
+        c = self.conv1.conv
+        self.conv = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True).requires_grad_(False)
+        self.conv.weight.data = kernel
+        self.conv.bias.data = bias
+        for para in self.parameters():
+            para.detach_()
+        del self.conv1, self.conv2
+        self.__dict__.pop("bn", None)
+        self.__dict__.pop("_plist", None)
+        ops.bump_weights_epoch()
+
+
+class RepC3(DyModule):
+    """cv3(m(cv1(x)) + cv2(x)), m a chain of n RepConv (reference block.py:499-512), the RT-DETR neck block.  Only e == 1.0
+    works in the reference (its cv1 already has c2 channels while m expects int(c2 * e)), and then cv3 is nn.Identity.  The add is
+    free: cv2's BatchNorm pass takes m(cv1(x)) as its residual; backward: both input gradients meet in one buffer (cv1 adds
+    into cv2's)."""
+
+    def __init__(self, c1, c2, n=3, e=1.0):
+        super().__init__()
+        c_ = int(c2 * e)
+        if c_ != c2:
+            raise NotImplementedError(f"RepC3: e={e} gives a hidden width {c_} != c2={c2}; the reference's cv1 feeds c2 channels into "
+                                      f"RepConv({c_}, {c_}) and fails there, so only e == 1.0 exists")
+        if c2 % 8:
+            raise NotImplementedError("RepC3: a width that is not a multiple of 8 is outside the Dedark-YOLO hot path")
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.cv2 = Conv(c1, c2, 1, 1)
+        self.m = nn.Sequential(*[RepConv(c_, c_) for _ in range(n)])
+        self.cv3 = Conv(c_, c2, 1, 1) if c_ != c2 else nn.Identity()
+
+    def _fwd(self, tape, x, out=None):
+        t = self.cv1._fwd(tape, x)
+        for m in self.m:
+            t = m._fwd(tape, t)
+        return self.cv2._fwd(tape, x, out=out, residual=t)
+
+    def _bwd(self, tape, dy, needs=(True,)):
+        dx = self.cv2._bwd(tape, dy, needs=needs)          # the residual's gradient is dy itself
+        g = dy
+        for m in reversed(self.m):
+            g = m._bwd(tape, g)
+        if not needs[0]:
+            return self.cv1._bwd(tape, g, needs=needs)
+        return self.cv1._bwd(tape, g, dx_out=dx, accumulate=True)
 
 
 class _ParamRows:

@@ -19,7 +19,7 @@ from .. import ops
 from .modules import (AIFI, AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
                       DyModule, FasterC2f, FasterC2f_N,
                       GhostBottleneck, GhostConv, MFRU,
-                      PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
+                      PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, RepC3, RepConv, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
                       SC_PW_C2f, SPPF, Segment, Tape, TransformerEncoderLayer, Upsample,
                       lowlight_recovery)
 
@@ -34,7 +34,7 @@ _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Det
                  AsffDoubLevel=AsffDoubLevel, MFRU=MFRU, RFBblock=RFBblock, lowlight_recovery=lowlight_recovery,
                  FasterC2f_N=FasterC2f_N, FasterC2f=FasterC2f, PconvBottleneck_n=PconvBottleneck_n, PconvBottleneck=PconvBottleneck,
                  Segment=Segment, Pose=Pose, Classify=Classify,
-                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost, C3TR=C3TR,
+                 GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost, C3TR=C3TR, RepC3=RepC3,
                  AIFI=AIFI, TransformerEncoderLayer=TransformerEncoderLayer,
                  SCC2f=SCC2f, SC_PW_C2f=SC_PW_C2f, SC_Conv3_C2f=SC_Conv3_C2f, Conv3_SC_C2f=Conv3_SC_C2f, SCConvBottleneck=SCConvBottleneck,
                  SC_PW_Bottleneck=SC_PW_Bottleneck, SC_Conv3_Bottleneck=SC_Conv3_Bottleneck, Conv3_SC_Bottleneck=Conv3_SC_Bottleneck)
@@ -108,7 +108,7 @@ _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
     PconvBottleneck_n: _rule_conv_like, PconvBottleneck: _rule_conv_like,
-    GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f, C3TR: _rule_c2f,   # tasks.py:856-874
+    GhostConv: _rule_conv_like, GhostBottleneck: _rule_conv_like, DWConv: _rule_conv_like, C3: _rule_c2f, C3Ghost: _rule_c2f, C3TR: _rule_c2f, RepC3: _rule_c2f,   # tasks.py:856-874
     SCC2f: _rule_c2f, SC_PW_C2f: _rule_c2f, SC_Conv3_C2f: _rule_c2f, Conv3_SC_C2f: _rule_c2f,                         # tasks.py:744-752, 857-871
     SCConvBottleneck: _rule_conv_like, SC_PW_Bottleneck: _rule_conv_like, SC_Conv3_Bottleneck: _rule_conv_like, Conv3_SC_Bottleneck: _rule_conv_like,
     AIFI: _rule_aifi,
@@ -126,7 +126,7 @@ _RULES = {
 _PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2, C2f, C3, GhostConv, SPPF, Upsample, TransformerEncoderLayer)      # (TransformerEncoderLayer covers AIFI, C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, C3, RepC3, GhostConv, SPPF, Upsample, TransformerEncoderLayer)      # (TransformerEncoderLayer covers AIFI, C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):
@@ -505,6 +505,9 @@ class BaseModel(nn.Module):
         and the eval forward launches no fold kernel afterwards.  The parameters stay untouched (training can continue; the caches
         are invalidated by any weight or buffer update)."""
         n = 0
+        for m in list(self.modules()):                  # tasks.py:173-175: a RepConv is visited before its two Conv children,
+            if isinstance(m, RepConv):                  # so their BatchNorms still exist when it builds its one 3x3 convolution
+                m.fuse_convs()
         for conv, bn in self._bn_pairs():
             if bn.weight.is_cuda:
                 ops.bn_fold(bn, ops.round_up(conv.out_channels, ops.vec_elems(ops.get_compute_dtype())))
@@ -515,6 +518,8 @@ class BaseModel(nn.Module):
 
     def is_fused(self, thresh=10):
         pairs = list(self._bn_pairs())
+        if any(isinstance(m, RepConv) and "conv" not in m._modules for m in self.modules()):
+            return False
         return bool(pairs) and all(ops.bn_fold_is_current(bn) for _, bn in pairs)
 
     def load(self, weights, verbose=True):

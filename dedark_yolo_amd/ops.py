@@ -715,6 +715,22 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
     else:
         dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev) if ctx.act != ACT_NONE else dy
         _act_backward(tape, dy, ctx.y, ctx.bias, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
+    return _conv_grads(tape, ctx, dz, need_dx, dx_out, accumulate, add_src)
+
+
+def _conv_grads(tape, ctx, dz, need_dx=True, dx_out=None, accumulate=False, add_src=None):
+    """Weight gradient (side stream when the trainer enabled it) and data gradient of the convolution recorded in `ctx`, from
+    dz, the gradient wrt its raw output.  The tail of conv_backward; repconv_backward runs it once per branch."""
+    x = ctx.x
+    dtype = x.dtype
+    dev = x.device
+    B, Cin, H, W = x.shape
+    KH, KW = ctx.k
+    Cout, cout_pad, cin_pad = ctx.cout, ctx.cout_pad, ctx.cin_pad
+    Ho, Wo = dz.shape[2], dz.shape[3]
+    pixels = B * Ho * Wo
+    did = dt_id(dtype)
+    st = stream()
     # weight gradient
     if ctx.owner.requires_grad:
         gw, direct = _grad_sink(ctx.owner, ctx.weight.shape, dev, ctx.shared)
@@ -784,6 +800,119 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
     if dx_out is not None:
         return dx_out
     return dxb if cin_pad == Cin else dxb[:, :Cin]
+
+
+# ------------------------------------------------------------------------------------------------ RepConv
+def conv_bn_stats_forward(x, weight, bn, stride=1, pad=0, dil=1, owner=None):
+    """A training-mode convolution up to and including dy_bn_finalize_valid: the raw output z, its batch sums from the conv
+    kernel's f32 accumulators, the running-buffer update, num_batches_tracked and the saved mean / invstd, but NOT the normalise
+    pass.  Returns (z, aff, ctx): aff = [4, C] f32 rows scale, shift, mean, invstd; ctx = the ConvCtx _conv_grads takes (it is
+    not pushed on a tape)."""
+    dtype = x.dtype
+    B, Cin, H, W = x.shape
+    Cout, Cw, KH, KW = weight.shape
+    if Cw != Cin:
+        raise RuntimeError(f"conv: weight expects {Cw} input channels, got {Cin}")
+    ve = vec_elems(dtype)
+    cin_pad = padded_channels(x)
+    cout_pad = round_up(Cout, ve)
+    Ho = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
+    dev = x.device
+    wp = _pack(weight, cout_pad, cin_pad, False, dtype)
+    z = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
+    stats = arena.alloc(2 * cout_pad * _C.STATS_REPLICAS, dev)
+    d = _conv_desc(x, wp, z, B, H, W, cin_pad, Ho, Wo, cout_pad, KH, KW, stride, pad, dil, None, None, ACT_NONE, stats, False, dtype)
+    pixels = B * Ho * Wo
+    st = stream()
+    _C._prof is not None and _C.set_meta(kind="conv_fwd", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, stride, B, H, W, pixels),
+                                         bytes=float((B * H * W * Cin + pixels * Cout + Cout * KH * KW * Cin) * x.element_size()))
+    call("dy_conv2d_fwd", C.byref(d), st)
+    emu_round(z)
+    aff = _bn_train_begin(bn, cout_pad, dev)
+    pa, sa = aff.data_ptr(), 4 * cout_pad
+    call("dy_bn_finalize_valid", ptr(stats), pixels, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+         float(bn.momentum), float(bn.eps), pa, pa + sa, pa + 2 * sa, pa + 3 * sa, cout_pad, Cout, st)
+    ctx = ConvCtx()
+    ctx.x, ctx.weight, ctx.bias, ctx.bn, ctx.act = x, weight, None, bn, ACT_NONE
+    ctx.owner, ctx.shared = owner if owner is not None else weight, False
+    ctx.k, ctx.stride, ctx.pad, ctx.dil = (KH, KW), stride, pad, dil
+    ctx.cout, ctx.cout_pad, ctx.cin_pad, ctx.has_bn = Cout, cout_pad, cin_pad, True
+    ctx.z, ctx.aff, ctx.y = z, aff, None
+    return z, aff, ctx
+
+
+def bn2_act_bwd_workspace(pixels, C_, dtype):
+    """floats of workspace dy_bn2_act_bwd needs for this shape"""
+    return int(_C.lib().dy_bn2_act_bwd_workspace(pixels, C_, dt_id(dtype)))
+
+
+def repconv_forward(tape, x, conv1, conv2, act, training, out=None):
+    """y = act(bn1(conv1(x)) + bn2(conv2(x))) of RepConv (reference conv.py:215-218); conv1 / conv2: the two Conv modules (3x3 and
+    1x1, act=False).  Training: the two raw convolutions on the usual routes with their batch statistics, then ONE
+    dy_bn2_act_fwd.  Eval: the same kernel with the two eval folds.  A context is pushed on `tape` when it is not None."""
+    dtype = x.dtype
+    B, Cin, H, W = x.shape
+    Cout = conv1.conv.weight.shape[0]
+    if Cout % vec_elems(dtype) or Cin % vec_elems(dtype):
+        raise NotImplementedError(f"RepConv: {Cin} -> {Cout} channels are not whole 16-byte vectors in {dtype}")
+    uv = []
+    for m in (conv1, conv2):
+        c = m.conv
+        if training:
+            uv.append(conv_bn_stats_forward(x, c.weight, m.bn, c.stride[0], c.padding[0], c.dilation[0]))
+        else:
+            if tape is not None:
+                raise RuntimeError("repconv: gradients through an eval-mode BatchNorm are not supported")
+            z = conv_forward(None, x, c.weight, None, None, ACT_NONE, c.stride[0], c.padding[0], c.dilation[0])
+            uv.append((z, bn_fold(m.bn, Cout), None))
+    (u, au, cu), (v, av, cv) = uv
+    if u.shape != v.shape:
+        raise RuntimeError(f"repconv: the branches disagree in shape, {tuple(u.shape)} and {tuple(v.shape)}")
+    y = out if out is not None else empty_nhwc(B, Cout, u.shape[2], u.shape[3], dtype, x.device)
+    pixels = B * u.shape[2] * u.shape[3]
+    _C._prof is not None and _C.set_meta(kind="bn2_act_fwd", shape=f"{Cout}ch {pixels}px", dtype=str(dtype), flops=0.0,
+                                         bytes=float(3 * pixels * Cout * x.element_size()))
+    call("dy_bn2_act_fwd", ptr(u), ld_of(u), ptr(v), ld_of(v), ptr(au[0]), ptr(au[1]), ptr(av[0]), ptr(av[1]), act, ptr(y), ld_of(y),
+         pixels, Cout, dt_id(dtype), stream())
+    emu_round(y)
+    if tape is not None:
+        tape.push((cu, cv, act))
+    return y
+
+
+def repconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src=None):
+    """Backward of the matching repconv_forward (pops its context): dy_bn2_act_bwd (du, dv and the four BatchNorm parameter
+    gradients), the two weight gradients, and the two data gradients into ONE buffer: the 3x3 branch honours accumulate /
+    add_src / dx_out like conv_backward, the 1x1 branch adds into the same buffer.  Returns dx or None."""
+    cu, cv, act = tape.pop()
+    u, v = cu.z, cv.z
+    B, Cc, Ho, Wo = u.shape
+    dtype, dev = u.dtype, u.device
+    pixels = B * Ho * Wo
+    du, dv = empty_nhwc(B, Cc, Ho, Wo, dtype, dev), empty_nhwc(B, Cc, Ho, Wo, dtype, dev)
+    ws = torch.empty(bn2_act_bwd_workspace(pixels, Cc, dtype), dtype=torch.float32, device=dev)
+    sinks = []
+    for c in (cu, cv):                      # dgamma / dbeta go direct only when both can; otherwise through one [2, C] temporary
+        gb_ = _grad_dst(c.bn.bias)
+        gw_, direct = _grad_sink(c.bn.weight, (2, Cc), dev, gb_ is None)
+        if not direct:
+            gw_, gb_ = gw_[0], gw_[1]
+        sinks.append((gw_, gb_, direct))
+    pu, pv, s = cu.aff.data_ptr(), cv.aff.data_ptr(), 4 * Cc
+    _C._prof is not None and _C.set_meta(kind="bn2_act_bwd", shape=f"{Cc}ch {pixels}px", dtype=str(dtype), flops=0.0,
+                                         bytes=float(8 * pixels * Cc * u.element_size()))
+    call("dy_bn2_act_bwd", ptr(dy), ld_of(dy), ptr(u), ld_of(u), ptr(v), ld_of(v), pu, pu + s, pu + 2 * s, pu + 3 * s, ptr(cu.bn.weight),
+         pv, pv + s, pv + 2 * s, pv + 3 * s, ptr(cv.bn.weight), act, ptr(du), ld_of(du), ptr(dv), ld_of(dv), ptr(sinks[0][0]),
+         ptr(sinks[0][1]), ptr(sinks[1][0]), ptr(sinks[1][1]), ptr(ws), ws.numel(), pixels, Cc, dt_id(dtype), stream())
+    emu_round(du, dv)
+    for c, (gw_, gb_, direct) in zip((cu, cv), sinks):
+        if not direct:
+            _add_pgrad(tape, c.bn.weight, gw_)
+            _add_pgrad(tape, c.bn.bias, gb_)
+    dx = _conv_grads(tape, cu, du, need_dx, dx_out, accumulate, add_src)
+    _conv_grads(tape, cv, dv, need_dx, dx, True)
+    return dx
 
 
 # ------------------------------------------------------------------------------------------------ PConv

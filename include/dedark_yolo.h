@@ -146,6 +146,28 @@ int dy_bn_act_bwd_apply_valid(const void* dy, int64_t dy_ld, const void* z, int6
                               const double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C,
                               int C_valid, int dtype, void* stream);
 
+/* Two-branch BatchNorm + activation: y = act(u scale_u + shift_u + v scale_v + shift_v) over the raw outputs u, v of two
+ * convolutions (RepConv.forward, U/nn/modules/conv.py:215-218 `self.act(self.conv1(x) + self.conv2(x))` with conv1 / conv2 =
+ * Conv(act=False), conv.py:208-209: two nn.BatchNorm2d, the add and the SiLU).  scale / shift (/ mean / invstd) of each branch
+ * come from dy_bn_finalize_valid (training) or dy_bn_fold_eval_valid (eval).  Views are `pixels` x C slices (ld >= C) of the
+ * dtype; C is a whole number of 16-byte vectors and nothing outside the C columns is touched; the per-channel vectors are C floats. */
+int dy_bn2_act_fwd(const void* u, int64_t u_ld, const void* v, int64_t v_ld, const float* scale_u, const float* shift_u,
+                   const float* scale_v, const float* shift_v, int act, void* y, int64_t y_ld, int64_t pixels, int C, int dtype,
+                   void* stream);
+/* its backward (the autograd of conv.py:215-218 through both BatchNorms): z recomputed from u and v, g = dy act'(z),
+ * S0 = sum g, S1 = sum g u^, S2 = sum g v^ (u^ = (u - mean_u) invstd_u), du = gamma_u invstd_u (g - S0 / M - u^ S1 / M), dv
+ * likewise with S2, dgamma_u = S1, dgamma_v = S2, dbeta_u = dbeta_v = S0 (all four nullable), M = pixels >= 1.  The sums are
+ * per-workgroup f32 partials over pixel ranges fixed by (pixels, C, dtype), added by a second kernel in f64 in an order fixed by
+ * their count: no atomics, identical bytes on every run.  workspace: dy_bn2_act_bwd_workspace(pixels, C, dtype) floats, at most
+ * 3 C (DY_BN2_MAX_PARTS + 1), 16-byte aligned, not initialised by the caller. */
+#define DY_BN2_MAX_PARTS 1024
+int64_t dy_bn2_act_bwd_workspace(int64_t pixels, int C, int dtype);
+int dy_bn2_act_bwd(const void* dy, int64_t dy_ld, const void* u, int64_t u_ld, const void* v, int64_t v_ld, const float* scale_u,
+                   const float* shift_u, const float* mean_u, const float* invstd_u, const float* gamma_u, const float* scale_v,
+                   const float* shift_v, const float* mean_v, const float* invstd_v, const float* gamma_v, int act, void* du,
+                   int64_t du_ld, void* dv, int64_t dv_ld, float* dgamma_u, float* dbeta_u, float* dgamma_v, float* dbeta_v,
+                   float* workspace, int64_t workspace_elems, int64_t pixels, int C, int dtype, void* stream);
+
 /* ----------------------------------------------------------------------------- pooling / resampling / concat
  * SPPF's 3 chained MaxPool2d(5,1,2) (block.py:331-338), ASFF's MaxPool2d(2,2) and max_pool2d(3,2,1) (block.py:58,85-86),
  * nn.Upsample / F.interpolate nearest (yolov8.yaml head; block.py:91,97,99), torch.cat (conv.py:473), x + y. */
