@@ -569,37 +569,61 @@ class RepC3(DyModule):
         return self.cv1._bwd(tape, g, dx_out=dx, accumulate=True)
 
 
-class _ParamRows:
-    """Rows [r0, r1) of a parameter as the gradient owner (and bias) of one conv: nn.MultiheadAttention keeps its three in-projections
-    in ONE in_proj_weight [3C, C] / in_proj_bias [3C], each of which runs as a 1x1 conv of its own.  ops' gradient sinks see an object
-    with the parameter's flags and, under the trainer's direct gradient placement, the rows of its .grad: the weight / bias gradient
-    kernels write them in place.  Without direct placement the three results are filed under these objects on the tape and
-    TransformerLayer._bwd joins them into the parameter's gradient."""
-
-    def __init__(self, p, r0, r1):
-        self.p, self.r0, self.r1 = p, r0, r1
-        self.shape = torch.Size((r1 - r0, *p.shape[1:]))
-
-    requires_grad = property(lambda self: self.p.requires_grad)
-    _dy_direct = property(lambda self: getattr(self.p, "_dy_direct", False))
-    grad = property(lambda self: None if self.p.grad is None else self.p.grad[self.r0:self.r1])
-
-    def detach(self):
-        return self.p.detach()[self.r0:self.r1]
+_ParamRows = ops._ParamRows
 
 
-class TransformerLayer(DyModule):
-    """x = ma(q(x), k(x), v(x)) + x; x = fc2(fc1(x)) + x over the pixels of an NHWC map, which already is the token matrix
-    [B, L = H W, C] (reference ultralytics/nn/modules/transformer.py:100-117; no LayerNorm).  nn.Linear / nn.MultiheadAttention hold
-    the parameters under the reference's names; every Linear runs as a 1x1 conv (nine per layer: q / k / v, the three in-projections
-    with bias writing Q | K | V into the slices of one buffer, out_proj with bias, fc1, fc2), softmax(Q K^T / sqrt(D)) V is
-    ops.attn_forward.  Both residuals are added by the conv's own dy_copy2d(accumulate) pass; in backward the fan-outs of x and of
-    the attention output add through add_src / accumulate."""
+def _linear(tape, x, weight, bias=None, out=None, residual=None, rows=None):
+    """x W^T [+ bias] [+ residual] over the pixels of an NHWC map, which already is the token matrix [B, L = H W, C]: an nn.Linear
+    weight [out, in] run as a 1x1 conv through its persistent view (ops.weight_view).  rows = (r0, r1): only those rows of the
+    weight and of the bias, which then own their part of the gradients (ops._ParamRows)."""
+    if rows is None:
+        w, owner = ops.weight_view(weight, (*weight.shape, 1, 1)), weight
+    else:
+        w = ops.weight_view(weight, (rows[1] - rows[0], weight.shape[1], 1, 1), *rows)
+        owner, bias = _ParamRows(weight, *rows), _ParamRows(bias, *rows)
+    return conv_forward(tape, x, w, bias, None, ACT_NONE, 1, 0, 1, False, out=out, residual=residual, owner=owner)
+
+
+class _AttnCore(DyModule):
+    """What the two transformer layers share: nn.MultiheadAttention `self.ma` of `self._heads` heads over `self._c` channels, run
+    as three in-projections with bias (rows of ONE in_proj_weight / in_proj_bias) writing Q | K | V into the slices of one buffer,
+    ops.attn_forward and out_proj with bias."""
+
+    def _check_heads(self, c, heads):
+        if c % heads or (c // heads) % 8 or not 8 <= c // heads <= 128:
+            raise NotImplementedError(f"{type(self).__name__}: head dim {c}/{heads} is outside the attention kernels' rule D % 8 == 0, 8 <= D <= 128")
+
+    def _attn_fwd(self, tape, q, k, v, residual=None):
+        """out_proj(attention(in0(q), in1(k), in2(v))) [+ residual]"""
+        ma, C_ = self.ma, self._c
+        B, _, H, W = q.shape
+        qkv = empty_nhwc(B, 3 * C_, H, W, q.dtype, q.device)
+        for i, t in enumerate((q, k, v)):
+            _linear(tape, t, ma.in_proj_weight, ma.in_proj_bias, out=qkv[:, i * C_:(i + 1) * C_], rows=(i * C_, (i + 1) * C_))
+        a = ops.attn_forward(tape, qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], self._heads)
+        return _linear(tape, a, ma.out_proj.weight, ma.out_proj.bias, residual=residual)
+
+    def _attn_bwd(self, tape, dy):
+        """out_proj and the attention backwards; returns dQ | dK | dV, which the caller takes through the in-projections (last
+        first) before _join_in_proj"""
+        return ops.attn_backward(tape, conv_backward(tape, dy))
+
+    def _join_in_proj(self, tape):
+        """no direct placement: the three row blocks of each in-projection parameter -> the parameter's gradient"""
+        ops.join_param_rows(tape, self.ma.in_proj_weight)
+        ops.join_param_rows(tape, self.ma.in_proj_bias)
+
+
+class TransformerLayer(_AttnCore):
+    """x = ma(q(x), k(x), v(x)) + x; x = fc2(fc1(x)) + x over the pixels of an NHWC map (reference
+    ultralytics/nn/modules/transformer.py:100-117; no LayerNorm).  nn.Linear / nn.MultiheadAttention hold the parameters under the
+    reference's names; every Linear runs as a 1x1 conv (nine per layer: q / k / v, the attention core's four, fc1, fc2).  Both
+    residuals are added by the conv's own dy_copy2d(accumulate) pass; in backward the fan-outs of x and of the attention output add
+    through add_src / accumulate."""
 
     def __init__(self, c, num_heads):
         super().__init__()
-        if c % num_heads or (c // num_heads) % 8 or not 8 <= c // num_heads <= 128:
-            raise NotImplementedError(f"TransformerLayer: head dim {c}/{num_heads} is outside the attention kernels' rule D % 8 == 0, 8 <= D <= 128")
+        self._check_heads(c, num_heads)
         self.q = nn.Linear(c, c, bias=False)
         self.k = nn.Linear(c, c, bias=False)
         self.v = nn.Linear(c, c, bias=False)
@@ -608,61 +632,22 @@ class TransformerLayer(DyModule):
         self.fc2 = nn.Linear(c, c, bias=False)
         self._c, self._heads = c, num_heads
 
-    def _views(self):
-        """The weights as [c, c, 1, 1] conv weights (the view OBJECTS are kept: the packed-weight caches live on them) and the row
-        proxies of the in-projection; rebuilt when the parameters moved."""
-        key = tuple(p.data_ptr() for p in (self.q.weight, self.ma.in_proj_weight, self.ma.in_proj_bias, self.fc2.weight))
-        c = self.__dict__.get("_view_cache")
-        if c is None or c[0] != key:
-            C_ = self._c
-            v = {n: getattr(self, n).weight.detach().view(C_, C_, 1, 1) for n in ("q", "k", "v", "fc1", "fc2")}
-            v["out"] = self.ma.out_proj.weight.detach().view(C_, C_, 1, 1)
-            wi, bi = self.ma.in_proj_weight, self.ma.in_proj_bias
-            for i in range(3):
-                v[f"in{i}"] = wi.detach()[i * C_:(i + 1) * C_].view(C_, C_, 1, 1)
-                v[f"own{i}"] = _ParamRows(wi, i * C_, (i + 1) * C_)
-                v[f"bias{i}"] = _ParamRows(bi, i * C_, (i + 1) * C_)
-            for t in v.values():
-                if torch.is_tensor(t):
-                    ops.register_pack_view(t)
-            c = (key, v)
-            self.__dict__["_view_cache"] = c
-        return c[1]
-
     def _fwd(self, tape, x, out=None):
         if self.ma.dropout:
             raise NotImplementedError("TransformerLayer: attention dropout > 0 is not implemented")
-        v, C_ = self._views(), self._c
-        B, _, H, W = x.shape
-        lin = lambda t, w, owner, bias=None, out=None, residual=None: conv_forward(tape, t, w, bias, None, ACT_NONE, 1, 0, 1, False, out=out,
-                                                                                   residual=residual, owner=owner)
-        qkv = empty_nhwc(B, 3 * C_, H, W, x.dtype, x.device)
-        for i, n in enumerate(("q", "k", "v")):
-            t = lin(x, v[n], getattr(self, n).weight)
-            lin(t, v[f"in{i}"], v[f"own{i}"], bias=v[f"bias{i}"], out=qkv[:, i * C_:(i + 1) * C_])
-        a = ops.attn_forward(tape, qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], self._heads)
-        x1 = lin(a, v["out"], self.ma.out_proj.weight, bias=self.ma.out_proj.bias, residual=x)
-        t = lin(x1, v["fc1"], self.fc1.weight)
-        return lin(t, v["fc2"], self.fc2.weight, out=out, residual=x1)
+        x1 = self._attn_fwd(tape, *(_linear(tape, x, m.weight) for m in (self.q, self.k, self.v)), residual=x)
+        return _linear(tape, _linear(tape, x1, self.fc1.weight), self.fc2.weight, out=out, residual=x1)
 
     def _bwd(self, tape, dy, needs=(True,)):
         C_ = self._c
         dt = conv_backward(tape, dy)                                       # fc2
         dx1 = conv_backward(tape, dt, add_src=dy)                          # fc1; + the second residual
-        da = conv_backward(tape, dx1)                                      # out_proj
-        g = ops.attn_backward(tape, da)                                    # dQ | dK | dV
-        dx = None
-        for i in (2, 1, 0):
-            dt = conv_backward(tape, g[:, i * C_:(i + 1) * C_])            # in-projection i
-            if dx is None:
-                dx = conv_backward(tape, dt, add_src=dx1)                  # v; + the first residual
-            else:
-                conv_backward(tape, dt, dx_out=dx, accumulate=True)        # k, q: x feeds all three
-        v = self._views()
-        for own, p in ((("own0", "own1", "own2"), self.ma.in_proj_weight), (("bias0", "bias1", "bias2"), self.ma.in_proj_bias)):
-            parts = [tape.pgrads.pop(v[o], None) for o in own]
-            if parts[0] is not None:                                       # no direct placement: the three row blocks -> the parameter
-                ops._add_pgrad(tape, p, torch.cat([t.reshape(C_, -1) for t in parts]).reshape(p.shape))
+        g = self._attn_bwd(tape, dx1)
+        dqkv = [conv_backward(tape, g[:, i * C_:(i + 1) * C_]) for i in (2, 1, 0)]      # the in-projections of V, K, Q
+        dx = conv_backward(tape, dqkv[0], add_src=dx1)                     # v; + the first residual
+        for dt in dqkv[1:]:
+            conv_backward(tape, dt, dx_out=dx, accumulate=True)            # k, q: x feeds all three
+        self._join_in_proj(tape)
         return dx
 
 
@@ -689,21 +674,11 @@ class TransformerBlock(DyModule):
     def __getitem__(self, i):
         return (self,)[i]
 
-    def _linear_view(self):
-        w = self.linear.weight
-        c = self.__dict__.get("_lin_view_cache")
-        if c is None or c[0] != w.data_ptr():
-            c = (w.data_ptr(), w.detach().view(w.shape[0], w.shape[1], 1, 1))
-            self.__dict__["_lin_view_cache"] = c
-            ops.register_pack_view(c[1])
-        return c[1]
-
     def _fwd(self, tape, x, out=None):
         if self.conv is not None:
             x = self.conv._fwd(tape, x)
         n = len(self.tr)
-        x = conv_forward(tape, x, self._linear_view(), self.linear.bias, None, ACT_NONE, 1, 0, 1, False, out=out if n == 0 else None, residual=x,
-                         owner=self.linear.weight)
+        x = _linear(tape, x, self.linear.weight, self.linear.bias, out=out if n == 0 else None, residual=x)
         for i, m in enumerate(self.tr):
             x = m._fwd(tape, x, out=out if i == n - 1 else None)
         return x
@@ -728,28 +703,21 @@ class C3TR(C3):
         self.m = TransformerBlock(c_, c_, 4, n)
 
 
-class TransformerEncoderLayer(DyModule):
+class TransformerEncoderLayer(_AttnCore):
     """The post-norm encoder layer over the pixels of an NHWC map = the token matrix [B, L = H W, C] (reference
     ultralytics/nn/modules/transformer.py:20-67, forward_post):
         q = k = src + pos; src = norm1(src + ma(q, k, src)); src = norm2(src + fc2(gelu(fc1(src))))
     Real nn.MultiheadAttention / nn.Linear / nn.LayerNorm objects hold the parameters under the reference's names.  Six 1x1 convs
-    (the three in-projections with bias writing Q | K | V into the slices of one buffer, out_proj, fc1, fc2, all with bias),
-    ops.attn_forward, ops.add_pos, ops.gelu_forward and two ops.add_layernorm_forward: each residual add is fused into its
-    LayerNorm, the position table is a constant.  Called on a map this class adds no position term (the reference's pos=None)."""
+    with bias (the attention core's four, fc1, fc2), ops.add_pos, ops.gelu_forward and two ops.add_layernorm_forward: each
+    residual add is fused into its LayerNorm, the position table is a constant.  Called on a map this class adds no position term
+    (the reference's pos=None)."""
 
     def __init__(self, c1, cm=2048, num_heads=8, dropout=0.0, act=nn.GELU(), normalize_before=False):
         super().__init__()
-        who = type(self).__name__
-        if normalize_before:
-            raise NotImplementedError(f"{who}: normalize_before=True (forward_pre) is not implemented")
-        if dropout:
-            raise NotImplementedError(f"{who}: dropout > 0 is not implemented")
-        if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
-            raise NotImplementedError(f"{who}: only the exact nn.GELU() activation is implemented, got {act!r}")
-        if c1 % num_heads or (c1 // num_heads) % 8 or not 8 <= c1 // num_heads <= 128:
-            raise NotImplementedError(f"{who}: head dim {c1}/{num_heads} is outside the attention kernels' rule D % 8 == 0, 8 <= D <= 128")
+        self._check(normalize_before, dropout, act)
+        self._check_heads(c1, num_heads)
         if cm % 4 or not 4 <= c1 <= 2048:
-            raise NotImplementedError(f"{who}: c1 = {c1} must be at most 2048 (the LayerNorm kernels) and cm = {cm} a multiple of 4")
+            raise NotImplementedError(f"{type(self).__name__}: c1 = {c1} must be at most 2048 (the LayerNorm kernels) and cm = {cm} a multiple of 4")
         self.ma = nn.MultiheadAttention(c1, num_heads, dropout=dropout, batch_first=True)
         self.fc1 = nn.Linear(c1, cm)
         self.fc2 = nn.Linear(cm, c1)
@@ -760,40 +728,20 @@ class TransformerEncoderLayer(DyModule):
         self.dropout2 = nn.Dropout(dropout)
         self.act = act
         self.normalize_before = normalize_before
-        self._c, self._cm, self._heads = c1, cm, num_heads
-
-    def _views(self):
-        """The Linear weights as [out, in, 1, 1] conv weights (the view OBJECTS are kept: the packed-weight caches live on them) and
-        the row proxies of the in-projection; rebuilt when the parameters moved."""
-        key = tuple(p.data_ptr() for p in (self.ma.in_proj_weight, self.ma.in_proj_bias, self.ma.out_proj.weight, self.fc1.weight, self.fc2.weight))
-        c = self.__dict__.get("_view_cache")
-        if c is None or c[0] != key:
-            C_ = self._c
-            v = {"out": self.ma.out_proj.weight.detach().view(C_, C_, 1, 1), "fc1": self.fc1.weight.detach().view(self._cm, C_, 1, 1),
-                 "fc2": self.fc2.weight.detach().view(C_, self._cm, 1, 1)}
-            wi, bi = self.ma.in_proj_weight, self.ma.in_proj_bias
-            for i in range(3):
-                v[f"in{i}"] = wi.detach()[i * C_:(i + 1) * C_].view(C_, C_, 1, 1)
-                v[f"own{i}"] = _ParamRows(wi, i * C_, (i + 1) * C_)
-                v[f"bias{i}"] = _ParamRows(bi, i * C_, (i + 1) * C_)
-            for t in v.values():
-                if torch.is_tensor(t):
-                    ops.register_pack_view(t)
-            c = (key, v)
-            self.__dict__["_view_cache"] = c
-        return c[1]
+        self._c, self._heads = c1, num_heads
 
     def _pos(self, x):
         return None
 
-    def _check(self):
+    def _check(self, normalize_before, dropout, act):
+        """what has no kernel: the constructor's arguments, and again what the attributes hold when the layer runs"""
         who = type(self).__name__
-        if self.normalize_before:
+        if normalize_before:
             raise NotImplementedError(f"{who}: normalize_before=True (forward_pre) is not implemented")
-        if self.ma.dropout or self.dropout.p or self.dropout1.p or self.dropout2.p:
+        if dropout:
             raise NotImplementedError(f"{who}: dropout > 0 is not implemented")
-        if not isinstance(self.act, nn.GELU) or getattr(self.act, "approximate", "none") != "none":
-            raise NotImplementedError(f"{who}: only the exact nn.GELU() activation is implemented, got {self.act!r}")
+        if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
+            raise NotImplementedError(f"{who}: only the exact nn.GELU() activation is implemented, got {act!r}")
 
     def forward(self, x, src_mask=None, src_key_padding_mask=None, pos=None, out=None):
         if src_mask is not None or src_key_padding_mask is not None:
@@ -803,21 +751,14 @@ class TransformerEncoderLayer(DyModule):
         return super().forward(x, out=out)
 
     def _fwd(self, tape, x, out=None):
-        self._check()
-        v, C_ = self._views(), self._c
-        B, _, H, W = x.shape
-        lin = lambda t, w, owner, bias, out=None: conv_forward(tape, t, w, bias, None, ACT_NONE, 1, 0, 1, False, out=out, owner=owner)
+        self._check(self.normalize_before, self.ma.dropout or self.dropout.p or self.dropout1.p or self.dropout2.p, self.act)
         pos = self._pos(x)
         p = x if pos is None else ops.add_pos(x, pos)
-        qkv = empty_nhwc(B, 3 * C_, H, W, x.dtype, x.device)
-        for i in range(3):
-            lin(p if i < 2 else x, v[f"in{i}"], v[f"own{i}"], v[f"bias{i}"], out=qkv[:, i * C_:(i + 1) * C_])
-        a = ops.attn_forward(tape, qkv[:, :C_], qkv[:, C_:2 * C_], qkv[:, 2 * C_:], self._heads)
-        s2 = lin(a, v["out"], self.ma.out_proj.weight, self.ma.out_proj.bias)
+        s2 = self._attn_fwd(tape, p, p, x)
         x1 = ops.add_layernorm_forward(tape, x, s2, self.norm1)
-        u = lin(x1, v["fc1"], self.fc1.weight, self.fc1.bias)
+        u = _linear(tape, x1, self.fc1.weight, self.fc1.bias)
         t = ops.gelu_forward(tape, u)
-        s3 = lin(t, v["fc2"], self.fc2.weight, self.fc2.bias)
+        s3 = _linear(tape, t, self.fc2.weight, self.fc2.bias)
         return ops.add_layernorm_forward(tape, x1, s3, self.norm2, out=out)
 
     def _bwd(self, tape, dy, needs=(True,)):
@@ -827,16 +768,11 @@ class TransformerEncoderLayer(DyModule):
         du = ops.gelu_backward(tape, dt)
         dx1 = conv_backward(tape, du, add_src=dz2)                         # fc1; + the second residual
         dz1 = ops.add_layernorm_backward(tape, dx1)                        # norm1: the gradient of src (residual) and of out_proj's output
-        da = conv_backward(tape, dz1)                                      # out_proj
-        g = ops.attn_backward(tape, da)                                    # dQ | dK | dV
+        g = self._attn_bwd(tape, dz1)
         dx = conv_backward(tape, g[:, 2 * C_:], add_src=dz1)               # V's in-projection reads src; + the first residual
         for i in (1, 0):                                                   # K, Q read src + pos: the table gets no gradient
             conv_backward(tape, g[:, i * C_:(i + 1) * C_], dx_out=dx, accumulate=True)
-        v = self._views()
-        for own, p in ((("own0", "own1", "own2"), self.ma.in_proj_weight), (("bias0", "bias1", "bias2"), self.ma.in_proj_bias)):
-            parts = [tape.pgrads.pop(v[o], None) for o in own]
-            if parts[0] is not None:                                       # no direct placement: the three row blocks -> the parameter
-                ops._add_pgrad(tape, p, torch.cat([t.reshape(C_, -1) for t in parts]).reshape(p.shape))
+        self._join_in_proj(tape)
         return dx
 
 
@@ -987,6 +923,38 @@ class SPPF(DyModule):
         return self.cv1._bwd(tape, dY[:, :c_], needs=needs)
 
 
+def _asff_blend_fwd(tape, rs, levels, weight_levels, level_conv, logits_conv):
+    """The blend stage of the ASFF blocks: levels[k] (through level_conv(tape, m, x, out=)) compresses source rs[k] into its slice
+    of one weight-vector buffer, weight_levels (through logits_conv(tape, m, x)) turns that into one logit per source and pixel,
+    and ops.asff_fuse_forward blends the sources under their soft-max.  Returns the fused map."""
+    n, c = len(rs), weight_levels.in_channels // len(rs)
+    B, _, H, W = rs[0].shape
+    wv = empty_nhwc(B, n * c, H, W, rs[0].dtype, rs[0].device)
+    for k in range(n):
+        level_conv(tape, levels[k], rs[k], out=wv[:, k * c:(k + 1) * c])
+    logits = logits_conv(tape, weight_levels, wv)                             # [B,n,H,W] view of a channel-padded buffer
+    fused = ops.asff_fuse_forward(rs, logits)
+    if tape is not None:
+        tape.push((rs, logits))
+    return fused
+
+
+def _asff_blend_bwd(tape, dfused, into=None):
+    """Mirror of _asff_blend_fwd: the gradients of the sources, each the blend's part plus its level conv's.  into[k]: a gradient
+    another consumer of source k already left, which both add into."""
+    rs, logits = tape.pop()
+    dr, dlog = ops.asff_fuse_backward(dfused, rs, logits, into)
+    dwv = conv_backward(tape, dlog)                                           # weight_levels -> the weight-vector buffer
+    c = dwv.shape[1] // len(rs)
+    for k in reversed(range(len(rs))):
+        conv_backward(tape, dwv[:, k * c:(k + 1) * c], dx_out=dr[k], accumulate=True)
+    return dr
+
+
+def _add_conv_fwd(training):
+    return lambda tape, m, x, out=None: m._fwd(tape, x, training, out=out)
+
+
 class AsffTribeLevel(DyModule):
     """3-level adaptive spatial feature fusion (reference block.py:48-115). Inputs (P5, P4, P3)."""
 
@@ -1028,18 +996,10 @@ class AsffTribeLevel(DyModule):
             r0 = ops.upsample_fwd(self.compress_level_0._fwd(tape, x0, tr), 4)
             r1 = ops.upsample_fwd(self.compress_level_1._fwd(tape, x1, tr), 2)
             r2 = x2
-        B, Cc, H, W = r0.shape
-        wv = empty_nhwc(B, 24, H, W, r0.dtype, r0.device)
-        self.weight_level_0._fwd(tape, r0, tr, out=wv[:, 0:8])
-        self.weight_level_1._fwd(tape, r1, tr, out=wv[:, 8:16])
-        self.weight_level_2._fwd(tape, r2, tr, out=wv[:, 16:24])
-        logits = plain_conv_fwd(tape, self.weight_levels, wv)                 # [B,3,H,W] view of an 8/4-channel padded buffer
-        fused = empty_nhwc(B, Cc, H, W, r0.dtype, r0.device)
-        call("dy_asff_fuse_fwd", ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), ptr(r2), ld_of(r2), ptr(logits), ld_of(logits),
-             ptr(fused), ld_of(fused), B * H * W, Cc, ops.dt_id(r0.dtype), stream())
-        ops.emu_round(fused)
+        fused = _asff_blend_fwd(tape, (r0, r1, r2), (self.weight_level_0, self.weight_level_1, self.weight_level_2), self.weight_levels,
+                                _add_conv_fwd(tr), plain_conv_fwd)
         if tape is not None:
-            saved.update(r0=r0, r1=r1, r2=r2, logits=logits, shapes=(x0.shape, x1.shape, x2.shape))
+            saved.update(shapes=(x0.shape, x1.shape, x2.shape))
             tape.push(saved)
         return self.expand._fwd(tape, fused, tr)
 
@@ -1048,24 +1008,9 @@ class AsffTribeLevel(DyModule):
     def _bwd(self, tape, dy, needs=(True, True, True), into=None):
         dfused = conv_backward(tape, dy)
         s = tape.pop()
-        r0, r1, r2, logits = s["r0"], s["r1"], s["r2"], s["logits"]
-        B, Cc, H, W = r0.shape
-        dt, dev = r0.dtype, r0.device
         into = list(into) if into is not None else [None, None, None]
         # the input this level takes as it is (r_k = x_k): the blend's gradient adds straight into what another consumer left
-        same = self.level
-        acc = [1 if (k == same and into[k] is not None) else 0 for k in range(3)]
-        dr = [into[k] if acc[k] else empty_nhwc(B, Cc, H, W, dt, dev) for k in range(3)]
-        lw = ld_of(logits)
-        dlog = empty_nhwc(B, lw, H, W, dt, dev)
-        call("dy_asff_fuse_bwd", ptr(dfused), ld_of(dfused), ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), ptr(r2), ld_of(r2),
-             ptr(logits), lw, ptr(dr[0]), ld_of(dr[0]), ptr(dr[1]), ld_of(dr[1]), ptr(dr[2]), ld_of(dr[2]), ptr(dlog), lw,
-             B * H * W, Cc, acc[0], acc[1], acc[2], ops.dt_id(dt), stream())
-        ops.emu_round(dr[0], dr[1], dr[2], dlog)
-        dwv = conv_backward(tape, dlog[:, :3])                                # weight_levels -> [B,24,H,W]
-        conv_backward(tape, dwv[:, 16:24], dx_out=dr[2], accumulate=True)     # weight_level_2
-        conv_backward(tape, dwv[:, 8:16], dx_out=dr[1], accumulate=True)
-        conv_backward(tape, dwv[:, 0:8], dx_out=dr[0], accumulate=True)
+        dr = _asff_blend_bwd(tape, dfused, [t if k == self.level else None for k, t in enumerate(into)])
         (s0, s1, s2) = s["shapes"]
         A = [dict(dx_out=t, accumulate=True) if t is not None else {} for t in into]      # add into an existing gradient
         if self.level == 0:
@@ -1390,37 +1335,14 @@ class MFRU(DyModule):
         r0 = ops.upsample_fwd(self._pw(tape, self.pwconv, self.scconv512._fwd(tape, x0)), 4)
         r1 = ops.upsample_fwd(self._pw(tape, self.pwconv, self.scconv512._fwd(tape, x1)), 2)
         r2 = self.scconv256._fwd(tape, x2)
-        B, Cc, H, W = r2.shape
         if tuple(r0.shape) != tuple(r2.shape) or tuple(r1.shape) != tuple(r2.shape):
             raise RuntimeError("MFRU: inputs must be at strides 4 : 2 : 1")
-        wv = empty_nhwc(B, 48, H, W, r2.dtype, r2.device)
-        self._pw(tape, self.weight_level_0, r0, out=wv[:, 0:16])
-        self._pw(tape, self.weight_level_1, r1, out=wv[:, 16:32])
-        self._pw(tape, self.weight_level_2, r2, out=wv[:, 32:48])
-        logits = self._pw(tape, self.weight_levels, wv)
-        fused = empty_nhwc(B, Cc, H, W, r2.dtype, r2.device)
-        call("dy_asff_fuse_fwd", ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), ptr(r2), ld_of(r2), ptr(logits), ld_of(logits),
-             ptr(fused), ld_of(fused), B * H * W, Cc, ops.dt_id(r2.dtype), stream())
-        if tape is not None:
-            tape.push(dict(r0=r0, r1=r1, r2=r2, logits=logits))
+        fused = _asff_blend_fwd(tape, (r0, r1, r2), (self.weight_level_0, self.weight_level_1, self.weight_level_2), self.weight_levels,
+                                self._pw, self._pw)
         return self.scconv256._fwd(tape, fused)
 
     def _bwd(self, tape, dy, needs=(True, True, True)):
-        dfused = self.scconv256._bwd(tape, dy)
-        s = tape.pop()
-        r0, r1, r2, logits = s["r0"], s["r1"], s["r2"], s["logits"]
-        B, Cc, H, W = r2.shape
-        dt, dev = r2.dtype, r2.device
-        dr = [empty_nhwc(B, Cc, H, W, dt, dev) for _ in range(3)]
-        lw = ld_of(logits)
-        dlog = empty_nhwc(B, lw, H, W, dt, dev)
-        call("dy_asff_fuse_bwd", ptr(dfused), ld_of(dfused), ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), ptr(r2), ld_of(r2),
-             ptr(logits), lw, ptr(dr[0]), ld_of(dr[0]), ptr(dr[1]), ld_of(dr[1]), ptr(dr[2]), ld_of(dr[2]), ptr(dlog), lw,
-             B * H * W, Cc, 0, 0, 0, ops.dt_id(dt), stream())
-        dwv = conv_backward(tape, dlog[:, :3])                                # weight_levels -> [B,48,H,W]
-        conv_backward(tape, dwv[:, 32:48], dx_out=dr[2], accumulate=True)
-        conv_backward(tape, dwv[:, 16:32], dx_out=dr[1], accumulate=True)
-        conv_backward(tape, dwv[:, 0:16], dx_out=dr[0], accumulate=True)
+        dr = _asff_blend_bwd(tape, self.scconv256._bwd(tape, dy))
         dx2 = self.scconv256._bwd(tape, dr[2])
         dx1 = self.scconv512._bwd(tape, conv_backward(tape, ops.upsample_bwd(dr[1], 2)))
         dx0 = self.scconv512._bwd(tape, conv_backward(tape, ops.upsample_bwd(dr[0], 4)))
@@ -1456,34 +1378,11 @@ class AsffDoubLevel(DyModule):
         else:
             r0 = ops.upsample_fwd(self.compress_level_0._fwd(tape, x0, tr), 2)
             r1 = x1
-        B, Cc, H, W = r0.shape
-        wv = empty_nhwc(B, 32, H, W, r0.dtype, r0.device)
-        self.weight_level_0._fwd(tape, r0, tr, out=wv[:, 0:16])
-        self.weight_level_1._fwd(tape, r1, tr, out=wv[:, 16:32])
-        logits = plain_conv_fwd(tape, self.weight_levels, wv)                 # [B,2,H,W] view of a channel-padded buffer
-        fused = empty_nhwc(B, Cc, H, W, r0.dtype, r0.device)
-        call("dy_asff_fuse_fwd", ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), None, 0, ptr(logits), ld_of(logits),
-             ptr(fused), ld_of(fused), B * H * W, Cc, ops.dt_id(r0.dtype), stream())
-        ops.emu_round(fused)
-        if tape is not None:
-            tape.push(dict(r0=r0, r1=r1, logits=logits))
+        fused = _asff_blend_fwd(tape, (r0, r1), (self.weight_level_0, self.weight_level_1), self.weight_levels, _add_conv_fwd(tr), plain_conv_fwd)
         return self.expand._fwd(tape, fused, tr)
 
     def _bwd(self, tape, dy, needs=(True, True)):
-        dfused = conv_backward(tape, dy)
-        s = tape.pop()
-        r0, r1, logits = s["r0"], s["r1"], s["logits"]
-        B, Cc, H, W = r0.shape
-        dt, dev = r0.dtype, r0.device
-        dr = [empty_nhwc(B, Cc, H, W, dt, dev) for _ in range(2)]
-        lw = ld_of(logits)
-        dlog = empty_nhwc(B, lw, H, W, dt, dev)
-        call("dy_asff_fuse_bwd", ptr(dfused), ld_of(dfused), ptr(r0), ld_of(r0), ptr(r1), ld_of(r1), None, 0,
-             ptr(logits), lw, ptr(dr[0]), ld_of(dr[0]), ptr(dr[1]), ld_of(dr[1]), None, 0, ptr(dlog), lw,
-             B * H * W, Cc, 0, 0, 0, ops.dt_id(dt), stream())
-        dwv = conv_backward(tape, dlog[:, :2])                                # weight_levels -> [B,32,H,W]
-        conv_backward(tape, dwv[:, 16:32], dx_out=dr[1], accumulate=True)     # weight_level_1
-        conv_backward(tape, dwv[:, 0:16], dx_out=dr[0], accumulate=True)
+        dr = _asff_blend_bwd(tape, conv_backward(tape, dy))
         if self.level == 0:
             dx1 = conv_backward(tape, dr[1])                                  # stride_level_1
             dx0 = dr[0]
@@ -1916,16 +1815,6 @@ class Classify(DyModule):
         self.drop = nn.Dropout(p=0.0, inplace=True)
         self.linear = nn.Linear(c_, c2)
 
-    def _linear_view(self):
-        """linear.weight as a [c2, 1280, 1, 1] conv weight; the view OBJECT is kept, the packed-weight cache lives on it."""
-        w = self.linear.weight
-        c = self.__dict__.get("_lin_view_cache")
-        if c is None or c[0] != w.data_ptr():
-            c = (w.data_ptr(), w.detach().view(w.shape[0], w.shape[1], 1, 1))
-            self.__dict__["_lin_view_cache"] = c
-            ops.register_pack_view(c[1])
-        return c[1]
-
     def _fwd(self, tape, x, *more):
         if more:
             raise NotImplementedError("Classify: a list of input layers (torch.cat in the reference) is outside the hot path")
@@ -1935,7 +1824,7 @@ class Classify(DyModule):
         pooled = ops.gap_fwd(y)
         if tape is not None:
             tape.push((y.shape[2], y.shape[3]))
-        z = conv_forward(tape, pooled, self._linear_view(), self.linear.bias, None, ACT_NONE, 1, 0, 1, False, owner=self.linear.weight)
+        z = _linear(tape, pooled, self.linear.weight, self.linear.bias)
         return z if self.training else ops.cls_softmax(z)
 
     def _wrap(self, out):
@@ -2022,9 +1911,9 @@ class lowlight_recovery(DyModule):
             t = plain_conv_fwd(tape, blk.conv_block[0], t, act=ACT_LEAKY)
         if xd != f32:
             t = as_nhwc(t, f32)                          # [B,32,8,8]: 64 K values
-        w1, w2 = self._fc_views()
+        w1 = ops.weight_view(ex.fc1.weight, (64, 32, 8, 8))             # fc1 as a conv whose window is the whole [32, 8, 8] input
         t = conv_forward(tape, t, w1, ex.fc1.bias, None, ACT_LEAKY, 1, 0, 1, False, owner=ex.fc1.weight)
-        feat = conv_forward(tape, t, w2, ex.fc2.bias, None, ACT_NONE, 1, 0, 1, False, owner=ex.fc2.weight)    # [B,15,1,1], ld 16
+        feat = _linear(tape, t, ex.fc2.weight, ex.fc2.bias)              # [B,15,1,1], ld 16
         params = torch.empty((B, 8), dtype=f32, device=dev)
         call("dy_filter_params_fwd", ptr(feat), ld_of(feat), ptr(params), B, st)
         s4 = torch.empty((B, 3, H, W), dtype=f32, device=dev)
@@ -2037,19 +1926,6 @@ class lowlight_recovery(DyModule):
         if tape is not None:
             tape.push(dict(x=x, feat=feat, params=params, hp=hp, A=A, I=I))
         return out8[:, :3]
-
-    def _fc_views(self):
-        """The fully connected weights as conv weights ([64,32,8,8] window = whole input, [15,64,1,1]).  The view OBJECTS are kept:
-        the packed-weight cache lives on the tensor object, and a fresh view per step meant four re-pack launches per step."""
-        ex = self.extractor
-        key = (ex.fc1.weight.data_ptr(), ex.fc2.weight.data_ptr())
-        c = self.__dict__.get("_fc_view_cache")
-        if c is None or c[0] != key:
-            c = (key, ex.fc1.weight.detach().view(64, 32, 8, 8), ex.fc2.weight.detach().view(15, 64, 1, 1))
-            self.__dict__["_fc_view_cache"] = c
-            ops.register_pack_view(c[1])
-            ops.register_pack_view(c[2])
-        return c[1], c[2]
 
     def _bwd(self, tape, dout, needs=(False,)):
         s = tape.pop()

@@ -272,6 +272,22 @@ def register_pack_view(t):
     _extra_pack_views.append(weakref.ref(t))
 
 
+def weight_view(p, shape, r0=None, r1=None):
+    """Parameter `p` (rows [r0, r1) of it when given) as a conv weight of the 4-D `shape`: how an nn.Linear weight reaches the conv
+    kernels.  The view OBJECT is kept on the parameter, next to _dy_pack, and comes back on every call: the packed-weight cache
+    lives on it, and a fresh view per step meant a re-pack launch per use and step.  It is rebuilt, and announced to PackPlan once,
+    when the parameter's storage moved (model.to(), the trainer's flat state)."""
+    cache = p.__dict__.setdefault("_dy_views", {})
+    key = (tuple(shape), r0, r1)
+    hit = cache.get(key)
+    at = p.data_ptr()
+    if hit is None or hit[0] != at:
+        w = p.detach()
+        hit = cache[key] = (at, (w if r0 is None else w[r0:r1]).view(shape))
+        register_pack_view(hit[1])
+    return hit[1]
+
+
 class PackPlan:
     """Re-packs every cached packed weight of a model with one launch (dy_pack_weights_multi) right after the optimizer
     step wrote the f32 masters; the per-conv lazy path of _pack() then only ever hits its cache."""
@@ -638,6 +654,33 @@ def _grad_sink(p, shape, dev, shared=False):
     if gd is not None:
         return gd, True
     return torch.empty(shape, dtype=torch.float32, device=dev), False
+
+
+class _ParamRows:
+    """Rows [r0, r1) of a parameter as the gradient owner (and bias) of one conv: nn.MultiheadAttention keeps its three in-projections
+    in ONE in_proj_weight [3C, C] / in_proj_bias [3C], each of which runs as a 1x1 conv of its own.  The gradient sinks see an object
+    with the parameter's flags and, under the trainer's direct gradient placement, the rows of its .grad: the weight / bias gradient
+    kernels write them in place.  Without direct placement the results are filed under these objects on the tape and
+    join_param_rows puts them together."""
+
+    def __init__(self, p, r0, r1):
+        self.p, self.r0, self.r1 = p, r0, r1
+        self.shape = torch.Size((r1 - r0, *p.shape[1:]))
+
+    requires_grad = property(lambda self: self.p.requires_grad)
+    _dy_direct = property(lambda self: getattr(self.p, "_dy_direct", False))
+    grad = property(lambda self: None if self.p.grad is None else self.p.grad[self.r0:self.r1])
+
+    def detach(self):
+        return self.p.detach()[self.r0:self.r1]
+
+
+def join_param_rows(tape, p):
+    """The row blocks filed on the tape under _ParamRows of `p` leave it and become p's gradient, concatenated in row order (they
+    cover p).  Under direct placement nothing was filed and nothing happens."""
+    rows = sorted((k for k in tape.pgrads if isinstance(k, _ParamRows) and k.p is p), key=lambda k: k.r0)
+    if rows:
+        _add_pgrad(tape, p, torch.cat([tape.pgrads.pop(k).reshape(k.shape[0], -1) for k in rows]).reshape(p.shape))
 
 
 def _bn_backward(tape, dy, z, aff, bn, act, dz, pixels, C, C_valid, did, st, dev, shared):
@@ -1433,6 +1476,49 @@ def upsample_bwd(dy, scale, dx_out=None, accumulate=False):
          1 if (accumulate and dx_out is not None) else 0, dt_id(dy.dtype), stream())
     emu_round(dx)
     return dx
+
+
+def _asff_dims(who, sources, logits, *like):
+    n = len(sources)
+    B, Cc, H, W = sources[0].shape
+    if n not in (2, 3) or any(tuple(t.shape) != (B, Cc, H, W) or t.dtype != logits.dtype for t in (*sources, *like) if t is not None):
+        raise RuntimeError(f"{who}: two or three sources, all NHWC views of one shape and of the logits' dtype")
+    if tuple(logits.shape) != (B, n, H, W):
+        raise RuntimeError(f"{who}: {n} sources need logits [B, {n}, H, W], got {tuple(logits.shape)}")
+    return n, B, Cc, H, W
+
+
+def _ptr_ld(t):
+    return (None, 0) if t is None else (t.data_ptr(), ld_of(t))
+
+
+def asff_fuse_forward(sources, logits, out=None):
+    """sum_k softmax_k(logits) * sources[k] per pixel (dy_asff_fuse_fwd): the ASFF blend of 2 or 3 same-shape NHWC maps under the
+    per-pixel logits [B, n, H, W].  Returns the fused map (`out` when given)."""
+    n, B, Cc, H, W = _asff_dims("asff_fuse_forward", sources, logits, out)
+    o = out if out is not None else empty_nhwc(B, Cc, H, W, logits.dtype, logits.device)
+    r = (*sources, None)[:3]
+    call("dy_asff_fuse_fwd", *_ptr_ld(r[0]), *_ptr_ld(r[1]), *_ptr_ld(r[2]), *_ptr_ld(logits), *_ptr_ld(o), B * H * W, Cc, dt_id(o.dtype),
+         stream())
+    emu_round(o)
+    return o
+
+
+def asff_fuse_backward(dfused, sources, logits, into=None):
+    """Backward of asff_fuse_forward (dy_asff_fuse_bwd).  Returns ([gradient of each source], gradient of the logits [B, n, H, W], a
+    view of a buffer as wide as the logits' own).  into[k]: a gradient another consumer of source k already left; the blend's adds
+    into it (the kernel's acc flag) and it is what comes back for k."""
+    n, B, Cc, H, W = _asff_dims("asff_fuse_backward", sources, logits, dfused, *(into or ()))
+    dt, dev = logits.dtype, logits.device
+    into = (*(into or (None,) * n), None)[:3]
+    r = (*sources, None)[:3]
+    d = [t if t is not None else empty_nhwc(B, Cc, H, W, dt, dev) for t in into[:n]] + [None] * (3 - n)
+    lw = ld_of(logits)
+    dlog = empty_nhwc(B, lw, H, W, dt, dev)
+    call("dy_asff_fuse_bwd", *_ptr_ld(dfused), *_ptr_ld(r[0]), *_ptr_ld(r[1]), *_ptr_ld(r[2]), ptr(logits), lw, *_ptr_ld(d[0]), *_ptr_ld(d[1]),
+         *_ptr_ld(d[2]), ptr(dlog), lw, B * H * W, Cc, *(int(t is not None) for t in into), dt_id(dt), stream())
+    emu_round(*d, dlog)
+    return d[:n], dlog[:, :n]
 
 
 DET_MAX_LEVELS = 4          # DY_DET_MAX_LEVELS

@@ -5,7 +5,8 @@ the trainer's direct placement (`p.grad` pre-allocated as f32, `p._dy_direct = T
 the same deterministic kernels and differ in the destination pointer only, so each case runs forward + backward twice from
 identical inputs, once per way, and asserts torch.equal on dx and on every parameter gradient, and that the direct run left
 nothing in `tape.pgrads`.  A `shared` conv (a weight used more than once per step) must deliver through `tape.pgrads` in both
-runs, and its two uses must add up.  The weight-gradient side stream is off, so both runs are on one stream."""
+runs, and its two uses must add up.  The attention in-projections own row blocks of one parameter (ops._ParamRows): the same two
+ways, through the two transformer layers.  The weight-gradient side stream is off, so both runs are on one stream."""
 import pytest
 import torch
 import torch.nn as nn
@@ -209,3 +210,35 @@ def test_conv_transpose2x2(dtype):
             return ops.conv_transpose2x2_backward(tape, dy)
         return dict(w=w, b=b), step
     _check_both_ways(build)
+
+
+@DTYPES
+@pytest.mark.parametrize("block", ["TransformerLayer", "TransformerEncoderLayer"])
+def test_attention_in_projection_rows(dtype, block):
+    """The three in-projections of nn.MultiheadAttention own ROWS of one in_proj_weight / in_proj_bias (ops._ParamRows): direct
+    placement writes the rows of p.grad in place, the tape path files three blocks and joins them.  Head dim 8 (the kernels'
+    minimum), a 3x5 map: every parameter of the block, the in-projection pair included, the same bytes both ways, and no row proxy
+    left on either tape."""
+    from dedark_yolo_amd import ops
+    from dedark_yolo_amd.nn import modules
+    ops.set_compute_dtype(dtype)
+    tapes = []
+
+    def build():
+        torch.manual_seed(16)
+        m = (modules.TransformerLayer(32, 4) if block == "TransformerLayer" else modules.TransformerEncoderLayer(32, 64, 4)).cuda().train()
+        g = torch.Generator().manual_seed(16)
+        x, dy = ops.as_nhwc(_randn(g, 2, 32, 3, 5), dtype), ops.as_nhwc(_randn(g, 2, 32, 3, 5), dtype)
+
+        def step(tape):
+            tapes.append(tape)
+            m._fwd(tape, x)
+            return m._bwd(tape, dy)
+        return dict(m.named_parameters()), step
+    g = _check_both_ways(build)
+    assert g["ma.in_proj_weight"].shape == (96, 32) and g["ma.in_proj_bias"].shape == (96,)
+    for i in range(3):                                        # each of the three row blocks received a gradient of its own
+        assert bool(g["ma.in_proj_weight"][32 * i:32 * i + 32].abs().max() > 0)
+        assert i == 1 or bool(g["ma.in_proj_bias"][32 * i:32 * i + 32].abs().max() > 0)      # (K's bias cancels in the soft-max)
+    assert len(tapes) == 2 and not tapes[1].pgrads, "direct placement, yet tape.pgrads is not empty"
+    assert not any(isinstance(k, ops._ParamRows) for t in tapes for k in t.pgrads)

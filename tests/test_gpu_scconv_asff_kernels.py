@@ -372,6 +372,89 @@ def test_asff_dlogits_width(lddl, nsrc, dt):
     _asff_bwd_case("c128", nsrc, 4, lddl, "mixed", (0, 0, 0), dt)
 
 
+# ============================================================================ ops.asff_fuse_forward / ops.asff_fuse_backward
+def _nhwc(v, C=None):
+    """A View, or a plain [P, ld] tensor with its first C columns, as the NHWC view [1, C, P, 1] the ops wrappers take."""
+    t, c0, C = (v.parent, C0, v.C) if isinstance(v, View) else (v, 0, C)
+    return t.view(1, t.shape[0], 1, t.shape[1]).permute(0, 3, 1, 2)[:, c0:c0 + C]
+
+
+def _bytes(t):
+    return t.contiguous().view(torch.uint8)
+
+
+ASFF_WRAPPER_INTO = {3: [None, (1, 0, 1), (1, 1, 1)], 2: [None, (0, 1), (1, 1)]}
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("nsrc,ldl,into", [(n, ldl, a) for n, ldl in ((3, 4), (2, 2)) for a in ASFF_WRAPPER_INTO[n]],
+                         ids=lambda v: "into" + ("".join(map(str, v)) if v else "None") if not isinstance(v, int) else str(v))
+@pytest.mark.parametrize("shape", ["p1", "p3"])
+def test_asff_wrappers_are_the_direct_calls(shape, nsrc, ldl, into, dt):
+    """ops.asff_fuse_forward / asff_fuse_backward on NHWC views of the same strided operands: within the groups' budgets of the f64
+    reference, and byte for byte what the direct call gives; `into` selects the kernel's acc flags and comes back as the result."""
+    from dedark_yolo_amd import ops
+    call, ptr, stream, dt_id = _api()
+    c = sr.asff_case(shape, nsrc, ldl, "mixed", dt)
+    P, C = c["P"], c["C"]
+    what = f"wrapper {shape} {nsrc}src ldl={ldl} into={into} {dt}"
+    xs, lg, arg = _asff_views(c, dt)
+    src, logits = [_nhwc(v) for v in xs[:nsrc]], _nhwc(lg, nsrc)
+    # forward: a fresh output, and `out=` a strided view
+    ref, t32 = sr.asff_ref(c["xs"], c["logits"])[0], sr.asff_ref(c["xs"], c["logits"], torch.float32)[0]
+    ov, wv = View(P, C, C + 48, DT[dt]), View(P, C, C + 48, DT[dt])
+    call("dy_asff_fuse_fwd", *arg(xs[0]), *arg(xs[1]), *arg(xs[2]), ptr(lg), ldl, ov.ptr, ov.ld, P, C, dt_id(DT[dt]), stream())
+    fresh = ops.asff_fuse_forward(src, logits)
+    assert ops.asff_fuse_forward(src, logits, out=_nhwc(wv)).data_ptr() == wv.ptr
+    torch.cuda.synchronize()
+    assert tuple(fresh.shape) == (1, C, P, 1) and fresh.dtype == DT[dt]
+    _elementwise("asff_fwd", wv.get(1, P, C), ref[None], t32[None], dt, what)
+    assert torch.equal(_bytes(ov.parent), _bytes(wv.parent)) and torch.equal(_bytes(fresh.permute(0, 2, 3, 1).reshape(P, C)), _bytes(ov.parent[:, C0:C0 + C]))
+    # backward
+    acc = tuple(into or (0,) * nsrc) + (0,) * (3 - nsrc)
+    priors = [c["priors"][k] if acc[k] else None for k in range(nsrc)]
+    dxs, dlog = sr.asff_bwd_ref(c["xs"], c["logits"], c["dout"], priors)
+    dxs32, dlog32 = sr.asff_bwd_ref(c["xs"], c["logits"], c["dout"], priors, torch.float32)
+    gv = View(P, C, C + 48, DT[dt], c["dout"])
+    mk = lambda: [View(P, C, C + 56 + 8 * k, DT[dt], *([priors[k]] if priors[k] is not None else [])) for k in range(nsrc)] + [None] * (3 - nsrc)
+    dv, wd = mk(), mk()
+    lddl = ops.ld_of(logits)                                  # the wrapper's dlogits buffer is as wide as the logits' own
+    dl = torch.full((P, lddl), float("nan"), device="cuda", dtype=DT[dt])
+    call("dy_asff_fuse_bwd", gv.ptr, gv.ld, *arg(xs[0]), *arg(xs[1]), *arg(xs[2]), ptr(lg), ldl, *arg(dv[0]), *arg(dv[1]), *arg(dv[2]),
+         ptr(dl), lddl, P, C, *acc, dt_id(DT[dt]), stream())
+    got, gl = ops.asff_fuse_backward(_nhwc(gv), src, logits, into=into and [_nhwc(wd[k]) if acc[k] else None for k in range(nsrc)])
+    torch.cuda.synchronize()
+    assert len(got) == nsrc and tuple(gl.shape) == (1, nsrc, P, 1) and ops.ld_of(gl) == lddl
+    for k in range(nsrc):
+        assert tuple(got[k].shape) == (1, C, P, 1) and (got[k].data_ptr() == wd[k].ptr) == bool(acc[k]), f"{what}: dx{k} is into[{k}] when given"
+        flat = got[k].permute(0, 2, 3, 1).reshape(P, C)
+        _elementwise("asff_dx", flat.double().cpu()[None], dxs[k][None], dxs32[k][None], dt, what + f" dx{k}")
+        assert torch.equal(_bytes(flat), _bytes(dv[k].parent[:, C0:C0 + C])), f"{what}: dx{k} differs from the direct call"
+    flat = gl.permute(0, 2, 3, 1).reshape(P, nsrc)
+    _elementwise("asff_dlogits", flat.double().cpu()[None], dlog[None], dlog32[None], dt, what)
+    assert torch.equal(_bytes(flat), _bytes(dl[:, :nsrc])), f"{what}: dlogits differ from the direct call"
+    for v in xs[:nsrc] + [gv, ov, wv] + [wd[k] for k in range(nsrc) if acc[k]]:
+        v.intact(what)
+
+
+def test_asff_wrappers_refuse_mismatched_operands():
+    from dedark_yolo_amd import ops
+    x = [ops.empty_nhwc(1, 16, 2, 2, torch.float32, "cuda") for _ in range(4)]
+    lg = ops.empty_nhwc(1, 4, 2, 2, torch.float32, "cuda")
+    with pytest.raises(RuntimeError, match="two or three sources"):
+        ops.asff_fuse_forward(x[:1], lg[:, :1])
+    with pytest.raises(RuntimeError, match="two or three sources"):
+        ops.asff_fuse_forward(x, lg)
+    with pytest.raises(RuntimeError, match="two or three sources"):
+        ops.asff_fuse_forward([x[0], x[1][:, :8]], lg[:, :2])
+    with pytest.raises(RuntimeError, match="two or three sources"):
+        ops.asff_fuse_forward(x[:2], lg[:, :2], out=x[2].half())
+    with pytest.raises(RuntimeError, match="need logits"):
+        ops.asff_fuse_forward(x[:3], lg[:, :2])
+    with pytest.raises(RuntimeError, match="two or three sources"):
+        ops.asff_fuse_backward(x[3][:, :8], x[:3], lg[:, :3])
+
+
 # ========================================================================================================= argument checks
 def _bad_calls():
     """name -> (entry, arguments).  Every tensor holds 7 and is large enough for the call as written, so even a check that
