@@ -1871,19 +1871,61 @@ class ExtractParameters2(nn.Module):
         self.fc2 = nn.Linear(64, self.output_dim)
 
 
+# the reference filters' short names (filtersB.py: DeDarkFilter, ImprovedWhiteBalanceFilter, GammaFilter, ToneFilter, ContrastFilter,
+# UsmFilter) and the chain filter_cfg.py:75 builds
+FILTER_NAMES = ("DF", "W", "G", "T", "Ct", "UF")
+DEFAULT_FILTERS = ("DF", "W", "G", "Ct", "UF")
+_FILTER_CODES = dict(DF=1, W=2, G=3, T=4, Ct=5)           # DY_FILTER_* of include/dedark_yolo.h
+
+
+def check_filters(filters):
+    """A chain as the tuple of short names lowlight_recovery runs: None -> DEFAULT_FILTERS; an empty chain, an unknown or a repeated
+    name raise ValueError; UF anywhere but last raises NotImplementedError (the blur needs the finished image)."""
+    if filters is None:
+        return DEFAULT_FILTERS
+    if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
+        raise ValueError(f"filters: expected a list of filter names out of {list(FILTER_NAMES)}, got {filters!r}")
+    names = tuple(filters)
+    if not names:
+        raise ValueError("filters: the chain is empty")
+    for k, n in enumerate(names):
+        if n not in FILTER_NAMES:
+            raise ValueError(f"filters: unknown filter {n!r} at position {k} (known: {list(FILTER_NAMES)})")
+        if n in names[:k]:
+            raise ValueError(f"filters: {n!r} is repeated at position {k}")
+    if "UF" in names and names.index("UF") != len(names) - 1:
+        raise NotImplementedError(f"filters: 'UF' at position {names.index('UF')} of {list(names)}: UsmFilter is only implemented as the last filter")
+    return names
+
+
+def chain_word(names):
+    """the pointwise filters of a chain as dy_filter_chain_fwd/bwd take them: one code per 4 bits, first stage lowest"""
+    w = 0
+    for k, n in enumerate(names):
+        w |= _FILTER_CODES[n] << (4 * k)
+    return w
+
+
 class lowlight_recovery(DyModule):
     """Image-adaptive enhancement front-end (reference ultralytics/nn/modules/llie.py:11-54).
 
     forward(x [B,3,H,W] fp32, dedark_A [B,3] | None, IcA [B,1,H,W] | None) -> enhanced image [B,3,H,W] (a 3-channel view of an
     NHWC8 buffer in the compute dtype, consumed in place by the stem conv).  All filter math is fp32.
+
+    `filters`: the chain as an ordered list of the reference filters' short names (the list `cfg.filters` of filter_cfg.py:65-75;
+    a model yaml's top-level `filters:` key), None = DEFAULT_FILTERS.  The default chain runs the fused pair
+    dy_filters_pointwise_fwd/bwd + dy_usm_*; any other chain runs dy_filter_chain_fwd/bwd (csrc/filterchain.hip) for its pointwise
+    part, dy_tone_params_* when it has a ToneFilter and dy_usm_* when it ends in UF.  The filters hold no parameters: the
+    state_dict does not depend on the chain.
     """
     in_dtype = torch.float32
 
     _planar_grad_ok = True          # _bwd takes the planar gradient written by the direct stem dgrad kernel
 
-    def __init__(self, in_channels=3, out_channels=3):
+    def __init__(self, in_channels=3, out_channels=3, filters=None):
         super().__init__()
         self.extractor = ExtractParameters2()
+        self.filter_names = check_filters(filters)
 
     def _adapt(self, t):
         ops.require_gpu(t)
@@ -1916,6 +1958,8 @@ class lowlight_recovery(DyModule):
         feat = _linear(tape, t, ex.fc2.weight, ex.fc2.bias)              # [B,15,1,1], ld 16
         params = torch.empty((B, 8), dtype=f32, device=dev)
         call("dy_filter_params_fwd", ptr(feat), ld_of(feat), ptr(params), B, st)
+        if self.filter_names != DEFAULT_FILTERS:
+            return self._chain_fwd(tape, x, feat, params, A, I)
         s4 = torch.empty((B, 3, H, W), dtype=f32, device=dev)
         call("dy_filters_pointwise_fwd", ptr(x), ptr(params), ptr(A), ptr(I), ptr(s4), B, H, W, int(ops.get_compute_dtype() != torch.float32), st)
         cd = ops.get_compute_dtype()
@@ -1927,6 +1971,33 @@ class lowlight_recovery(DyModule):
             tape.push(dict(x=x, feat=feat, params=params, hp=hp, A=A, I=I))
         return out8[:, :3]
 
+    def _chain_fwd(self, tape, x, feat, params, A, I):
+        """any chain but the default: [dy_tone_params_fwd] -> dy_filter_chain_fwd (the filters before UF, one pass) ->
+        dy_usm_fwd, or dy_image_to_nhwc8 when the chain has no UF"""
+        B, _, H, W = x.shape
+        dev, f32, st, cd = x.device, torch.float32, stream(), ops.get_compute_dtype()
+        names = self.filter_names
+        pw = tuple(n for n in names if n != "UF")
+        tone = None
+        if "T" in pw:
+            tone = torch.empty((B, 8), dtype=f32, device=dev)
+            call("dy_tone_params_fwd", ptr(feat), ld_of(feat), ptr(tone), B, st)
+        s = x
+        if pw:
+            s = torch.empty((B, 3, H, W), dtype=f32, device=dev)
+            call("dy_filter_chain_fwd", ptr(x), ptr(params), ptr(tone), ptr(A), ptr(I), chain_word(pw), ptr(s), B, H, W, int(cd != f32), st)
+        out8 = torch.empty((B, H, W, 8), dtype=cd, device=dev).permute(0, 3, 1, 2)
+        hp = None
+        if names[-1] == "UF":
+            hp = torch.empty((B, 3, H, W), dtype=f32, device=dev) if tape is not None else None
+            call("dy_usm_fwd", ptr(s), ptr(params), None, ptr(out8), ptr(hp), B, H, W, ops.dt_id(cd), st)
+        else:
+            call("dy_image_to_nhwc8", ptr(s), B, H, W, ptr(out8), H, W, ops.dt_id(cd), st)
+        ops.emu_round(out8)
+        if tape is not None:
+            tape.push(dict(x=x, feat=feat, params=params, hp=hp, A=A, I=I, tone=tone))
+        return out8[:, :3]
+
     def _bwd(self, tape, dout, needs=(False,)):
         s = tape.pop()
         x, feat, params, hp = s["x"], s["feat"], s["params"], s["hp"]
@@ -1934,20 +2005,23 @@ class lowlight_recovery(DyModule):
         dev, f32, st = x.device, torch.float32, stream()
         need_dx = bool(needs[0])
         dparams = torch.zeros((B, 8), dtype=torch.float64, device=dev)      # f64 atomics: order-free sums (frontend.hip)
-        ds4 = torch.empty((B, 3, H, W), dtype=f32, device=dev)
         if dout.is_contiguous() and dout.shape[1] == 3:       # planar gradient from the direct stem dgrad kernel
             dld = 0
         else:
             ops.padded_channels(dout)           # raises unless dout is a zero-padded NHWC view
             dld = ld_of(dout)
-        call("dy_usm_bwd", None, ptr(dout), dld, ptr(hp), ptr(params), ptr(ds4), ptr(dparams), B, H, W,
-             ops.dt_id(dout.dtype), st)
-        dx = torch.empty((B, 3, H, W), dtype=f32, device=dev) if need_dx else None
-        call("dy_filters_pointwise_bwd", ptr(x), ptr(params), ptr(s["A"]), ptr(s["I"]), ptr(ds4), ptr(dx), ptr(dparams), B, H, W, 0,
-             int(ops.get_compute_dtype() != torch.float32), st)
         fl = ld_of(feat)
         dfeat = torch.empty((B, 1, 1, fl), dtype=f32, device=dev).permute(0, 3, 1, 2)
-        call("dy_filter_params_bwd", ptr(feat), fl, ptr(dparams), ptr(dfeat), B, st)
+        if self.filter_names != DEFAULT_FILTERS:
+            dx = self._chain_bwd(s, dout, dld, dparams, dfeat, need_dx)
+        else:
+            ds4 = torch.empty((B, 3, H, W), dtype=f32, device=dev)
+            call("dy_usm_bwd", None, ptr(dout), dld, ptr(hp), ptr(params), ptr(ds4), ptr(dparams), B, H, W,
+                 ops.dt_id(dout.dtype), st)
+            dx = torch.empty((B, 3, H, W), dtype=f32, device=dev) if need_dx else None
+            call("dy_filters_pointwise_bwd", ptr(x), ptr(params), ptr(s["A"]), ptr(s["I"]), ptr(ds4), ptr(dx), ptr(dparams), B, H, W, 0,
+                 int(ops.get_compute_dtype() != torch.float32), st)
+            call("dy_filter_params_bwd", ptr(feat), fl, ptr(dparams), ptr(dfeat), B, st)
         g = conv_backward(tape, dfeat[:, :15])            # fc2
         g = conv_backward(tape, g)                        # fc1
         if not _EXTRACTOR_F32 and ops.get_compute_dtype() != f32:
@@ -1958,4 +2032,31 @@ class lowlight_recovery(DyModule):
             if g.dtype != f32:
                 g = as_nhwc(g, f32)
             call("dy_resize_bwd", ptr(g), ld_of(g), B, H, W, 256, 256, ptr(dx), st)
+        return dx
+
+    def _chain_bwd(self, s, dout, dld, dparams, dfeat, need_dx):
+        """adjoint of _chain_fwd up to the regressed features: dy_usm_bwd (chains ending in UF; its f32 planar result feeds
+        dy_filter_chain_bwd) or dy_filter_chain_bwd straight on the stem's gradient in either of its layouts; then
+        dy_filter_params_bwd and, after it, dy_tone_params_bwd into columns 5..12 of the same rows.  Returns dx (None unless needed)."""
+        x, feat, params, tone = s["x"], s["feat"], s["params"], s["tone"]
+        B, _, H, W = x.shape
+        dev, f32, st = x.device, torch.float32, stream()
+        names = self.filter_names
+        pw = tuple(n for n in names if n != "UF")
+        fast = int(ops.get_compute_dtype() != f32)
+        dtone = torch.zeros((B, 8), dtype=torch.float64, device=dev) if tone is not None else None
+        dx = torch.empty((B, 3, H, W), dtype=f32, device=dev) if need_dx else None
+        if names[-1] == "UF":
+            ds = dx if (not pw and need_dx) else torch.empty((B, 3, H, W), dtype=f32, device=dev)
+            call("dy_usm_bwd", None, ptr(dout), dld, ptr(s["hp"]), ptr(params), ptr(ds), ptr(dparams), B, H, W, ops.dt_id(dout.dtype), st)
+            if pw:
+                call("dy_filter_chain_bwd", ptr(x), ptr(params), ptr(tone), ptr(s["A"]), ptr(s["I"]), chain_word(pw), ptr(ds), None, 0, 0,
+                     ptr(dx), ptr(dparams), ptr(dtone), B, H, W, 0, fast, st)
+        else:
+            call("dy_filter_chain_bwd", ptr(x), ptr(params), ptr(tone), ptr(s["A"]), ptr(s["I"]), chain_word(pw), None, ptr(dout), dld,
+                 ops.dt_id(dout.dtype), ptr(dx), ptr(dparams), ptr(dtone), B, H, W, 0, fast, st)
+        fl = ld_of(feat)
+        call("dy_filter_params_bwd", ptr(feat), fl, ptr(dparams), ptr(dfeat), B, st)
+        if tone is not None:
+            call("dy_tone_params_bwd", ptr(feat), fl, ptr(dtone), ptr(dfeat), B, st)
         return dx

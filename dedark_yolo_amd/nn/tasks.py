@@ -346,7 +346,9 @@ def parse_model(d, ch, verbose=False):
         rel = [src] if isinstance(src, int) else list(src)
         row.ch_in = [(widths[j] if widths else ch) if j == -1 else widths[j] for j in rel]
         ctor_args, c_out, n_mod = _RULES.get(cls, _PASS_THROUGH)(row)
-        layer = nn.Sequential(*(cls(*ctor_args) for _ in range(n_mod))) if n_mod > 1 else cls(*ctor_args)
+        # the yaml's top-level `filters:` (the front-end's chain, filter_cfg.py:65-75) goes to every lowlight_recovery row
+        ctor_kw = dict(filters=d["filters"]) if cls is lowlight_recovery and "filters" in d else {}
+        layer = nn.Sequential(*(cls(*ctor_args, **ctor_kw) for _ in range(n_mod))) if n_mod > 1 else cls(*ctor_args, **ctor_kw)
         layer.np = sum(p.numel() for p in layer.parameters())
         layer.i, layer.f, layer.type = index, src, kind
         layer.c_out = c_out                       # output channels (GraphPlan places producers inside yaml-level Concat buffers)

@@ -178,12 +178,40 @@ def load_checkpoint(path, device="cpu"):
         names = _plain(getattr(rec, "names", None))
         if isinstance(yaml_, dict) and nc is None:
             nc = yaml_.get("nc")
+        if isinstance(yaml_, dict) and yaml_.get("filters") is None:       # a reference-written file: its chain is the pickled filter objects
+            chain = pickled_filter_chain(rec)
+            if chain is not None and tuple(chain) != _DEFAULT_CHAIN:
+                yaml_ = dict(yaml_, filters=chain)
     ta = ck.get("train_args")
     return SimpleNamespace(state_dict=f32(sd), model_sd=f32(model_sd), yaml=yaml_, nc=nc, names=names,
                            train_args=_plain(ta) if ta is not None else None, epoch=ck.get("epoch"),
                            best_fitness=ck.get("best_fitness"), updates=ck.get("updates"), optimizer=_plain(ck.get("optimizer")),
                            dy_state=_plain(ck.get("dy_state")),
                            source="reference-pickle" if rec is not None else "state-dict")
+
+
+def pickled_filter_chain(rec):
+    """The front-end chain of a pickled reference model as a list of short names: the class names of the `filters` ModuleList of its
+    first lowlight_recovery layer (llie.py:15 = filter_cfg.cfg.filters at construction); None for a model without that layer.  A
+    filter class this package has no kernel for raises NotImplementedError: loading it as another chain would compute something
+    else without a word."""
+    layers = getattr(getattr(rec, "_modules", {}).get("model"), "_modules", None) or {}
+    for m in layers.values():
+        if type(m).__name__ != "lowlight_recovery" or not _is_module_record(m):
+            continue
+        flt = m._modules.get("filters")
+        if flt is None:
+            return None
+        short = {cname: attrs["short_name"] for cname, attrs in _FILTERS.values()}
+        chain = []
+        for f in flt._modules.values():
+            cname = type(f).__name__
+            if cname not in short:
+                raise NotImplementedError(f"checkpoint: the front-end chain holds a {cname}, which has no kernel here "
+                                          f"(known: {sorted(short)})")
+            chain.append(short[cname])
+        return chain
+    return None
 
 
 def intersect_dicts(da, db, exclude=()):
@@ -229,12 +257,16 @@ _FILTER_CFG = dict(num_filter_parameters=15, dedark_begin_param=0, wb_begin_para
                    usm_range=(0.0, 5), masking=False, minimum_strength=0.3, maximum_sharpness=1, clamp=False, source_img_size=64,
                    base_channels=32, dropout_keep_prob=0.5, share_feed_dict=True, shared_feature_extractor=True, fc1_size=128, bnw=False,
                    feature_extractor_dims=4096)
-_FILTERS = (("DeDarkFilter", dict(num_filter_parameters=1, short_name="DF", filter_parameters=None, begin_filter_parameter=0)),
-            ("ImprovedWhiteBalanceFilter", dict(num_filter_parameters=3, short_name="W", filter_parameters=None, channels=3,
-                                                begin_filter_parameter=1)),
-            ("GammaFilter", dict(num_filter_parameters=1, short_name="G", filter_parameters=None, begin_filter_parameter=4)),
-            ("ContrastFilter", dict(num_filter_parameters=1, short_name="Ct", filter_parameters=None, begin_filter_parameter=13)),
-            ("UsmFilter", dict(num_filter_parameters=1, short_name="UF", filter_parameters=None, begin_filter_parameter=14)))
+# (keyed by short name; the attribute ORDER is the order the reference's constructors assign them in, which the pickle keeps)
+_FILTERS = {"DF": ("DeDarkFilter", dict(num_filter_parameters=1, short_name="DF", filter_parameters=None, begin_filter_parameter=0)),
+            "W": ("ImprovedWhiteBalanceFilter", dict(num_filter_parameters=3, short_name="W", filter_parameters=None, channels=3,
+                                                     begin_filter_parameter=1)),
+            "G": ("GammaFilter", dict(num_filter_parameters=1, short_name="G", filter_parameters=None, begin_filter_parameter=4)),
+            "T": ("ToneFilter", dict(num_filter_parameters=8, short_name="T", filter_parameters=None, curve_steps=8,
+                                     begin_filter_parameter=5)),
+            "Ct": ("ContrastFilter", dict(num_filter_parameters=1, short_name="Ct", filter_parameters=None, begin_filter_parameter=13)),
+            "UF": ("UsmFilter", dict(num_filter_parameters=1, short_name="UF", filter_parameters=None, begin_filter_parameter=14))}
+_DEFAULT_CHAIN = ("DF", "W", "G", "Ct", "UF")        # filter_cfg.py:75 (nn.modules.DEFAULT_FILTERS)
 
 # plain (non-module, non-parameter) attributes an instance of each reference class carries (g12_ref_skeleton.json); the product's
 # modules hold the same names with the same values plus a few of their own, which must not travel
@@ -417,7 +449,7 @@ class _RefWriter:
         self.fill(state, mod, prefix)
         kids = state["_modules"]
         if name == "lowlight_recovery":
-            kids["filters"] = self.filter_list()
+            kids["filters"] = self.filter_list(tuple(getattr(mod, "filter_names", _DEFAULT_CHAIN)))
         elif name == "ExtractParameters2":
             state["cfg"] = self.cfg
         elif name == "SPPF":                              # the pooling layer is an object there (block.py:331), a kernel argument here
@@ -442,11 +474,16 @@ class _RefWriter:
         obj.__dict__.update(state)
         return obj
 
-    def filter_list(self):
+    def filter_list(self, chain=_DEFAULT_CHAIN):
+        """the filter objects of the model's chain, in chain order (ONE list per file, like filter_cfg.cfg.filters)"""
+        if self.filters is not None and chain != self.chain:
+            raise NotImplementedError(f"save_reference_checkpoint: two front-ends with different chains ({list(self.chain)} and "
+                                      f"{list(chain)}); the reference has one filter list per process")
         if self.filters is None:
             nn = torch.nn
+            self.chain = chain
             objs = collections.OrderedDict()
-            for k, (fname, attrs) in enumerate(_FILTERS):
+            for k, (fname, attrs) in enumerate(_FILTERS[n] for n in chain):
                 o = _standin_type("ultralytics.nn.modules.filtersB", fname)()
                 st = _nn_base_state(self.training)
                 st.update(cfg=self.cfg, **attrs)

@@ -279,6 +279,39 @@ int dy_usm_bwd(const float* dout_nchw, const void* dout_nhwc, int dout_ld, const
 int dy_filters_pointwise_bwd(const float* x, const float* params, const float* A, const float* IcA, const float* ds4,
                              float* dx, double* dparams, int B, int H, int W, int accumulate, int fast_math, void* stream);
 
+/* ------------------------------------------------------------------------------------- front-end filter chains
+ * Any order of the reference's pointwise filters (U/nn/modules/filter_cfg.py:17-75 builds the list, llie.py:51-52 applies it in
+ * order), ToneFilter (filtersB.py:262-286) among them.  The default chain keeps dy_filters_pointwise_fwd/bwd. */
+#define DY_TONE_STEPS 8          /* cfg.curve_steps (filter_cfg.py:28): features 5..12 (tone_begin_param, :23) */
+#define DY_CHAIN_MAX 5           /* pointwise stages of a chain: each filter at most once; UsmFilter stays with dy_usm_* */
+#define DY_FILTER_DEDARK 1       /* DF  filtersB.py:178-216 */
+#define DY_FILTER_WB 2           /* W   filtersB.py:237-259 */
+#define DY_FILTER_GAMMA 3        /* G   filtersB.py:219-233 */
+#define DY_FILTER_TONE 4         /* T   filtersB.py:262-286 */
+#define DY_FILTER_CONTRAST 5     /* Ct  filtersB.py:289-303 */
+/* ToneFilter.filter_param_regressor (filtersB.py:271-274, tanh_range(0.5, 2) of filter_cfg.py:34):
+ * tone[b, i] = tanh(feat[b, 5 + i]) * 0.75 + 1.25, i < 8.  Columns outside 5..12 are not read. */
+int dy_tone_params_fwd(const float* feat, int feat_ld, float* tone, int B, void* stream);
+/* its adjoint: writes columns 5..12 of dfeat ONLY (run it after dy_filter_params_bwd, which zeroes the row); dtone f64 [B,8] is
+ * zeroed by the caller and accumulated by dy_filter_chain_bwd */
+int dy_tone_params_bwd(const float* feat, int feat_ld, const double* dtone, float* dfeat, int B, void* stream);
+/* The pointwise part of a filter chain in one pass, x [B,3,H,W] f32 -> y (replaces the loop of llie.py:51-52 over the filters of
+ * filter_cfg.py:17-75 up to UsmFilter).  `chain`: one DY_FILTER_* code per 4 bits, first stage in the lowest bits, 0 ends it;
+ * 1..DY_CHAIN_MAX stages, none repeated.  Each stage sees the output of the one before it; the contrast filter's per-row luminance
+ * comes from columns 0..2 of ITS input and the stages after it act on the multiplied row.  params [B,8] as dy_filter_params_fwd
+ * writes them; tone [B,8] (NULL without a tone stage); A [B,3] or NULL (0.8); IcA [B,H,W] or NULL (0.5).  W >= 3 with a contrast
+ * stage, else W >= 1.  fast_math as dy_filters_pointwise_fwd. */
+int dy_filter_chain_fwd(const float* x, const float* params, const float* tone, const float* A, const float* IcA,
+                        unsigned chain, float* y, int B, int H, int W, int fast_math, void* stream);
+/* Backward: recomputes the chain from x, writes dx (overwrite or +=; NULL = not needed) and accumulates dparams[b, 0..5] and
+ * dtone[b, 0..7] (f64 atomics, as dy_filters_pointwise_bwd; dtone may be NULL without a tone stage).  The upstream gradient is
+ * either NCHW f32 (dy_nchw: what dy_usm_bwd writes) or, for a chain that ends without UsmFilter, in `dtype` a padded NHWC view
+ * with pixel stride dy_ld >= 3 / a planar [B,3,H,W] tensor when dy_ld == 0 (dy_any: the two layouts dy_usm_bwd accepts);
+ * exactly one of the two pointers is non-NULL. */
+int dy_filter_chain_bwd(const float* x, const float* params, const float* tone, const float* A, const float* IcA,
+                        unsigned chain, const float* dy_nchw, const void* dy_any, int dy_ld, int dtype, float* dx,
+                        double* dparams, double* dtone, int B, int H, int W, int accumulate, int fast_math, void* stream);
+
 /* ------------------------------------------------------------------------------------------ detection loss
  * v8DetectionLoss / RcoveryDetectionLoss (U/utils/loss.py:103-193,388-416), TaskAlignedAssigner (U/utils/tal.py),
  * bbox_iou CIoU (U/utils/metrics.py:75-128), make_anchors / dist2bbox (tal.py:246-271). */
