@@ -425,14 +425,6 @@ int check_shape(const char* who, int B, int L, int H, int D) {
   return 0;
 }
 
-// token-major view of H D channels: exactly those are touched, element alignment is enough
-int check_tokens(const char* who, const void* p, long ld, int HD, int dtype) {
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  if (int e = dy_check_dtype(who, dtype)) return e;
-  DY_CHECK(ld >= HD && ((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: bad view (pitch %ld < %d channels, or misaligned)", who, ld, HD);
-  return 0;
-}
-
 template <typename T> int lds_bytes(int DP, int own_imgs, int swept_imgs, int p_imgs, int row_consts) {
   const int ld = DP + Cfg<T>::PAD;
   return (int)sizeof(T) * ((own_imgs * TQ + swept_imgs * Cfg<T>::TS) * ld + p_imgs * 4 * 16 * Cfg<T>::LDP) + 8 * row_consts;
@@ -454,10 +446,10 @@ template <typename F> void with_blocks(int DP, F&& f) {
 extern "C" int dy_attn_fwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o, int64_t o_ld, float* lse, int B,
                            int L, int H, int D, float scale, int dtype, void* stream) {
   if (int e = check_shape("dy_attn_fwd", B, L, H, D)) return e;
-  if (int e = check_tokens("dy_attn_fwd(q)", q, q_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_fwd(k)", k, k_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_fwd(v)", v, v_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_fwd(o)", o, o_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_fwd(q)", q, q_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_fwd(k)", k, k_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_fwd(v)", v, v_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_fwd(o)", o, o_ld, H * D, dtype)) return e;
   const int es = dy_elem_size(dtype), DP = (D + 31) / 32 * 32;
   const int vq = dy_aligned16(q, q_ld, es), vk = dy_aligned16(k, k_ld, es), vv = dy_aligned16(v, v_ld, es);
   const dim3 grid((unsigned)((L + TQ - 1) / TQ), (unsigned)H, (unsigned)B);
@@ -481,14 +473,14 @@ extern "C" int dy_attn_bwd(const void* q, int64_t q_ld, const void* k, int64_t k
                            const void* dout, int64_t do_ld, const float* lse, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld, void* dv, int64_t dv_ld,
                            int B, int L, int H, int D, float scale, int dtype, void* stream) {
   if (int e = check_shape("dy_attn_bwd", B, L, H, D)) return e;
-  if (int e = check_tokens("dy_attn_bwd(q)", q, q_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(k)", k, k_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(v)", v, v_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(o)", o, o_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(do)", dout, do_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(dq)", dq, dq_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(dk)", dk, dk_ld, H * D, dtype)) return e;
-  if (int e = check_tokens("dy_attn_bwd(dv)", dv, dv_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(q)", q, q_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(k)", k, k_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(v)", v, v_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(o)", o, o_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(do)", dout, do_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(dq)", dq, dq_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(dk)", dk, dk_ld, H * D, dtype)) return e;
+  if (int e = dy_check_lanes("dy_attn_bwd(dv)", dv, dv_ld, H * D, dtype)) return e;
   DY_CHECK(lse != nullptr, "dy_attn_bwd: the forward's LSE is needed");
   const int es = dy_elem_size(dtype), DP = (D + 31) / 32 * 32;
   const int vq = dy_aligned16(q, q_ld, es), vk = dy_aligned16(k, k_ld, es), vv = dy_aligned16(v, v_ld, es), vdo = dy_aligned16(dout, do_ld, es);

@@ -897,11 +897,10 @@ int launch_thin(const dy_conv_desc* d, int mode, hipStream_t st, const dy_conv_d
 
 // the register-staged kernel takes every problem: its instantiation by dtype and mode
 int launch_generic(const dy_conv_desc* d, int mode, hipStream_t st, const dy_conv_desc* classes = nullptr, int ncls = 0) {
-  if (mode == 0)
-    return d->dtype == DY_F32 ? launch_conv<float, 0>(d, st, classes, ncls)
-                              : (d->dtype == DY_F16 ? launch_conv<f16_t, 0>(d, st, classes, ncls) : launch_conv<bf16_t, 0>(d, st, classes, ncls));
-  return d->dtype == DY_F32 ? launch_conv<float, 1>(d, st, classes, ncls)
-                            : (d->dtype == DY_F16 ? launch_conv<f16_t, 1>(d, st, classes, ncls) : launch_conv<bf16_t, 1>(d, st, classes, ncls));
+  int r = 0;
+  if (mode == 0) DY_DISPATCH_DTYPE("dy_conv2d", d->dtype, r = launch_conv<T, 0>(d, st, classes, ncls));
+  else DY_DISPATCH_DTYPE("dy_conv2d", d->dtype, r = launch_conv<T, 1>(d, st, classes, ncls));
+  return r;
 }
 
 int check_conv(const dy_conv_desc* d, const char* who) {

@@ -1,11 +1,12 @@
 // What the convolution routes share outside their kernels: two device helpers, the descriptor -> kernel-parameter fills, the
 // eligibility checks more than one route repeats, and the prototype of every route's entry points; for the weight gradient also
-// the split plan of the pixel loop and the slab layout its shared reduce kernel reads.  The order in which the routes are tried is
-// the pair of tables in conv.hip (kRoutes, kWgradRoutes); tile-count and K thresholds stay with the kernel they tune.
+// the slab layout its shared reduce kernel reads (the split plan of the pixel loop is dy_plan.h's).  The order in which the routes
+// are tried is the pair of tables in conv.hip (kRoutes, kWgradRoutes); tile-count and K thresholds stay with the kernel they tune.
 #pragma once
 #include <type_traits>
 #include <utility>
 #include "dy_common.h"
+#include "dy_plan.h"
 #include "../../include/dedark_yolo.h"
 
 namespace dy_route {
@@ -207,25 +208,6 @@ inline void fill_wgrad_problem(P& p, const DyWgradArgs& a) {
   p.M = (long)a.N * a.Ho * a.Wo;
   p.Ktot = a.KH * a.KW * a.Cin_pad;
   if constexpr (HasPointwise<P>::value) p.pointwise = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0) ? 1 : 0;
-}
-
-// The M output pixels of a weight gradient in `splits` chunks of `chunk` pixels, one slab set (all tiles) per split: `want` splits
-// (the caller's target block count over its tile count), no more than leave `min_pixels` per split, than `fit` slab sets in the
-// scratch buffer (scratch_elems / slab_set_elems) or than `grid_cap`, at least one; the chunk is a whole number of `step`-pixel
-// K-steps, and the splits are recounted for it.
-struct WgradSplits {
-  long splits, chunk;
-};
-constexpr long kGridDimYCap = 65535, kNoGridCap = 1L << 40;
-inline WgradSplits plan_wgrad_splits(long M, long want, long min_pixels, long step, long fit, long grid_cap) {
-  const long max_splits = (M + min_pixels - 1) / min_pixels;
-  long splits = want < max_splits ? want : max_splits;
-  if (splits > fit) splits = fit;
-  if (splits < 1) splits = 1;
-  if (splits > grid_cap) splits = grid_cap;
-  long chunk = (M + splits - 1) / splits;
-  chunk = (chunk + step - 1) / step * step;
-  return {(M + chunk - 1) / chunk, chunk};
 }
 
 }  // namespace dy_route

@@ -580,7 +580,7 @@ bool dy_conv_v4_eligible(const dy_conv_desc* d, int mode) {
 }
 
 int dy_conv_v4_launch(const dy_conv_desc* d, int mode, void* stream) {
-  return d->dtype == DY_F16 ? v4_launch<0, f16_t>(d, mode, stream) : v4_launch<0, bf16_t>(d, mode, stream);
+  return dy_dispatch_16bit("conv_v4", d->dtype, [&](auto tag) { return v4_launch<0, typename decltype(tag)::type>(d, mode, stream); });
 }
 
 // The parity classes of a stride-2 data gradient (conv.hip: dgrad_dispatch; heaviest class first) as one launch: same dz, same weight
@@ -606,6 +606,7 @@ bool dy_conv_v4_classes_eligible(const dy_conv_desc* c, int ncls) {
 }
 
 int dy_conv_v4_launch_classes(const dy_conv_desc* c, int ncls, void* stream) {
-  return c[0].dtype == DY_F16 ? v4_launch<0, f16_t>(&c[0], 0, stream, 0, c, ncls) : v4_launch<0, bf16_t>(&c[0], 0, stream, 0, c, ncls);
+  return dy_dispatch_16bit("conv_v4", c[0].dtype,
+                           [&](auto tag) { return v4_launch<0, typename decltype(tag)::type>(&c[0], 0, stream, 0, c, ncls); });
 }
 #endif

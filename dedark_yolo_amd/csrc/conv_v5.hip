@@ -719,32 +719,29 @@ static int v5_launch(const dy_conv_desc* d, int mode, void* stream, const dy_con
                                              {&v5::band_kernel<128, f16_t>, SB128}, {&v5::band_kernel<64, f16_t>, SB64},
                                              {&v5::band_kernel<64, bf16_t, 2>, SB64S}, {&v5::band_kernel<64, f16_t, 2>, SB64S}}))
     return e;
-  const bool f16 = d->dtype == DY_F16;
-  if (band && bn == 128) {
-    dy_note_kernel("v5::band_kernel<128>");
-    if (f16) v5::band_kernel<128, f16_t><<<p.nblk, 256, SB128, (hipStream_t)stream>>>(p);
-    else v5::band_kernel<128, bf16_t><<<p.nblk, 256, SB128, (hipStream_t)stream>>>(p);
-  } else if (band && band64_nband == 2) {
-    dy_note_kernel("v5::band_kernel<64>");
-    if (f16) v5::band_kernel<64, f16_t, 2><<<p.nblk, 256, SB64S, (hipStream_t)stream>>>(p);
-    else v5::band_kernel<64, bf16_t, 2><<<p.nblk, 256, SB64S, (hipStream_t)stream>>>(p);
-  } else if (band) {
-    dy_note_kernel("v5::band_kernel<64>");
-    if (f16) v5::band_kernel<64, f16_t><<<p.nblk, 256, SB64, (hipStream_t)stream>>>(p);
-    else v5::band_kernel<64, bf16_t><<<p.nblk, 256, SB64, (hipStream_t)stream>>>(p);
-  } else if (bn == 128) {
-    dy_note_kernel("v5::conv_kernel<128>");
-    if (f16) v5::conv_kernel<128, f16_t><<<p.nblk, 256, SH128, (hipStream_t)stream>>>(p);
-    else v5::conv_kernel<128, bf16_t><<<p.nblk, 256, SH128, (hipStream_t)stream>>>(p);
-  } else if (slim64) {
-    dy_note_kernel("v5::conv_kernel<64>");
-    if (f16) v5::conv_kernel<64, f16_t, true><<<p.nblk, 256, SH64S, (hipStream_t)stream>>>(p);
-    else v5::conv_kernel<64, bf16_t, true><<<p.nblk, 256, SH64S, (hipStream_t)stream>>>(p);
-  } else {
-    dy_note_kernel("v5::conv_kernel<64>");
-    if (f16) v5::conv_kernel<64, f16_t><<<p.nblk, 256, SH64, (hipStream_t)stream>>>(p);
-    else v5::conv_kernel<64, bf16_t><<<p.nblk, 256, SH64, (hipStream_t)stream>>>(p);
-  }
-  DY_LAUNCH_CHECK();
-  return 0;
+  return dy_dispatch_16bit("conv_v5", d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipStream_t st = (hipStream_t)stream;
+    if (band && bn == 128) {
+      dy_note_kernel("v5::band_kernel<128>");
+      v5::band_kernel<128, T><<<p.nblk, 256, SB128, st>>>(p);
+    } else if (band && band64_nband == 2) {
+      dy_note_kernel("v5::band_kernel<64>");
+      v5::band_kernel<64, T, 2><<<p.nblk, 256, SB64S, st>>>(p);
+    } else if (band) {
+      dy_note_kernel("v5::band_kernel<64>");
+      v5::band_kernel<64, T><<<p.nblk, 256, SB64, st>>>(p);
+    } else if (bn == 128) {
+      dy_note_kernel("v5::conv_kernel<128>");
+      v5::conv_kernel<128, T><<<p.nblk, 256, SH128, st>>>(p);
+    } else if (slim64) {
+      dy_note_kernel("v5::conv_kernel<64>");
+      v5::conv_kernel<64, T, true><<<p.nblk, 256, SH64S, st>>>(p);
+    } else {
+      dy_note_kernel("v5::conv_kernel<64>");
+      v5::conv_kernel<64, T><<<p.nblk, 256, SH64, st>>>(p);
+    }
+    DY_LAUNCH_CHECK();
+    return 0;
+  });
 }

@@ -15,7 +15,9 @@
 // up to four 16-row blocks: v_mfma_f32_16x16x32 (bf16 / f16) or v_mfma_f32_16x16x4_f32, f32 accumulate.  With weights as operand A a
 // lane ends up with 4 consecutive channels of one pixel.  K is padded to the step with zeros in LDS only; the gather reads exactly
 // the channels of its slice (element loads when a slice is no whole vector, 16-byte loads when S3, S1 and the view allow it) and the
-// epilogue writes exactly the rows of the group, so the views may be channel slices of wider buffers with live neighbours.
+// epilogue writes exactly the rows of the group, so the views may be channel slices of wider buffers with live neighbours -- of one
+// buffer too, as long as the source and the destination lanes do not overlap (a block reads all channels and the halo of its pixels
+// while others write theirs: refused, dy_views_overlap).
 //
 // Weight gradient: per group a GEMM over the pixels, rows = dy channels, columns = the 9 C3 + C1 weight columns (+ one column of
 // ones: the bias gradient); both operands are needed pixel-contiguous per channel: f32 stages them transposed ([channel][32 pixels]),
@@ -420,14 +422,6 @@ int check_shape(const char* who, int B, int H, int W, int G, int N, int C3, int 
   return 0;
 }
 
-// exactly the lanes [0, C) of every pixel are touched: any element-aligned view
-int check_slice(const char* who, const void* p, long ld, int C, int dtype) {
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  if (int e = dy_check_dtype(who, dtype)) return e;
-  DY_CHECK(ld >= C && ((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: bad view (ld=%ld, C=%d)", who, ld, C);
-  return 0;
-}
-
 // x view of `rows` output rows per group from the gather (S3 per group at g S3, S1 at 0), K = 9 S3 + S1
 int launch_conv(const char* who, const void* x, long x_ld, const void* wp, const float* bias, void* y, long y_ld, int B, int H, int W, int G, int R,
                 int S3, int S1, int accumulate, int dtype, hipStream_t st) {
@@ -463,18 +457,22 @@ extern "C" int dy_cru_conv_pack(const float* w3, const float* w1, void* wp, int 
 extern "C" int dy_cru_conv_fwd(const void* x, int64_t x_ld, const void* wp, const float* bias, void* y, int64_t y_ld, int B, int H, int W, int G, int N,
                                int C3, int C1, int dtype, void* stream) {
   if (int e = check_shape("dy_cru_conv_fwd", B, H, W, G, N, C3, C1)) return e;
-  if (int e = check_slice("dy_cru_conv_fwd(x)", x, x_ld, C1, dtype)) return e;
-  if (int e = check_slice("dy_cru_conv_fwd(y)", y, y_ld, G * N, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_fwd(x)", x, x_ld, C1, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_fwd(y)", y, y_ld, G * N, dtype)) return e;
   DY_CHECK(wp != nullptr, "dy_cru_conv_fwd: null weight pack");
+  DY_CHECK(!dy_views_overlap(x, x_ld, (long)B * H * W, C1, y, y_ld, (long)B * H * W, G * N, dy_elem_size(dtype)),
+           "dy_cru_conv_fwd: the lanes of x and y overlap (in-place or misplaced slices)");
   return launch_conv("dy_cru_conv_fwd", x, x_ld, wp, bias, y, y_ld, B, H, W, G, N, C3, C1, 0, dtype, (hipStream_t)stream);
 }
 
 extern "C" int dy_cru_conv_dgrad(const void* dy, int64_t dy_ld, const void* wp, void* dx, int64_t dx_ld, int B, int H, int W, int G, int N, int C3,
                                  int C1, int accumulate, int dtype, void* stream) {
   if (int e = check_shape("dy_cru_conv_dgrad", B, H, W, G, N, C3, C1)) return e;
-  if (int e = check_slice("dy_cru_conv_dgrad(dy)", dy, dy_ld, G * N, dtype)) return e;
-  if (int e = check_slice("dy_cru_conv_dgrad(dx)", dx, dx_ld, C1, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_dgrad(dy)", dy, dy_ld, G * N, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_dgrad(dx)", dx, dx_ld, C1, dtype)) return e;
   DY_CHECK(wp != nullptr, "dy_cru_conv_dgrad: null weight pack");
+  DY_CHECK(!dy_views_overlap(dy, dy_ld, (long)B * H * W, G * N, dx, dx_ld, (long)B * H * W, C1, dy_elem_size(dtype)),
+           "dy_cru_conv_dgrad: the lanes of dy and dx overlap (in-place or misplaced slices)");
   // rows: the C3 input channels of the group (all C1 for a pure 1x1); K = the group's N dy channels at nine taps + all G N at the centre
   const int R = C3 > 0 ? C3 : C1, S3 = C3 > 0 ? N : 0;
   return launch_conv("dy_cru_conv_dgrad", dy, dy_ld, wp, nullptr, dx, dx_ld, B, H, W, G, R, S3, G * N, accumulate ? 1 : 0, dtype, (hipStream_t)stream);
@@ -483,8 +481,8 @@ extern "C" int dy_cru_conv_dgrad(const void* dy, int64_t dy_ld, const void* wp, 
 extern "C" int dy_cru_conv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw3, float* db, float* dw1, int B, int H, int W,
                                  int G, int N, int C3, int C1, float* scratch, int64_t scratch_elems, int dtype, void* stream) {
   if (int e = check_shape("dy_cru_conv_wgrad", B, H, W, G, N, C3, C1)) return e;
-  if (int e = check_slice("dy_cru_conv_wgrad(x)", x, x_ld, C1, dtype)) return e;
-  if (int e = check_slice("dy_cru_conv_wgrad(dy)", dy, dy_ld, G * N, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_wgrad(x)", x, x_ld, C1, dtype)) return e;
+  if (int e = dy_check_lanes("dy_cru_conv_wgrad(dy)", dy, dy_ld, G * N, dtype)) return e;
   const int NC = 9 * C3 + C1 + (db ? 1 : 0);
   const long slab = (long)G * N * NC;
   DY_CHECK(scratch && scratch_elems >= slab, "dy_cru_conv_wgrad: scratch of %ld floats needed", slab);
@@ -492,13 +490,9 @@ extern "C" int dy_cru_conv_wgrad(const void* x, int64_t x_ld, const void* dy, in
   const int es = dy_elem_size(dtype);
   const int row_tiles = (N + TR - 1) / TR, col_tiles = (NC + TR - 1) / TR;
   // pixel ranges: whole steps of 32 pixels, about 1024 blocks in all, as many as the scratch holds; a function of the shape alone
-  const long steps = (M + KC - 1) / KC;
-  long splits = 1024 / ((long)row_tiles * col_tiles * G);
-  if (splits > scratch_elems / slab) splits = scratch_elems / slab;
-  if (splits > steps) splits = steps;
-  if (splits < 1) splits = 1;
-  const long range = (steps + splits - 1) / splits * KC;
-  splits = (M + range - 1) / range;
+  const dy_route::WgradSplits plan =
+      dy_route::plan_wgrad_splits(M, 1024 / ((long)row_tiles * col_tiles * G), KC, KC, scratch_elems / slab, dy_route::kNoGridCap);
+  const long splits = plan.splits, range = plan.chunk;
   Gather gt;
   gt.ld = x_ld; gt.H = H; gt.W = W; gt.S3 = C3; gt.S1 = C1; gt.K3 = 9 * C3; gt.coff = 0; gt.ones = db ? 1 : 0;
   gt.vec = (C3 % 8 == 0 && C1 % 8 == 0 && dy_aligned16(x, x_ld, es)) ? 1 : 0;

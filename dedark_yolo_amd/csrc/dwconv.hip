@@ -364,14 +364,14 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_kernel(const T* __res
   }
 }
 
-// pass 2: dw[e] = sum_b part[b][e] in block order
-__global__ __launch_bounds__(DW_THREADS) void dwconv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, long E,
-                                                                         int nparts) {
+// pass 2 of this and of PConv's weight gradient (dy_sum_partials): out[e] = sum_k part[k][e] in index order
+__global__ __launch_bounds__(DW_THREADS) void sum_partials_kernel(const float* __restrict__ part, float* __restrict__ out, long E,
+                                                                  int nparts) {
   const long e = (long)blockIdx.x * DW_THREADS + threadIdx.x;
   if (e >= E) return;
   float s = 0.f;
   for (int k = 0; k < nparts; ++k) s += part[(long)k * E + e];
-  dw[e] = s;
+  out[e] = s;
 }
 
 // exact-bounds strided copy / add of pixels x C lanes (the twin of dy_copy2d for views that are not vector-aligned)
@@ -388,36 +388,6 @@ __global__ __launch_bounds__(DW_THREADS) void copy2d_exact_kernel(const T* __res
 }
 
 // ---- host side
-int check_xview(const char* who, const void* p, long ld, int C, int dtype) {       // dy_check_view without the vector demands
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(ld >= C, "%s: pixel stride %ld < C=%d", who, ld, C);
-  DY_CHECK(((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: misaligned pointer", who);
-  return 0;
-}
-
-// widest access (in bytes: 16, 8 or 0 = one element) that pointer, pixel stride and channel count allow
-int view_bytes(const void* p, long ld, int C, int es) {
-  const uintptr_t a = (uintptr_t)p;
-  const long lb = ld * es, cb = (long)C * es;
-  if (a % 16 == 0 && lb % 16 == 0 && cb % 16 == 0) return 16;
-  if (a % 8 == 0 && lb % 8 == 0 && cb % 8 == 0) return 8;
-  return 0;
-}
-
-// Do the C lanes of a source view (sp pixels) and of a destination view (dp pixels) share a byte?  A thread reads a halo that other
-// threads write, so any overlap races.  Views whose extents are disjoint cannot; inside one buffer (equal pixel strides) the lane
-// ranges [0, C) are compared modulo the pixel stride; intersecting extents with different pixel strides are refused outright.
-bool views_overlap(const void* src, long s_ld, long sp, const void* dst, long d_ld, long dp, int C, int es) {
-  const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
-  const uintptr_t cb = (uintptr_t)C * es;
-  const uintptr_t s1 = s0 + (uintptr_t)(sp - 1) * s_ld * es + cb, d1 = d0 + (uintptr_t)(dp - 1) * d_ld * es + cb;
-  if (s1 <= d0 || d1 <= s0) return false;
-  if (s_ld != d_ld) return true;
-  const uintptr_t row = (uintptr_t)s_ld * es;
-  const uintptr_t off = d0 >= s0 ? (d0 - s0) % row : (row - (s0 - d0) % row) % row;
-  return off < cb || row - off < cb;
-}
-
 int pow2_ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -507,10 +477,8 @@ int launch_wg(const void* x, long x_ld, const void* dz, long dz_ld, float* dw, c
     dwconv_wgrad_kernel<T, V, K, 2><<<grid, DW_THREADS, 0, st>>>((const T*)x, x_ld, (const T*)dz, dz_ld, scratch, g.N, g.H, g.W, g.Ho,
                                                                   g.Wo, g.C, cbv, groups);
   DY_LAUNCH_CHECK();
-  dwconv_wgrad_reduce_kernel<<<(unsigned)((E + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, st>>>(scratch, dw, E, (int)nparts);
   dy_note_kernel("dwconv_wgrad_kernel");
-  DY_LAUNCH_CHECK();
-  return 0;
+  return dy_sum_partials(scratch, (int)nparts, E, dw, st);
 }
 
 // the K*K*V partial sums of a thread stay in registers: V <= 8 for k = 3 (72), 4 for k = 5 (100), 2 for k = 7 (98)
@@ -537,23 +505,29 @@ int launch_wgrad(const void* x, long x_ld, const void* dz, long dz_ld, float* dw
 
 }  // namespace
 
+int dy_sum_partials(const float* part, int nparts, long E, float* out, hipStream_t stream) {
+  sum_partials_kernel<<<(unsigned)((E + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, stream>>>(part, out, E, nparts);
+  DY_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int dy_dwconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* w, int N, int H, int W, int C, int k,
                              int stride, const float* scale, const float* shift, int act, double* stats, int stats_c, int dtype,
                              void* stream) {
   DwGeom g{k, stride, N, H, W, 0, 0, C};
   if (int e = check_geom("dy_dwconv_fwd", g, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_fwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_fwd(y)", y, y_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_fwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_fwd(y)", y, y_ld, C, dtype)) return e;
   DY_CHECK(w != nullptr, "dy_dwconv_fwd: null weight");
-  DY_CHECK(!views_overlap(x, x_ld, (long)N * H * W, y, y_ld, (long)N * ((H + 2 * (k / 2) - k) / stride + 1) * ((W + 2 * (k / 2) - k) / stride + 1),
-                          C, dy_elem_size(dtype)),
+  DY_CHECK(!dy_views_overlap(x, x_ld, (long)N * H * W, C, y, y_ld,
+                             (long)N * ((H + 2 * (k / 2) - k) / stride + 1) * ((W + 2 * (k / 2) - k) / stride + 1), C, dy_elem_size(dtype)),
            "dy_dwconv_fwd: the lanes of x and y overlap (in-place or misplaced slices)");
   DY_CHECK(act == DY_ACT_NONE || act == DY_ACT_SILU || act == DY_ACT_LEAKY, "dy_dwconv_fwd: bad act %d", act);
   DY_CHECK(stats == nullptr || (scale == nullptr && shift == nullptr && act == DY_ACT_NONE && stats_c >= C),
            "dy_dwconv_fwd: the statistics mode writes the raw output (no scale / shift / act) and needs stats_c >= C");
   const int es = dy_elem_size(dtype);
-  int bytes = view_bytes(x, x_ld, C, es);
-  const int by = view_bytes(y, y_ld, C, es);
+  int bytes = dy_view_bytes(x, x_ld, C, es);
+  const int by = dy_view_bytes(y, y_ld, C, es);
   if (by < bytes) bytes = by;
   DwArgs a{};
   a.src = x, a.src_ld = x_ld, a.dst = y, a.dst_ld = y_ld, a.w = w;
@@ -568,17 +542,17 @@ extern "C" int dy_dwconv_dgrad(const void* dz, int64_t dz_ld, void* dx, int64_t 
                                int stride, int accumulate, const void* add_src, int64_t add_ld, int dtype, void* stream) {
   DwGeom g{k, stride, N, H, W, 0, 0, C};
   if (int e = check_geom("dy_dwconv_dgrad", g, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_dgrad(dz)", dz, dz_ld, C, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_dgrad(dx)", dx, dx_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_dgrad(dz)", dz, dz_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_dgrad(dx)", dx, dx_ld, C, dtype)) return e;
   if (add_src)
-    if (int e = check_xview("dy_dwconv_dgrad(add_src)", add_src, add_ld, C, dtype)) return e;
+    if (int e = dy_check_lanes("dy_dwconv_dgrad(add_src)", add_src, add_ld, C, dtype)) return e;
   DY_CHECK(w != nullptr, "dy_dwconv_dgrad: null weight");
-  DY_CHECK(!views_overlap(dz, dz_ld, (long)N * ((H + 2 * (k / 2) - k) / stride + 1) * ((W + 2 * (k / 2) - k) / stride + 1), dx, dx_ld,
-                          (long)N * H * W, C, dy_elem_size(dtype)),
+  DY_CHECK(!dy_views_overlap(dz, dz_ld, (long)N * ((H + 2 * (k / 2) - k) / stride + 1) * ((W + 2 * (k / 2) - k) / stride + 1), C, dx,
+                             dx_ld, (long)N * H * W, C, dy_elem_size(dtype)),
            "dy_dwconv_dgrad: the lanes of dz and dx overlap (in-place or misplaced slices)");
   const int es = dy_elem_size(dtype);
-  int bytes = view_bytes(dz, dz_ld, C, es);
-  const int b1 = view_bytes(dx, dx_ld, C, es), b2 = add_src ? view_bytes(add_src, add_ld, C, es) : 16;
+  int bytes = dy_view_bytes(dz, dz_ld, C, es);
+  const int b1 = dy_view_bytes(dx, dx_ld, C, es), b2 = add_src ? dy_view_bytes(add_src, add_ld, C, es) : 16;
   if (b1 < bytes) bytes = b1;
   if (b2 < bytes) bytes = b2;
   DwArgs a{};
@@ -596,12 +570,12 @@ extern "C" int dy_dwconv_wgrad(const void* x, int64_t x_ld, const void* dz, int6
                                int stride, float* scratch, int64_t scratch_elems, int dtype, void* stream) {
   DwGeom g{k, stride, N, H, W, (H + 2 * (k / 2) - k) / stride + 1, (W + 2 * (k / 2) - k) / stride + 1, C};
   if (int e = check_geom("dy_dwconv_wgrad", g, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_wgrad(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check_xview("dy_dwconv_wgrad(dz)", dz, dz_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_wgrad(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_dwconv_wgrad(dz)", dz, dz_ld, C, dtype)) return e;
   DY_CHECK(dw != nullptr && scratch != nullptr, "dy_dwconv_wgrad: null dw / scratch");
   const int es = dy_elem_size(dtype);
-  int bytes = view_bytes(x, x_ld, C, es);
-  const int b1 = view_bytes(dz, dz_ld, C, es);
+  int bytes = dy_view_bytes(x, x_ld, C, es);
+  const int b1 = dy_view_bytes(dz, dz_ld, C, es);
   if (b1 < bytes) bytes = b1;
   int r = 0;
   DY_DISPATCH_DTYPE("dy_dwconv_wgrad", dtype, r = launch_wgrad<T>(x, x_ld, dz, dz_ld, dw, g, bytes, scratch, scratch_elems, (hipStream_t)stream));
@@ -612,8 +586,8 @@ extern "C" int dy_copy2d_exact(const void* src, int64_t src_ld, void* dst, int64
                                int dtype, void* stream) {
   if (int e = dy_check_dtype("dy_copy2d_exact", dtype)) return e;
   DY_CHECK(pixels >= 0 && C >= 1, "dy_copy2d_exact: bad size");
-  if (int e = check_xview("dy_copy2d_exact(src)", src, src_ld, C, dtype)) return e;
-  if (int e = check_xview("dy_copy2d_exact(dst)", dst, dst_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_copy2d_exact(src)", src, src_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_copy2d_exact(dst)", dst, dst_ld, C, dtype)) return e;
   if (pixels == 0) return 0;
   const long total = pixels * C;
   const int blocks = dy_ew_blocks(total, 4096);

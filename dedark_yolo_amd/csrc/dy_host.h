@@ -1,9 +1,11 @@
 // Host-side helpers shared by the C-ABI launchers: the dtype dispatches, the dynamic-LDS limit of the big-tile kernels, the NHWC
-// view check and the small grid / alignment helpers.  Nothing here is device code.
+// view checks and the small grid / alignment helpers.  Nothing here is device code; the pure arithmetic (access width, overlap test,
+// split plan) is dy_plan.h's.
 #pragma once
 #include <initializer_list>
 #include <unordered_set>
 #include "dy_common.h"
+#include "dy_plan.h"
 
 static inline int dy_elem_size(int dtype) { return dtype == DY_F32 ? 4 : 2; }   // bytes per element
 static inline int dy_vec_elems(int dtype) { return dtype == DY_F32 ? 4 : 8; }   // elements per 16-byte vector (DT<T>::VE)
@@ -78,6 +80,15 @@ static inline int dy_check_view(const char* who, const void* p, long ld, int C, 
   return 0;
 }
 
+// the same view for the kernels that touch exactly the lanes [0, C) of every pixel, element by element where they must: any
+// element-aligned channel slice of a wider buffer, no vector demands
+static inline int dy_check_lanes(const char* who, const void* p, long ld, int C, int dtype) {
+  DY_CHECK(p != nullptr, "%s: null pointer", who);
+  if (int e = dy_check_dtype(who, dtype)) return e;
+  DY_CHECK(ld >= C && ((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: bad view (ld=%ld, C=%d)", who, ld, C);
+  return 0;
+}
+
 // rows of ld elements can be read with 16-byte vectors
 static inline bool dy_aligned16(const void* p, long ld, int elem_size) { return ((uintptr_t)p % 16) == 0 && (ld * elem_size) % 16 == 0; }
 
@@ -86,3 +97,6 @@ static inline int dy_ew_blocks(long total, int cap) {
   const long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
+
+// out[e] = sum_k part[k * E + e], k = 0 .. nparts-1 in index order (the second pass of a deterministic weight gradient); dwconv.hip
+int dy_sum_partials(const float* part, int nparts, long E, float* out, hipStream_t stream);

@@ -318,11 +318,10 @@ __global__ __launch_bounds__(NT) void add_pos_kernel(const T* __restrict__ x, lo
   }
 }
 
-// a view of C channels at pixel stride ld: non-null, ld >= C; `vec` is cleared when 16-byte accesses are not possible
+// dy_check_lanes for one more view of the entry; `vec` is cleared when the view does not allow 16-byte accesses
 int check_row_view(const char* who, const void* p, long ld, int C, int dtype, bool* vec) {
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(ld >= C, "%s: ld=%ld below C=%d", who, ld, C);
-  if (C % dy_vec_elems(dtype) || !dy_aligned16(p, ld, dy_elem_size(dtype))) *vec = false;
+  if (int e = dy_check_lanes(who, p, ld, C, dtype)) return e;
+  if (dy_view_bytes(p, ld, C, dy_elem_size(dtype)) != 16) *vec = false;
   return 0;
 }
 

@@ -9,7 +9,8 @@
 // Channel bounds are exact: c3 and C need not be vector multiples, a view may be a channel slice of a wider buffer whose
 // neighbouring lanes hold live data, so no kernel here reads a source lane outside [0, C) (the conv part reads only [0, c3)) or
 // writes a destination lane outside [0, C).  That is why PConv is not "existing conv on the slice + copy": the tiled convs read
-// and write whole 16-byte vectors (ops.padded_channels).
+// and write whole 16-byte vectors (ops.padded_channels).  Source and destination may be slices of one buffer as long as their lanes do not
+// overlap: a thread reads the halo that other threads write, so overlapping views are refused (dy_views_overlap).
 //
 // VALU route (fp32, c3 < 16): one thread per pixel keeps COB output-channel accumulators, each input value is loaded once and feeds COB FMAs against weights that
 // sit in LDS as f32 (the whole [9][c3][COB] slab of the block's output-channel group; ds_read_b128, one address per wave = a
@@ -159,16 +160,6 @@ __global__ __launch_bounds__(PC_THREADS) void pconv_wgrad_kernel(const T* __rest
     const int co = co0 + j;
     if (co < c3) out[((long)co * c3 + ci) * 9 + tap] = acc[j];
   }
-}
-
-// pass 2: dw[e] = sum_k part[k][e] in chunk order
-__global__ __launch_bounds__(PC_THREADS) void pconv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, long E,
-                                                                        int nchunks) {
-  const long e = (long)blockIdx.x * PC_THREADS + threadIdx.x;
-  if (e >= E) return;
-  float s = 0.f;
-  for (int k = 0; k < nchunks; ++k) s += part[(long)k * E + e];
-  dw[e] = s;
 }
 
 // ---- 16-bit route, c3 >= 16: implicit GEMM on v_mfma_f32_16x16x32_{bf16,f16}.  A = packed weights (16 output channels x 32 input
@@ -348,13 +339,6 @@ int pconv_cob(int c3) {                     // output channels per block: the sm
   return 9 * c3 * 32 * 4 <= PC_LDS_MAX ? 32 : (9 * c3 * 16 * 4 <= PC_LDS_MAX ? 16 : 8);
 }
 
-int check_pview(const char* who, const void* p, long ld, int C, int dtype) {
-  DY_CHECK(p != nullptr, "%s: null pointer", who);
-  DY_CHECK(ld >= C, "%s: pixel stride %ld < C=%d", who, ld, C);
-  DY_CHECK(((uintptr_t)p) % dy_elem_size(dtype) == 0, "%s: misaligned pointer", who);
-  return 0;
-}
-
 template <typename T>
 int launch_conv(const void* src, long src_ld, void* dst, long dst_ld, const float* w, int transposed, long pixels, int H, int W, int C,
                 int c3, int accumulate, const void* add, long add_ld, hipStream_t st) {
@@ -379,23 +363,18 @@ int launch_wgrad(const void* x, long x_ld, const void* dy, long dy_ld, float* dw
   const long E = 9L * c3 * c3;
   const int cob = c3 <= 8 ? 8 : 16;
   const int nslices = (9 * c3 + PC_THREADS - 1) / PC_THREADS, ngroups = (c3 + cob - 1) / cob;
-  long nchunks = (pixels + 2047) / 2048;                 // >= 2048 pixels of work per thread block
-  const long cap = scratch_elems / E;
-  if (nchunks > 512) nchunks = 512;
-  if (nchunks > cap) nchunks = cap;
-  DY_CHECK(nchunks >= 1, "dy_pconv_wgrad: scratch of %ld floats < one partial of %ld", scratch_elems, E);
-  const long chunk = (pixels + nchunks - 1) / nchunks;
-  nchunks = (pixels + chunk - 1) / chunk;
+  DY_CHECK(scratch_elems >= E, "dy_pconv_wgrad: scratch of %ld floats < one partial of %ld", scratch_elems, E);
+  // >= 2048 pixels of work per thread block, at most 512 chunks
+  const dy_route::WgradSplits plan = dy_route::plan_wgrad_splits(pixels, 512, 2048, 1, scratch_elems / E, dy_route::kNoGridCap);
+  const long nchunks = plan.splits, chunk = plan.chunk;
   dim3 grid((unsigned)(nslices * ngroups), (unsigned)nchunks);
   if (cob == 8)
     pconv_wgrad_kernel<T, 8><<<grid, PC_THREADS, 0, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, scratch, pixels, H, W, c3, chunk);
   else
     pconv_wgrad_kernel<T, 16><<<grid, PC_THREADS, 0, st>>>((const T*)x, x_ld, (const T*)dy, dy_ld, scratch, pixels, H, W, c3, chunk);
   DY_LAUNCH_CHECK();
-  pconv_wgrad_reduce_kernel<<<(unsigned)((E + PC_THREADS - 1) / PC_THREADS), PC_THREADS, 0, st>>>(scratch, dw, E, (int)nchunks);
   dy_note_kernel(cob == 8 ? "pconv_wgrad_kernel<COB=8>" : "pconv_wgrad_kernel<COB=16>");
-  DY_LAUNCH_CHECK();
-  return 0;
+  return dy_sum_partials(scratch, (int)nchunks, E, dw, st);
 }
 
 int check_common(const char* who, int N, int H, int W, int C, int c3, int dtype) {
@@ -414,26 +393,28 @@ extern "C" int dy_pconv_pack(const float* w, void* wp, int c3, int transposed, i
   const int KC = (c3 + 31) / 32, NT = (c3 + 15) / 16;
   const long total = 9L * KC * NT * 512;
   const unsigned blocks = (unsigned)((total + PC_THREADS - 1) / PC_THREADS);
-  if (dtype == DY_BF16)
-    pconv_pack_kernel<bf16_t><<<blocks, PC_THREADS, 0, (hipStream_t)stream>>>(w, (bf16_t*)wp, c3, KC, NT, transposed ? 1 : 0);
-  else
-    pconv_pack_kernel<f16_t><<<blocks, PC_THREADS, 0, (hipStream_t)stream>>>(w, (f16_t*)wp, c3, KC, NT, transposed ? 1 : 0);
   dy_note_kernel("pconv_pack_kernel");
-  DY_LAUNCH_CHECK();
-  return 0;
+  return dy_dispatch_16bit("dy_pconv_pack", dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    pconv_pack_kernel<T><<<blocks, PC_THREADS, 0, (hipStream_t)stream>>>(w, (T*)wp, c3, KC, NT, transposed ? 1 : 0);
+    DY_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int dy_pconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* w, const void* wp, int N, int H, int W,
                             int C, int c3, int dtype, void* stream) {
   if (int e = check_common("dy_pconv_fwd", N, H, W, C, c3, dtype)) return e;
-  if (int e = check_pview("dy_pconv_fwd(x)", x, x_ld, C, dtype)) return e;
-  if (int e = check_pview("dy_pconv_fwd(y)", y, y_ld, C, dtype)) return e;
-  DY_CHECK(w != nullptr && x != y, "dy_pconv_fwd: null weight or in-place call");
-  if (use_mfma(c3, dtype)) {
-    DY_CHECK(wp != nullptr, "dy_pconv_fwd: 16-bit c3=%d needs the packed weights of dy_pconv_pack", c3);
-    return dtype == DY_BF16 ? launch_mfma<bf16_t>(x, x_ld, y, y_ld, wp, N, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream)
-                            : launch_mfma<f16_t>(x, x_ld, y, y_ld, wp, N, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream);
-  }
+  if (int e = dy_check_lanes("dy_pconv_fwd(x)", x, x_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_pconv_fwd(y)", y, y_ld, C, dtype)) return e;
+  DY_CHECK(w != nullptr, "dy_pconv_fwd: null weight");
+  DY_CHECK(!use_mfma(c3, dtype) || wp != nullptr, "dy_pconv_fwd: 16-bit c3=%d needs the packed weights of dy_pconv_pack", c3);
+  DY_CHECK(!dy_views_overlap(x, x_ld, (long)N * H * W, C, y, y_ld, (long)N * H * W, C, dy_elem_size(dtype)),
+           "dy_pconv_fwd: the lanes of x and y overlap (in-place or misplaced slices)");
+  if (use_mfma(c3, dtype))
+    return dy_dispatch_16bit("dy_pconv_fwd", dtype, [&](auto tag) {
+      return launch_mfma<typename decltype(tag)::type>(x, x_ld, y, y_ld, wp, N, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream);
+    });
   int r = 0;
   DY_DISPATCH_DTYPE("dy_pconv_fwd", dtype,
                     r = launch_conv<T>(x, x_ld, y, y_ld, w, 0, (long)N * H * W, H, W, C, c3, 0, nullptr, 0, (hipStream_t)stream));
@@ -443,16 +424,19 @@ extern "C" int dy_pconv_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, 
 extern "C" int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t dx_ld, const float* w, const void* wp, int N, int H,
                               int W, int C, int c3, int accumulate, const void* add_src, int64_t add_ld, int dtype, void* stream) {
   if (int e = check_common("dy_pconv_dgrad", N, H, W, C, c3, dtype)) return e;
-  if (int e = check_pview("dy_pconv_dgrad(dy)", dy, dy_ld, C, dtype)) return e;
-  if (int e = check_pview("dy_pconv_dgrad(dx)", dx, dx_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_pconv_dgrad(dy)", dy, dy_ld, C, dtype)) return e;
+  if (int e = dy_check_lanes("dy_pconv_dgrad(dx)", dx, dx_ld, C, dtype)) return e;
   if (add_src)
-    if (int e = check_pview("dy_pconv_dgrad(add_src)", add_src, add_ld, C, dtype)) return e;
-  DY_CHECK(w != nullptr && dy != dx, "dy_pconv_dgrad: null weight or in-place call");
-  if (use_mfma(c3, dtype)) {
-    DY_CHECK(wp != nullptr, "dy_pconv_dgrad: 16-bit c3=%d needs the transposed packed weights of dy_pconv_pack", c3);
-    return dtype == DY_BF16 ? launch_mfma<bf16_t>(dy, dy_ld, dx, dx_ld, wp, N, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld, (hipStream_t)stream)
-                            : launch_mfma<f16_t>(dy, dy_ld, dx, dx_ld, wp, N, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld, (hipStream_t)stream);
-  }
+    if (int e = dy_check_lanes("dy_pconv_dgrad(add_src)", add_src, add_ld, C, dtype)) return e;
+  DY_CHECK(w != nullptr, "dy_pconv_dgrad: null weight");
+  DY_CHECK(!use_mfma(c3, dtype) || wp != nullptr, "dy_pconv_dgrad: 16-bit c3=%d needs the transposed packed weights of dy_pconv_pack", c3);
+  DY_CHECK(!dy_views_overlap(dy, dy_ld, (long)N * H * W, C, dx, dx_ld, (long)N * H * W, C, dy_elem_size(dtype)),
+           "dy_pconv_dgrad: the lanes of dy and dx overlap (in-place or misplaced slices)");
+  if (use_mfma(c3, dtype))
+    return dy_dispatch_16bit("dy_pconv_dgrad", dtype, [&](auto tag) {
+      return launch_mfma<typename decltype(tag)::type>(dy, dy_ld, dx, dx_ld, wp, N, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld,
+                                                       (hipStream_t)stream);
+    });
   int r = 0;
   DY_DISPATCH_DTYPE("dy_pconv_dgrad", dtype,
                     r = launch_conv<T>(dy, dy_ld, dx, dx_ld, w, 1, (long)N * H * W, H, W, C, c3, accumulate ? 1 : 0, add_src, add_ld,
@@ -463,8 +447,8 @@ extern "C" int dy_pconv_dgrad(const void* dy, int64_t dy_ld, void* dx, int64_t d
 extern "C" int dy_pconv_wgrad(const void* x, int64_t x_ld, const void* dy, int64_t dy_ld, float* dw, int N, int H, int W, int c3,
                               float* scratch, int64_t scratch_elems, int dtype, void* stream) {
   if (int e = check_common("dy_pconv_wgrad", N, H, W, c3, c3, dtype)) return e;
-  if (int e = check_pview("dy_pconv_wgrad(x)", x, x_ld, c3, dtype)) return e;
-  if (int e = check_pview("dy_pconv_wgrad(dy)", dy, dy_ld, c3, dtype)) return e;
+  if (int e = dy_check_lanes("dy_pconv_wgrad(x)", x, x_ld, c3, dtype)) return e;
+  if (int e = dy_check_lanes("dy_pconv_wgrad(dy)", dy, dy_ld, c3, dtype)) return e;
   DY_CHECK(dw != nullptr && scratch != nullptr, "dy_pconv_wgrad: null dw / scratch");
   int r = 0;
   DY_DISPATCH_DTYPE("dy_pconv_wgrad", dtype,

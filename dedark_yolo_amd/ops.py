@@ -265,6 +265,20 @@ def _pack(weight, cout_pad, cin_pad, transposed, dtype):
     return out
 
 
+def _packed_image(owner, slot, key, tag, numel, dtype, fill, *args):
+    """The packed operand image `key` that the parameter `owner` keeps under owner.__dict__[slot]: built by fill(out, *args) at its
+    first use and re-packed into the same storage whenever `tag` is not the one it was packed for (optimizer step,
+    load_state_dict, an in-place update).  The hit is the per-call path of small layers: no closure, one dict lookup each."""
+    cache = owner.__dict__.get(slot)
+    hit = None if cache is None else cache.get(key)
+    if hit is not None and hit[0] == tag:
+        return hit[1]
+    out = hit[1] if hit is not None else torch.empty(numel, dtype=dtype, device=owner.device)
+    fill(out, *args)
+    owner.__dict__.setdefault(slot, {})[key] = (tag, out)
+    return out
+
+
 _extra_pack_views = []      # weakrefs of persistent weight VIEWS (fully connected layers run as convs) that PackPlan re-packs too
 
 
@@ -967,21 +981,27 @@ def _nhwc_like(B, Cc, H, W, dtype, device):
     return zeros_nhwc(B, Cp, H, W, dtype, device)[:, :Cc]
 
 
+def _dx_dest(op, dx_out, accumulate, add_src, shape, dtype, alloc):
+    """Where the data gradient of `op` goes: (dx, accumulate).  Without dx_out a fresh alloc(), which there is nothing to accumulate
+    onto; dx_out and add_src are NHWC views of the input's shape and dtype."""
+    for name, t in (("dx_out", dx_out), ("add_src", add_src)):
+        if t is not None and (tuple(t.shape) != tuple(shape) or t.dtype != dtype):
+            raise RuntimeError(f"{op}: {name} must be an NHWC view of the input's shape and dtype")
+    return (alloc(), False) if dx_out is None else (dx_out, accumulate)
+
+
 def _pconv_packed(weight, w32, transposed, dtype):
     """MFMA operand image of a PConv weight for the 16-bit route (dy_pconv_pack; None where the VALU route runs), cached on the
     parameter and re-packed when the weights changed (optimizer step, load_state_dict)."""
     c3 = weight.shape[0]
     if dtype == torch.float32 or c3 < 16:
         return None
-    cache = weight.__dict__.setdefault("_dy_pconv_pack", {})
-    key, tag = (bool(transposed), dtype), (_weights_epoch, weight._version, weight.data_ptr())
-    hit = cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    out = hit[1] if hit is not None else torch.empty(9 * ((c3 + 31) // 32) * ((c3 + 15) // 16) * 512, dtype=dtype, device=weight.device)
-    call("dy_pconv_pack", ptr(w32), ptr(out), c3, 1 if transposed else 0, dt_id(dtype), stream())
-    cache[key] = (tag, out)
-    return out
+    return _packed_image(weight, "_dy_pconv_pack", (bool(transposed), dtype), (_weights_epoch, weight._version, weight.data_ptr()),
+                         9 * ((c3 + 31) // 32) * ((c3 + 15) // 16) * 512, dtype, _pconv_pack, w32, c3, transposed)
+
+
+def _pconv_pack(out, w32, c3, transposed):
+    call("dy_pconv_pack", ptr(w32), ptr(out), c3, 1 if transposed else 0, dt_id(out.dtype), stream())
 
 
 def pconv_forward(tape, x, weight, out=None):
@@ -1022,12 +1042,8 @@ def pconv_backward(tape, dy, dx_out=None, accumulate=False, add_src=None):
         call("dy_pconv_wgrad", ptr(x), ld_of(x), ptr(dy), ld_of(dy), ptr(gw), B, H, W, c3, ptr(scratch), scratch.numel(), dt_id(dtype), st)
         if not direct:
             _add_pgrad(tape, weight, gw)
-    if dx_out is None:
-        dx, accumulate = _nhwc_like(B, Cc, H, W, dtype, dev), False
-    else:
-        dx = dx_out
-    if add_src is not None and (tuple(add_src.shape) != (B, Cc, H, W) or add_src.dtype != dtype):
-        raise RuntimeError("pconv_backward: add_src must be an NHWC view of dx's shape and dtype")
+    dx, accumulate = _dx_dest("pconv_backward", dx_out, accumulate, add_src, (B, Cc, H, W), dtype,
+                              lambda: _nhwc_like(B, Cc, H, W, dtype, dev))
     w32 = _w32(weight)
     n_rw = 2 + (1 if accumulate else 0) + (1 if add_src is not None else 0)
     _C._prof is not None and _C.set_meta(kind="pconv_dgrad", shape=f"{c3}/{Cc} k3 in {B}x{H}x{W}", dtype=str(dtype),
@@ -1045,17 +1061,14 @@ def _cru_packed(w3, w1, G, transposed, dtype):
     changed (optimizer step, load_state_dict)."""
     GN, C1 = w1.shape[0], w1.shape[1]
     C3 = 0 if w3 is None else w3.shape[1]
-    cache = w1.__dict__.setdefault("_dy_cru_pack", {})
-    key = (bool(transposed), dtype)
     tag = (_weights_epoch, w1._version, w1.data_ptr(), None if w3 is None else (w3._version, w3.data_ptr()))
-    hit = cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    out = hit[1] if hit is not None else torch.empty(GN * (9 * C3 + C1), dtype=dtype, device=w1.device)
-    call("dy_cru_conv_pack", None if w3 is None else ptr(_w32(w3)), ptr(_w32(w1)), ptr(out), G, GN // G, C3, C1, 1 if transposed else 0,
-         dt_id(dtype), stream())
-    cache[key] = (tag, out)
-    return out
+    return _packed_image(w1, "_dy_cru_pack", (bool(transposed), dtype), tag, GN * (9 * C3 + C1), dtype, _cru_pack, w3, w1, G, transposed)
+
+
+def _cru_pack(out, w3, w1, G, transposed):
+    GN, C1 = w1.shape[0], w1.shape[1]
+    call("dy_cru_conv_pack", None if w3 is None else ptr(_w32(w3)), ptr(_w32(w1)), ptr(out), G, GN // G, 0 if w3 is None else w3.shape[1], C1,
+         1 if transposed else 0, dt_id(out.dtype), stream())
 
 
 def _cru_dims(x, w3, bias, w1, G):
@@ -1114,12 +1127,8 @@ def cru_conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False):
                 _add_pgrad(tape, p, g)
     if not need_dx:
         return None
-    if dx_out is None:
-        dx, accumulate = empty_nhwc(B, C1, H, W, dtype, dev), False
-    else:
-        dx = dx_out
-        if tuple(dx.shape) != (B, C1, H, W) or dx.dtype != dtype:
-            raise RuntimeError("cru_conv_backward: dx_out must be an NHWC view of the input's shape and dtype")
+    dx, accumulate = _dx_dest("cru_conv_backward", dx_out, accumulate, None, (B, C1, H, W), dtype,
+                              lambda: empty_nhwc(B, C1, H, W, dtype, dev))
     wp = _cru_packed(w3, w1, G, True, dtype)
     _C._prof is not None and _C.set_meta(kind="cru_dgrad", shape=f"{G}x{N} <- 9x{C3}+{C1} in {B}x{H}x{W}", dtype=str(dtype),
                                          flops=2.0 * B * H * W * G * N * (9 * C3 + C1),
@@ -1417,14 +1426,8 @@ def dwconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_s
             _add_pgrad(tape, ctx.weight, gw)
     if not need_dx:
         return None
-    if dx_out is None:
-        dx, accumulate = _nhwc_like(B, Cc, H, W, dtype, dev), False
-    else:
-        dx = dx_out
-        if tuple(dx.shape) != (B, Cc, H, W) or dx.dtype != dtype:
-            raise RuntimeError("dwconv_backward: dx_out does not match the input")
-    if add_src is not None and (tuple(add_src.shape) != (B, Cc, H, W) or add_src.dtype != dtype):
-        raise RuntimeError("dwconv_backward: add_src must be an NHWC view of dx's shape and dtype")
+    dx, accumulate = _dx_dest("dwconv_backward", dx_out, accumulate, add_src, (B, Cc, H, W), dtype,
+                              lambda: _nhwc_like(B, Cc, H, W, dtype, dev))
     n_rw = 1 + (1 if accumulate else 0) + (1 if add_src is not None else 0)
     _C._prof is not None and _C.set_meta(kind="dwconv_dgrad", shape=shape, dtype=str(dtype), flops=flops,
                                          bytes=float((n_rw * B * H * W + pixels) * Cc * es + Cc * k * k * 4))

@@ -151,6 +151,30 @@ def test_pconv_rejects_bad_arguments():
     xb = x.to(torch.bfloat16)
     with pytest.raises(RuntimeError, match="packed weights"):          # the 16-bit route has no silent fallback
         _C.call("dy_pconv_fwd", xb.data_ptr(), 600, xb.data_ptr() + 16, 600, w.data_ptr(), None, 1, 8, 8, 600, 32, 1, ops.stream())
+    # source and destination lanes that overlap inside one buffer (in place, or halves cut 4 lanes too close) are refused and launch
+    # nothing: a thread reads the 3x3 halo that other threads write.  Sibling halves are fine.
+    buf = rnd(21, 1, 8, 8, 16, lo=-1, hi=1).cuda()
+    w2 = (rnd(22, 2, 2, 3, 3, lo=-1, hi=1) / 4.0).cuda()
+    a, b_, c = buf[..., :8], buf[..., 4:12], buf[..., 8:]
+    for dst in (a, b_):
+        for name, tail in (("dy_pconv_fwd", (0,)), ("dy_pconv_dgrad", (0, None, 0, 0))):
+            src, dst_ = (a, dst) if name == "dy_pconv_fwd" else (dst, a)
+            _C.lib().dy_clear_last_kernel()
+            with pytest.raises(RuntimeError, match="overlap"):
+                _C.call(name, src.data_ptr(), 16, dst_.data_ptr(), 16, w2.data_ptr(), None, 1, 8, 8, 8, 2, *tail, ops.stream())
+            assert _C.lib().dy_last_kernel().decode() == ""
+    xa = a.permute(0, 3, 1, 2).double()
+    want = torch.cat([F.conv2d(xa[:, :2], w2.double(), padding=1), xa[:, 2:]], 1)
+    assert _call("dy_pconv_fwd", a.data_ptr(), 16, c.data_ptr(), 16, w2.data_ptr(), None, 1, 8, 8, 8, 2, 0).startswith("pconv_kernel<")
+    torch.cuda.synchronize()
+    _check(c.permute(0, 3, 1, 2), want, torch.float32, "fwd into the sibling half")
+    assert torch.equal(a.permute(0, 3, 1, 2).double(), xa)
+    g = c.permute(0, 3, 1, 2).double()
+    want = torch.cat([torch.nn.grad.conv2d_input((1, 2, 8, 8), w2.double(), g[:, :2], padding=1), g[:, 2:]], 1)
+    _call("dy_pconv_dgrad", c.data_ptr(), 16, a.data_ptr(), 16, w2.data_ptr(), None, 1, 8, 8, 8, 2, 0, None, 0, 0)
+    torch.cuda.synchronize()
+    _check(a.permute(0, 3, 1, 2), want, torch.float32, "dgrad into the sibling half")
+    assert torch.equal(c.permute(0, 3, 1, 2).double(), g)
 
 
 @pytest.mark.parametrize("name,cls,args", [("g14_fasterc2f_n_sc", "FasterC2f_N", (32, 32, 2, True)),

@@ -226,6 +226,36 @@ def test_cru_conv_rejects_bad_arguments():
         _C.call("dy_cru_conv_dgrad", x.data_ptr(), 4, wp.data_ptr(), x.data_ptr(), 16, 1, 4, 4, 1, 8, 0, 8, 0, 0, ops.stream())
     with pytest.raises(RuntimeError, match="scratch"):
         _C.call("dy_cru_conv_wgrad", x.data_ptr(), 16, x.data_ptr(), 16, None, None, wp.data_ptr(), 1, 4, 4, 1, 8, 0, 8, wp.data_ptr(), 8, 0, ops.stream())
+    # source and destination lanes that overlap inside one buffer (in place, or halves cut 4 lanes too close) are refused and launch
+    # nothing: a thread reads all channels of a pixel and its 3x3 halo, which other threads write.  Sibling halves are fine.
+    G, N, C3, C1, H, W = 2, 4, 4, 8, 8, 8
+    g = np.random.default_rng(12)
+    buf = sr._randn(g, 1, 16, H, W).permute(0, 2, 3, 1).contiguous().cuda()
+    w3, w1 = sr._randn(g, G * N, C3, 3, 3, scale=0.15), sr._randn(g, G * N, C1, 1, 1, scale=0.15)
+    w3d, w1d = w3.cuda(), w1.cuda()
+    packs = [torch.empty(G * N * (9 * C3 + C1), device="cuda") for _ in range(2)]
+    for tr, pk in enumerate(packs):
+        _call("dy_cru_conv_pack", w3d.data_ptr(), w1d.data_ptr(), pk.data_ptr(), G, N, C3, C1, tr, 0)
+    a, b_, c = buf[..., :8], buf[..., 4:12], buf[..., 8:]
+    for dst in (a, b_):
+        for name, args in (("dy_cru_conv_fwd", (a.data_ptr(), 16, packs[0].data_ptr(), None, dst.data_ptr(), 16, 1, H, W, G, N, C3, C1, 0)),
+                           ("dy_cru_conv_dgrad", (dst.data_ptr(), 16, packs[1].data_ptr(), a.data_ptr(), 16, 1, H, W, G, N, C3, C1, 0, 0))):
+            _C.lib().dy_clear_last_kernel()
+            with pytest.raises(RuntimeError, match="overlap"):
+                _C.call(name, *args, ops.stream())
+            assert _C.lib().dy_last_kernel().decode() == ""
+    x64 = a.permute(0, 3, 1, 2).double().cpu()
+    _call("dy_cru_conv_fwd", a.data_ptr(), 16, packs[0].data_ptr(), None, c.data_ptr(), 16, 1, H, W, G, N, C3, C1, 0)
+    torch.cuda.synchronize()
+    y = c.permute(0, 3, 1, 2).double().cpu()
+    _ratio(y, sc.cru_conv_ref(x64, w3.double(), None, w1.double(), G), sc.cru_conv_fwd_terms(x64, w3.double(), None, w1.double(), G), "f32",
+           "fwd into the sibling half")
+    assert torch.equal(a.permute(0, 3, 1, 2).double().cpu(), x64)
+    _call("dy_cru_conv_dgrad", c.data_ptr(), 16, packs[1].data_ptr(), a.data_ptr(), 16, 1, H, W, G, N, C3, C1, 0, 0)
+    torch.cuda.synchronize()
+    _ratio(a.permute(0, 3, 1, 2).double().cpu(), sc.cru_conv_dgrad_ref(y, w3.double(), w1.double(), G, x64.shape),
+           sc.cru_conv_dgrad_terms(y, w3.double(), w1.double(), G, x64.shape), "f32", "dgrad into the sibling half")
+    assert torch.equal(c.permute(0, 3, 1, 2).double().cpu(), y)
 
 
 # ------------------------------------------------------------------------------------------------ modules
