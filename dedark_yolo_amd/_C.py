@@ -212,7 +212,19 @@ _SIGS = {
     "dy_cls_metrics_update": [vp, i32, vp, i32, i32, vp, vp, vp],
     "dy_val_box_match": [vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp],
     "dy_val_iou_match": [vp, i64, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp],
+    "dy_chan_pool_fwd": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "dy_chan_gate_fwd": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "dy_spatial_stats_fwd": [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp],
+    "dy_spatial_gate_fwd": [vp, i64, vp, i64, vp, vp, vp, i32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "dy_spatial_gate_bwd_px": [vp, i64, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp],
+    "dy_spatial_conv_bwd_workspace": [i32, i32, i32, i32],
+    "dy_spatial_conv_bwd": [vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "dy_cbam_reduce_workspace": [i32, i32, i32, i32],
+    "dy_spatial_gate_bwd_reduce": [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "dy_spatial_gate_bwd_apply": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, vp],
 }
+_I64_RESULT = ("dy_pack_item_blocks", "dy_bn2_act_bwd_workspace", "dy_spatial_conv_bwd_workspace", "dy_cbam_reduce_workspace")
+CBAM_MAX_C = 2048            # DY_CBAM_MAX_C
 
 _lib = None
 
@@ -234,7 +246,7 @@ def lib():
         for name, sig in _SIGS.items():
             fn = getattr(L, name)          # AttributeError if the .so does not export a declared symbol
             fn.argtypes = sig
-            fn.restype = C.c_int64 if name in ("dy_pack_item_blocks", "dy_bn2_act_bwd_workspace") else C.c_int
+            fn.restype = C.c_int64 if name in _I64_RESULT else C.c_int
         _lib = L
     return _lib
 

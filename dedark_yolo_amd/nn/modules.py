@@ -17,7 +17,7 @@ from .. import ops
 from .._C import ACT_LEAKY, ACT_NONE, ACT_SILU, call
 from ..ops import as_nhwc, conv_backward, conv_forward, copy2d, empty_nhwc, ld_of, ptr, stream
 
-__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "RepConv", "RepC3","TransformerLayer", "TransformerBlock", "TransformerEncoderLayer", "AIFI", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
+__all__ = ("Conv", "DWConv", "GhostConv", "GhostBottleneck", "C3", "C3Ghost", "C3TR", "RepConv", "RepC3", "ChannelAttention", "SpatialAttention", "CBAM", "TransformerLayer", "TransformerBlock", "TransformerEncoderLayer", "AIFI", "Concat", "Bottleneck", "C2", "C2f", "PConv", "PconvBottleneck", "PconvBottleneck_n", "FasterC2f", "FasterC2f_N", "SPPF", "Upsample", "AsffTribeLevel", "AsffDoubLevel", "MFRU", "SCConv", "SCConvBottleneck", "SC_PW_Bottleneck", "SC_Conv3_Bottleneck", "Conv3_SC_Bottleneck", "SCC2f", "SC_PW_C2f",
            "SC_Conv3_C2f", "Conv3_SC_C2f", "RFBblock", "DFL", "Detect",
            "AsffDetect", "Proto", "Segment", "Pose", "Classify",
            "lowlight_recovery", "ExtractParameters2", "autopad")
@@ -567,6 +567,106 @@ class RepC3(DyModule):
         if not needs[0]:
             return self.cv1._bwd(tape, g, needs=needs)
         return self.cv1._bwd(tape, g, dx_out=dx, accumulate=True)
+
+
+def _check_attn_channels(who, c):
+    if c % 8 or not 8 <= c <= ops._C.CBAM_MAX_C:
+        raise NotImplementedError(f"{who}: C={c} is outside the attention kernels' rule C % 8 == 0, 8 <= C <= {ops._C.CBAM_MAX_C}")
+
+
+def _spatial_fwd(tape, weight, x, a, out):
+    """y = u s, u = x sigmoid(a) (a None: u = x), s = sigmoid(cv1(mean_c u, max_c u)): one read of x for the planes, one read and one
+    write for the scale; u is never stored.  With a tape the planes (and the argmax channel) stay for the backward."""
+    train = tape is not None
+    planes = ops.spatial_stats_fwd(x, a, want_arg=train)
+    y = ops.spatial_gate_fwd(x, a, planes, weight, out=out, keep_s=train)
+    if train:
+        tape.push((x, a, planes, weight))
+    return y
+
+
+def _spatial_bwd(tape, dy):
+    """the plane half of the backward: pops _spatial_fwd's context, files cv1's weight gradient; -> (x, a, planes with dmean / dmx)"""
+    x, a, planes, weight = tape.pop()
+    dpre = ops.spatial_gate_bwd_px(dy, x, a, planes)
+    ops.spatial_conv_bwd(tape, dpre, planes, weight)
+    return x, a, planes
+
+
+def _chan_bwd(tape, dy, x, a, planes, needs, dx_out, accumulate):
+    """the channel half: da from one reduce pass, the fc's backward (its context is next on the tape), then ONE apply pass that
+    writes dx with the pooled branch's share dp / (H W) already in it"""
+    da = ops.gate_bwd_reduce(dy, x, a, planes)
+    dp = conv_backward(tape, da, need_dx=needs[0])
+    if not needs[0]:
+        return None
+    return ops.gate_bwd_apply(dy, a, planes, dp, dx_out=dx_out, accumulate=accumulate)
+
+
+class ChannelAttention(DyModule):
+    """x * sigmoid(fc(avgpool(x))), fc = Conv2d(C, C, 1, bias=True) (reference ultralytics/nn/modules/conv.py:294-304).  The pool is
+    dy_chan_pool_fwd, the fc a 1x1 conv with bias on the pooled [B, C, 1, 1] map (as Classify's Linear), the scale dy_chan_gate_fwd.
+    `pool` and `act` are containers only (the checkpoint writer names them)."""
+
+    def __init__(self, channels: int) -> None:
+        super().__init__()
+        _check_attn_channels(type(self).__name__, channels)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Conv2d(channels, channels, 1, 1, 0, bias=True)
+        self.act = nn.Sigmoid()
+
+    def _logits(self, tape, x):
+        return plain_conv_fwd(tape, self.fc, ops.chan_pool_fwd(x))
+
+    def _fwd(self, tape, x, out=None):
+        a = self._logits(tape, x)
+        y = ops.chan_gate_fwd(x, a, out=out)
+        if tape is not None:
+            tape.push((x, a))
+        return y
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        x, a = tape.pop()
+        return _chan_bwd(tape, dy, x, a, None, needs, dx_out, accumulate)
+
+
+class SpatialAttention(DyModule):
+    """x * sigmoid(cv1(cat(mean_c x, max_c x))), cv1 = Conv2d(2, 1, k, padding=k // 2, bias=False), k in (3, 7) (reference
+    conv.py:307-320): dy_spatial_stats_fwd + dy_spatial_gate_fwd, no cat and no stored planes beyond [B, H, W] f32 ones."""
+
+    def __init__(self, kernel_size=7):
+        super().__init__()
+        assert kernel_size in (3, 7), 'kernel size must be 3 or 7'
+        padding = 3 if kernel_size == 7 else 1
+        self.cv1 = nn.Conv2d(2, 1, kernel_size, padding=padding, bias=False)
+        self.act = nn.Sigmoid()
+
+    def _fwd(self, tape, x, out=None):
+        return _spatial_fwd(tape, self.cv1.weight, x, None, out)
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        _, _, planes = _spatial_bwd(tape, dy)
+        if not needs[0]:
+            return None
+        return ops.gate_bwd_apply(dy, None, planes, None, dx_out=dx_out, accumulate=accumulate)
+
+
+class CBAM(DyModule):
+    """spatial_attention(channel_attention(x)) (reference conv.py:449-459) without the intermediate map: the channel gate is folded
+    into both spatial kernels (forward 3 reads + 1 write of the map with the pool; backward 5 reads + 1 write)."""
+
+    def __init__(self, c1, kernel_size=7):
+        super().__init__()
+        self.channel_attention = ChannelAttention(c1)
+        self.spatial_attention = SpatialAttention(kernel_size)
+
+    def _fwd(self, tape, x, out=None):
+        a = self.channel_attention._logits(tape, x)
+        return _spatial_fwd(tape, self.spatial_attention.cv1.weight, x, a, out)
+
+    def _bwd(self, tape, dy, needs=(True,), dx_out=None, accumulate=False):
+        x, a, planes = _spatial_bwd(tape, dy)
+        return _chan_bwd(tape, dy, x, a, planes, needs, dx_out, accumulate)
 
 
 _ParamRows = ops._ParamRows

@@ -16,7 +16,7 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from .modules import (AIFI, AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
+from .modules import (AIFI, CBAM, ChannelAttention, SpatialAttention, AsffDetect, AsffDoubLevel, AsffTribeLevel, C2, C2f, C3, C3Ghost, C3TR, Classify, Concat, Conv, Conv3_SC_Bottleneck, Conv3_SC_C2f, DWConv, Detect,
                       DyModule, FasterC2f, FasterC2f_N,
                       GhostBottleneck, GhostConv, MFRU,
                       PconvBottleneck, PconvBottleneck_n, Pose, RFBblock, RepC3, RepConv, SCC2f, SCConvBottleneck, SC_Conv3_Bottleneck, SC_Conv3_C2f, SC_PW_Bottleneck,
@@ -36,6 +36,7 @@ _REGISTRY = dict(Conv=Conv, C2=C2, C2f=C2f, SPPF=SPPF, Concat=Concat, Detect=Det
                  Segment=Segment, Pose=Pose, Classify=Classify,
                  GhostConv=GhostConv, GhostBottleneck=GhostBottleneck, DWConv=DWConv, C3=C3, C3Ghost=C3Ghost, C3TR=C3TR, RepC3=RepC3,
                  AIFI=AIFI, TransformerEncoderLayer=TransformerEncoderLayer,
+                 CBAM=CBAM, ChannelAttention=ChannelAttention, SpatialAttention=SpatialAttention,
                  SCC2f=SCC2f, SC_PW_C2f=SC_PW_C2f, SC_Conv3_C2f=SC_Conv3_C2f, Conv3_SC_C2f=Conv3_SC_C2f, SCConvBottleneck=SCConvBottleneck,
                  SC_PW_Bottleneck=SC_PW_Bottleneck, SC_Conv3_Bottleneck=SC_Conv3_Bottleneck, Conv3_SC_Bottleneck=Conv3_SC_Bottleneck)
 _REGISTRY["nn.Upsample"] = Upsample
@@ -104,6 +105,11 @@ def _rule_aifi(row):                      # tasks.py `elif m is AIFI: args = [ch
     return [row.ch_in[0], *row.args], row.ch_in[0], 1
 
 
+def _rule_attn(row):                      # CBAM, ChannelAttention: [ch_in, *args] (AIFI's form); the reference has no rule for them (its
+    return [row.ch_in[0], *row.args], row.ch_in[0], row.repeats       # tasks.py does not import the names): this one is ours
+
+
+_PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock, SpatialAttention: channels unchanged
 _RULES = {
     Conv: _rule_conv_like, SPPF: _rule_conv_like, C2f: _rule_c2f,
     C2: _rule_c2f, FasterC2f_N: _rule_c2f, FasterC2f: _rule_c2f,                               # tasks.py:743-753
@@ -112,6 +118,7 @@ _RULES = {
     SCC2f: _rule_c2f, SC_PW_C2f: _rule_c2f, SC_Conv3_C2f: _rule_c2f, Conv3_SC_C2f: _rule_c2f,                         # tasks.py:744-752, 857-871
     SCConvBottleneck: _rule_conv_like, SC_PW_Bottleneck: _rule_conv_like, SC_Conv3_Bottleneck: _rule_conv_like, Conv3_SC_Bottleneck: _rule_conv_like,
     AIFI: _rule_aifi,
+    CBAM: _rule_attn, ChannelAttention: _rule_attn, SpatialAttention: _PASS_THROUGH,
     Concat: lambda r: (r.args, sum(r.ch_in), r.repeats),
     lowlight_recovery: lambda r: (r.args, r.args[0], r.repeats),
     AsffTribeLevel: lambda r: (r.args, 512 if r.args[0] in (0, 1) else 256, r.repeats),       # tasks.py:892-896
@@ -123,10 +130,9 @@ _RULES = {
     Pose: lambda r: ([*r.args, list(r.ch_in)], r.ch_in[0], r.repeats),                        # tasks.py:897-898
     Classify: _rule_conv_like,                                                                 # tasks.py:743-753: [c1, nc], nc unscaled
 }
-_PASS_THROUGH = lambda r: (r.args, r.ch_in[0], r.repeats)         # Upsample, RFBblock: channels unchanged
 
 
-_PLACEABLE = (Conv, C2, C2f, C3, RepC3, GhostConv, SPPF, Upsample, TransformerEncoderLayer)      # (TransformerEncoderLayer covers AIFI, C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
+_PLACEABLE = (Conv, C2, C2f, C3, RepC3, GhostConv, SPPF, Upsample, TransformerEncoderLayer, CBAM, ChannelAttention, SpatialAttention)      # (TransformerEncoderLayer covers AIFI, C2f covers FasterC2f / FasterC2f_N / the SCConv C2f family, C3 covers C3Ghost, Conv covers DWConv) top-level modules whose last kernel can write into a caller-provided NHWC view
 
 
 def _out_hw(m, x):

@@ -1318,6 +1318,149 @@ def add_pos(x, pos, out=None):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ channel / spatial attention (csrc/cbam.hip)
+class SpatialPlanes:
+    """The per-pixel planes of one spatial-attention stage, dense f32 [B, H, W] (arg: int32): mean_c / max_c of u = x g, the argmax
+    channel and s = sigmoid(cv1(mean, max)) from the forward; dmean / dmax from spatial_conv_bwd."""
+    __slots__ = ("mean", "mx", "arg", "s", "dmean", "dmx")
+
+    def __init__(self, mean, mx, arg=None, s=None):
+        self.mean, self.mx, self.arg, self.s, self.dmean, self.dmx = mean, mx, arg, s, None, None
+
+
+def _cbam_dims(who, x, a, *like):
+    """(B, H, W, C) of the NHWC view x after the kernels' rule; `a`: the fc's logits [B, C, 1, 1] or None; `like`: views of x's shape"""
+    B, Cc, H, W = x.shape
+    if Cc % 8 or not 8 <= Cc <= _C.CBAM_MAX_C:
+        raise NotImplementedError(f"{who}: C={Cc} is outside the attention kernels' rule C % 8 == 0, 8 <= C <= {_C.CBAM_MAX_C}")
+    if a is not None and (tuple(a.shape) != (B, Cc, 1, 1) or a.dtype != x.dtype):
+        raise RuntimeError(f"{who}: gate logits {tuple(a.shape)} {a.dtype} do not belong to a {tuple(x.shape)} {x.dtype} map")
+    for t in like:
+        if t is not None and (tuple(t.shape) != tuple(x.shape) or t.dtype != x.dtype):
+            raise RuntimeError(f"{who}: views differ in shape or dtype ({tuple(t.shape)} {t.dtype} vs {tuple(x.shape)} {x.dtype})")
+    return B, H, W, Cc
+
+
+def _gate_args(a):
+    return (None, 0) if a is None else (ptr(a), ld_of(a))
+
+
+def _cbam_meta(kind, x, passes):
+    B, Cc, H, W = x.shape
+    _C._prof is not None and _C.set_meta(kind=kind, shape=f"{Cc}ch {B * H * W}px", dtype=str(x.dtype), flops=0.0,
+                                         bytes=float(passes * B * H * W * Cc * x.element_size()))
+
+
+def chan_pool_fwd(x):
+    """AdaptiveAvgPool2d(1) of an NHWC view [B, C, H, W] -> NHWC [B, C, 1, 1] (dy_chan_pool_fwd; reference conv.py:299, 304): the
+    pixels of an image are spread over up to 64 workgroups, partial sums added in a fixed order"""
+    B, H, W, Cc = _cbam_dims("chan_pool_fwd", x, None)
+    y = empty_nhwc(B, Cc, 1, 1, x.dtype, x.device)
+    need = int(_C.lib().dy_cbam_reduce_workspace(B, H * W, Cc, dt_id(x.dtype)))
+    ws = torch.empty(need, dtype=torch.float32, device=x.device)
+    _cbam_meta("chan_pool_fwd", x, 1)
+    call("dy_chan_pool_fwd", ptr(x), ld_of(x), ptr(y), ld_of(y), ptr(ws), need, B, H * W, Cc, dt_id(x.dtype), stream())
+    emu_round(y)
+    return y
+
+
+def chan_gate_fwd(x, a, out=None):
+    """y = x sigmoid(a[b]) (dy_chan_gate_fwd; reference conv.py:302-304): ChannelAttention alone"""
+    B, H, W, Cc = _cbam_dims("chan_gate_fwd", x, a, out)
+    y = out if out is not None else empty_nhwc(B, Cc, H, W, x.dtype, x.device)
+    _cbam_meta("chan_gate_fwd", x, 2)
+    call("dy_chan_gate_fwd", ptr(x), ld_of(x), ptr(a), ld_of(a), ptr(y), ld_of(y), B, H * W, Cc, dt_id(x.dtype), stream())
+    emu_round(y)
+    return y
+
+
+def spatial_stats_fwd(x, a=None, want_arg=False):
+    """mean_c / max_c (and the argmax channel, lowest index on ties) of u = x sigmoid(a[b]) in one read of x, u not stored
+    (dy_spatial_stats_fwd; reference conv.py:320).  a = None: u = x."""
+    B, H, W, Cc = _cbam_dims("spatial_stats_fwd", x, a)
+    mean = torch.empty((2, B, H, W), dtype=torch.float32, device=x.device)
+    arg = torch.empty((B, H, W), dtype=torch.int32, device=x.device) if want_arg else None
+    _cbam_meta("spatial_stats_fwd", x, 1)
+    call("dy_spatial_stats_fwd", ptr(x), ld_of(x), *_gate_args(a), ptr(mean[0]), ptr(mean[1]), ptr(arg), B, H * W, Cc, dt_id(x.dtype), stream())
+    return SpatialPlanes(mean[0], mean[1], arg)
+
+
+def spatial_gate_fwd(x, a, planes, weight, out=None, keep_s=False):
+    """y = x g s, s = sigmoid(cv1(mean, max)) with zero padding k // 2 (dy_spatial_gate_fwd; reference conv.py:320, 458).  weight:
+    cv1.weight [1, 2, k, k]; keep_s: s is stored in `planes` for the backward."""
+    B, H, W, Cc = _cbam_dims("spatial_gate_fwd", x, a, out)
+    k = weight.shape[-1]
+    if tuple(weight.shape) != (1, 2, k, k):
+        raise RuntimeError(f"spatial_gate_fwd: weight {tuple(weight.shape)} is not [1, 2, k, k]")
+    y = out if out is not None else empty_nhwc(B, Cc, H, W, x.dtype, x.device)
+    if keep_s:
+        planes.s = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    _cbam_meta("spatial_gate_fwd", x, 2)
+    call("dy_spatial_gate_fwd", ptr(x), ld_of(x), *_gate_args(a), ptr(planes.mean), ptr(planes.mx), ptr(_w32(weight)), k, ptr(y), ld_of(y),
+         ptr(planes.s) if keep_s else None, B, H, W, Cc, dt_id(x.dtype), stream())
+    emu_round(y)
+    return y
+
+
+def spatial_gate_bwd_px(dy, x, a, planes):
+    """dpre [B, H, W] f32 = s (1 - s) sum_c dy x g (dy_spatial_gate_bwd_px)"""
+    B, H, W, Cc = _cbam_dims("spatial_gate_bwd_px", x, a, dy)
+    dpre = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    _cbam_meta("spatial_gate_bwd_px", x, 2)
+    call("dy_spatial_gate_bwd_px", ptr(dy), ld_of(dy), ptr(x), ld_of(x), *_gate_args(a), ptr(planes.s), ptr(dpre), B, H * W, Cc,
+         dt_id(x.dtype), stream())
+    return dpre
+
+
+def spatial_conv_bwd(tape, dpre, planes, weight):
+    """Backward of cv1 on the planes (dy_spatial_conv_bwd): planes.dmean / planes.dmx = the transposed convolution of dpre, and the
+    weight's gradient (deterministic) goes into its sink."""
+    B, H, W = dpre.shape
+    k, dev = weight.shape[-1], dpre.device
+    dm = torch.empty((2, B, H, W), dtype=torch.float32, device=dev)
+    planes.dmean, planes.dmx = dm[0], dm[1]
+    dw, direct = _grad_sink(weight, tuple(weight.shape), dev)
+    need = int(_C.lib().dy_spatial_conv_bwd_workspace(B, H, W, k))
+    ws = torch.empty(need, dtype=torch.float32, device=dev)
+    call("dy_spatial_conv_bwd", ptr(dpre), ptr(planes.mean), ptr(planes.mx), ptr(_w32(weight)), k, ptr(planes.dmean), ptr(planes.dmx), ptr(dw),
+         ptr(ws), need, B, H, W, stream())
+    if not direct:
+        _add_pgrad(tape, weight, dw)
+
+
+def gate_bwd_reduce(dy, x, a, planes=None):
+    """da [B, C, 1, 1] = g (1 - g) sum_p du x in the compute dtype (dy_spatial_gate_bwd_reduce, deterministic); du = dy s + dmean / C +
+    (c == argmax ? dmax : 0), or dy without `planes` (ChannelAttention alone)"""
+    B, H, W, Cc = _cbam_dims("gate_bwd_reduce", x, a, dy)
+    da = empty_nhwc(B, Cc, 1, 1, x.dtype, x.device)
+    need = int(_C.lib().dy_cbam_reduce_workspace(B, H * W, Cc, dt_id(x.dtype)))
+    ws = torch.empty(need, dtype=torch.float32, device=x.device)
+    p = planes
+    _cbam_meta("gate_bwd_reduce", x, 2)
+    call("dy_spatial_gate_bwd_reduce", ptr(dy), ld_of(dy), ptr(x), ld_of(x), ptr(a), ld_of(a), *(_plane_args(p)), ptr(da), ld_of(da), ptr(ws),
+         need, B, H * W, Cc, dt_id(x.dtype), stream())
+    emu_round(da)
+    return da
+
+
+def _plane_args(p):
+    return (None, None, None, None) if p is None else (ptr(p.s), ptr(p.dmean), ptr(p.dmx), ptr(p.arg))
+
+
+def gate_bwd_apply(dy, a, planes=None, dpool=None, dx_out=None, accumulate=False):
+    """dx = du g + dpool[b] / (H W) (+ dx_out when accumulate) (dy_spatial_gate_bwd_apply); dpool [B, C, 1, 1]: the fc's data gradient,
+    i.e. the pooled branch's share; a = None: g = 1 (SpatialAttention alone)"""
+    B, H, W, Cc = _cbam_dims("gate_bwd_apply", dy, a, dx_out)
+    if dpool is not None and (tuple(dpool.shape) != (B, Cc, 1, 1) or dpool.dtype != dy.dtype):
+        raise RuntimeError("gate_bwd_apply: dpool does not belong to the map")
+    dx = dx_out if dx_out is not None else empty_nhwc(B, Cc, H, W, dy.dtype, dy.device)
+    _cbam_meta("gate_bwd_apply", dy, 3 if (accumulate and dx_out is not None) else 2)
+    call("dy_spatial_gate_bwd_apply", ptr(dy), ld_of(dy), *_gate_args(a), *_plane_args(planes), *_gate_args(dpool), ptr(dx), ld_of(dx),
+         1 if (accumulate and dx_out is not None) else 0, B, H * W, Cc, dt_id(dy.dtype), stream())
+    emu_round(dx)
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ depthwise conv
 def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, training=False, out=None):
     """y = act(bn(dwconv(x) [+ bias])) for a depthwise conv (weight [C, 1, k, k], pad k // 2), the contract of conv_forward.

@@ -247,6 +247,7 @@ _REF_HOME.update({"C3TR": "ultralytics.nn.modules.block", "TransformerLayer": "u
                   "TransformerBlock": "ultralytics.nn.modules.transformer", "AIFI": "ultralytics.nn.modules.transformer",
                   "TransformerEncoderLayer": "ultralytics.nn.modules.transformer"})
 _REF_HOME.update({"RepConv": "ultralytics.nn.modules.conv", "RepC3": "ultralytics.nn.modules.block"})
+_REF_HOME.update({n: "ultralytics.nn.modules.conv" for n in ("ChannelAttention", "SpatialAttention", "CBAM")})
 _REF_HOME.update({"lowlight_recovery": "ultralytics.nn.modules.llie", "ExtractParameters2": "ultralytics.nn.modules.common",
                   "ConvBlock": "ultralytics.nn.modules.common"})
 # the front-end's filter objects (ultralytics/nn/modules/filtersB.py, filter_cfg.py:17-75): parameter-free modules holding these
@@ -284,6 +285,7 @@ _REF_ATTRS = {"Conv": (), "Concat": ("d",), "C2": ("c",), "C2f": ("c",), "Bottle
               "C3TR": (), "TransformerLayer": (), "TransformerBlock": ("c2",),      # (torch's Linear / MultiheadAttention are torch_leaf children)
               "AIFI": ("normalize_before",), "TransformerEncoderLayer": ("normalize_before",),   # (LayerNorm, GELU and the Dropouts are torch_leaf children too)
               "RepConv": ("g", "c1", "c2", "bn"), "RepC3": (),      # (`self.bn = None` is a plain attribute there: conv.py:207)
+              "ChannelAttention": (), "SpatialAttention": (), "CBAM": (),   # (AdaptiveAvgPool2d, Conv2d and Sigmoid are torch_leaf children: conv.py:299-301, 315-316)
               "Classify": ()}          # (its children are a Conv and torch's AdaptiveAvgPool2d, Dropout and Linear: head.py:250-253)
 
 _STANDINS = {}

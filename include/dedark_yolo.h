@@ -832,6 +832,55 @@ int dy_val_iou_match(const float* iou, int64_t iou_numel, const int64_t* moff, c
                      int max_det, const float* lcls, const int* loff, int L, const float* iouv, int T, int single_cls, uint8_t* correct,
                      void* workspace, void* stream);
 
+/* ---- channel and spatial attention (csrc/cbam.hip) --------------------------------------------------------------------------------
+ * The device side of ChannelAttention (U/nn/modules/conv.py:294-304), SpatialAttention (conv.py:307-320) and CBAM (conv.py:449-459):
+ *   g = sigmoid(a[b]), u = x g, m = (mean_c u, max_c u), s = sigmoid(cv1(m)), y = u s
+ * a [B][a_ld]: the fc's logits in the compute dtype (the pool is dy_chan_pool_fwd, the fc a 1x1 convolution); a == NULL: no channel gate
+ * (SpatialAttention alone).  x / y / dy / dx: NHWC views [B][HW][ld] of which exactly the channels [0, C) are touched, 16-byte
+ * accesses when every map view of a call is 16-byte aligned in pointer and pitch, element accesses otherwise.  C % 8 == 0,
+ * 8 <= C <= DY_CBAM_MAX_C, B <= 65535, B HW < 2^31, k = 3 or 7; all arithmetic f32.  The planes (mean, mx, s, dpre, dmean, dmx: f32
+ * [B][HW]; arg: int32 [B][HW]) are dense.  w: cv1.weight f32 [1][2][k][k] (plane 0 = mean, 1 = max), zero padding k / 2.
+ * Every backward entry gives identical bytes on every run (fixed partial ranges, fixed-order second pass, no atomics). */
+#define DY_CBAM_MAX_C 2048
+#define DY_CBAM_MAX_PARTS 64   /* most workgroups (= partial sums per channel) along the pixels of one image in the reduce */
+#define DY_CBAM_GATE_TILE 8    /* dy_spatial_gate_fwd: pixels per workgroup and direction */
+#define DY_CBAM_CONV_TILE 16   /* dy_spatial_conv_bwd: likewise */
+/* AdaptiveAvgPool2d(1) of ChannelAttention (conv.py:299, 304) for maps of many pixels: y[b][c] = mean_p x[b][p][c] in the compute
+ * dtype, f32 partial sums of at most DY_CBAM_MAX_PARTS workgroups per image added in index order in f64 (deterministic); dy_gap_fwd
+ * walks an image in one thread per channel group and is left as it is.  workspace: dy_cbam_reduce_workspace floats. */
+int dy_chan_pool_fwd(const void* x, int64_t x_ld, void* y, int64_t y_ld, float* workspace, int64_t workspace_elems, int B, int HW, int C,
+                     int dtype, void* stream);
+/* ChannelAttention.forward (conv.py:302-304): y = x sigmoid(a[b]) */
+int dy_chan_gate_fwd(const void* x, int64_t x_ld, const void* a, int64_t a_ld, void* y, int64_t y_ld, int B, int HW, int C, int dtype,
+                     void* stream);
+/* torch.mean(x, 1) / torch.max(x, 1) (conv.py:320) of u = x g in one read, u not stored: mean, mx; arg (NULL: not wanted) = the
+ * lowest channel index that reaches the maximum (torch.max's gradient rule on the CPU).  The running maximum starts from -inf. */
+int dy_spatial_stats_fwd(const void* x, int64_t x_ld, const void* a, int64_t a_ld, float* mean, float* mx, int32_t* arg, int B, int HW,
+                         int C, int dtype, void* stream);
+/* cat + cv1 + sigmoid + the two scales (conv.py:320, 458): s = sigmoid(conv_kxk(mean, mx)) from a halo tile of the planes in LDS,
+ * y = x g s; s (NULL: not kept) is stored for the backward. */
+int dy_spatial_gate_fwd(const void* x, int64_t x_ld, const void* a, int64_t a_ld, const float* mean, const float* mx, const float* w,
+                        int k, void* y, int64_t y_ld, float* s, int B, int H, int W, int C, int dtype, void* stream);
+/* autograd of `u * s` towards s and of the sigmoid: dpre = s (1 - s) sum_c dy x g */
+int dy_spatial_gate_bwd_px(const void* dy, int64_t dy_ld, const void* x, int64_t x_ld, const void* a, int64_t a_ld, const float* s,
+                           float* dpre, int B, int HW, int C, int dtype, void* stream);
+/* autograd of cv1 on the planes: (dmean, dmx) = the transposed convolution of dpre (flipped taps, zero padding) and
+ * dw f32 [2][k][k] = sum_{b, p} dpre[p] m[p + tap].  workspace: dy_spatial_conv_bwd_workspace floats. */
+int64_t dy_spatial_conv_bwd_workspace(int B, int H, int W, int k);
+int dy_spatial_conv_bwd(const float* dpre, const float* mean, const float* mx, const float* w, int k, float* dmean, float* dmx, float* dw,
+                        float* workspace, int64_t workspace_elems, int B, int H, int W, void* stream);
+/* autograd of mean / max / `x * g`, split around the fc's backward so that dx is written once:
+ *   du = dy s + dmean / C + (c == arg ? dmx : 0)                       (s == NULL: no spatial stage, du = dy: ChannelAttention alone)
+ *   reduce: da[b][c] = g (1 - g) sum_p du x, rounded once to the compute dtype; workspace: dy_cbam_reduce_workspace floats
+ *   apply:  dx = du g + dpool[b][c] / HW (+ dx when accumulate); dpool [B][dpool_ld] = the fc's data gradient (NULL: none) */
+int64_t dy_cbam_reduce_workspace(int B, int HW, int C, int dtype);
+int dy_spatial_gate_bwd_reduce(const void* dy, int64_t dy_ld, const void* x, int64_t x_ld, const void* a, int64_t a_ld, const float* s,
+                               const float* dmean, const float* dmx, const int32_t* arg, void* da, int64_t da_ld, float* workspace,
+                               int64_t workspace_elems, int B, int HW, int C, int dtype, void* stream);
+int dy_spatial_gate_bwd_apply(const void* dy, int64_t dy_ld, const void* a, int64_t a_ld, const float* s, const float* dmean,
+                              const float* dmx, const int32_t* arg, const void* dpool, int64_t dpool_ld, void* dx, int64_t dx_ld,
+                              int accumulate, int B, int HW, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
