@@ -511,6 +511,9 @@ extern "C" int dy_bn_act_bwd_valid(const void* dy, int64_t dy_ld, const void* z,
                                    int act, double* sums, void* dz, int64_t dz_ld, float* dgamma, float* dbeta, int64_t pixels, int C,
                                    int C_valid, int dtype, void* stream) {
   DY_CHECK(aff, "dy_bn_act_bwd: null affine buffer");
+  // everything the second pass would refuse is refused here, before the first pass has added to `sums`
+  if (int e = dy_check_view("dy_bn_act_bwd(dz)", dz, dz_ld, C, dtype)) return e;
+  DY_CHECK(C_valid > 0 && C_valid <= C, "dy_bn_act_bwd: C_valid=%d outside 1..C=%d", C_valid, C);
   if (int e = dy_bn_act_bwd_reduce(dy, dy_ld, z, z_ld, aff, aff + C, aff + 2 * C, aff + 3 * C, act, 1, sums, pixels, C, dtype, stream))
     return e;
   return dy_bn_act_bwd_apply_valid(dy, dy_ld, z, z_ld, aff, aff + C, aff + 2 * C, aff + 3 * C, gamma, act, 1, sums, dz, dz_ld, dgamma,

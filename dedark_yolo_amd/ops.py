@@ -509,11 +509,19 @@ def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pa
             scale, shift = None, _padded_vec(bias, cout_pad)
         direct = residual is None
         y = out if (out is not None and direct) else empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev)
-        d = _conv_desc(x, wp, y, B, H, W, cin_pad, Ho, Wo, cout_pad, KH, KW, stride, pad, dil, scale, shift, act, None, False,
-                       dtype)
+        # The backward pass needs act'(conv + bias).  y gives that for no activation and for LeakyReLU (same sign), not for SiLU:
+        # with a tape the conv then leaves the pre-activation in z and y = SiLU(z) is a second pass.  Every other case, and every
+        # call without a tape (predict, val), stays one launch with the activation in the conv's epilogue.
+        keep_z = ctx is not None and not has_bn and act == ACT_SILU
+        z = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev) if keep_z else None
+        d = _conv_desc(x, wp, z if keep_z else y, B, H, W, cin_pad, Ho, Wo, cout_pad, KH, KW, stride, pad, dil, scale, shift,
+                       ACT_NONE if keep_z else act, None, False, dtype)
         _C._prof is not None and _C.set_meta(kind="conv_fwd", dtype=str(dtype), **_conv_meta(Cin, Cout, KH, KW, stride, B, H, W, B * Ho * Wo),
                                              bytes=float((B * H * W * Cin + B * Ho * Wo * Cout + Cout * KH * KW * Cin) * x.element_size()))
         call("dy_conv2d_fwd", C.byref(d), stream())
+        if keep_z:
+            emu_round(z)
+            call("dy_bn_act_fwd", ptr(z), ld_of(z), None, None, act, None, 0, ptr(y), ld_of(y), B * Ho * Wo, cout_pad, dt_id(dtype), stream())
         if not direct:                  # eval-time residual: y_out = y + residual
             tgt = out if out is not None else y
             if tgt is not y:
@@ -525,7 +533,7 @@ def conv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, pa
         if ctx is not None:
             if has_bn:
                 raise RuntimeError("conv: gradients through an eval-mode BatchNorm are not supported")
-            ctx.z, ctx.aff, ctx.y = None, None, y
+            ctx.z, ctx.aff, ctx.y = (z, None, None) if keep_z else (None, None, y)
     if tape is not None:
         tape.push(ctx)
     return y if cout_pad == Cout else y[:, :Cout]
@@ -724,14 +732,16 @@ def _bn_backward(tape, dy, z, aff, bn, act, dz, pixels, C, C_valid, did, st, dev
         _add_pgrad(tape, bn.bias, gb_)
 
 
-def _act_backward(tape, dy, y, bias, act, dz, pixels, C, C_valid, did, st, dev, shared):
-    """Backward of y = act(z + bias) without BatchNorm: dz from dy (the caller passes dz = dy for ACT_NONE, where only the bias
-    gradient is left to compute: 0 pixels), and dbias.  dy / y / dz: whole-vector NHWC views of C channels."""
+def _act_backward(tape, dy, z, bias, act, dz, pixels, C, C_valid, did, st, dev, shared):
+    """Backward of y = act(u), u = conv + bias, without BatchNorm: dz = dy act'(u) (the caller passes dz = dy for ACT_NONE, where
+    only the bias gradient is left to compute: 0 pixels), and dbias.  z must be the pre-activation u, which the forward keeps for
+    SiLU; for the sign-preserving activations (none, LeakyReLU) the stored output y gives the same act' and is passed instead.
+    dy / z / dz: whole-vector NHWC views of C channels."""
     need_bias = bias is not None and bias.requires_grad
     if dz is dy and not need_bias:
         return
     sums = arena.alloc(2 * C * _C.BN_BWD_REPLICAS, dev)
-    pdy, ldy, py, ly = dy.data_ptr(), ld_of(dy), y.data_ptr(), ld_of(y)
+    pdy, ldy, py, ly = dy.data_ptr(), ld_of(dy), z.data_ptr(), ld_of(z)
     call("dy_bn_act_bwd_reduce", pdy, ldy, py, ly, None, None, None, None, act, 0, ptr(sums), pixels, C, did, st)
     db, direct = _grad_sink(bias, C, dev, shared or C != C_valid)         # (a padded dbias never goes straight into bias.grad)
     pdz, ldz, n = (pdy, ldy, 0) if dz is dy else (dz.data_ptr(), ld_of(dz), pixels)                  # 0 pixels: only dbias
@@ -771,7 +781,7 @@ def conv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_src
         _bn_backward(tape, dy, ctx.z, ctx.aff, ctx.bn, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
     else:
         dz = empty_nhwc(B, cout_pad, Ho, Wo, dtype, dev) if ctx.act != ACT_NONE else dy
-        _act_backward(tape, dy, ctx.y, ctx.bias, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
+        _act_backward(tape, dy, ctx.y if ctx.z is None else ctx.z, ctx.bias, ctx.act, dz, pixels, cout_pad, Cout, did, st, dev, ctx.shared)
     return _conv_grads(tape, ctx, dz, need_dx, dx_out, accumulate, add_src)
 
 
@@ -1510,15 +1520,30 @@ def dwconv_forward(tape, x, weight, bias=None, bn=None, act=ACT_NONE, stride=1, 
             scale, shift = aff[0], aff[1]
         else:
             scale, shift = None, (None if bias is None else bias.detach().float())
-        y = out if out is not None else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+        keep_z = ctx is not None and not has_bn and act == ACT_SILU         # conv_forward: SiLU's backward needs the pre-activation
         _C._prof is not None and _C.set_meta(kind="dwconv_fwd", shape=shape, dtype=str(dtype), flops=flops, bytes=nbytes)
-        call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(y), ld_of(y), ptr(w32), B, H, W, Cc, k, stride, ptr(scale), ptr(shift), act, None, 0,
-             did, st)
-        emu_round(y)
+        if keep_z:
+            z = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+            call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(z), ld_of(z), ptr(w32), B, H, W, Cc, k, stride, ptr(scale), ptr(shift), ACT_NONE,
+                 None, 0, did, st)
+            emu_round(z)
+            direct = out is not None and vec_ok(out)
+            y = out if direct else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+            call("dy_bn_act_fwd", ptr(z), ld_of(z), None, None, act, None, 0, ptr(y), ld_of(y), pixels, cpad, did, st)
+            emu_round(y)
+            if out is not None and not direct:
+                copy_exact(y, out)
+                y = out
+        else:
+            z = None
+            y = out if out is not None else _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+            call("dy_dwconv_fwd", ptr(x), ld_of(x), ptr(y), ld_of(y), ptr(w32), B, H, W, Cc, k, stride, ptr(scale), ptr(shift), act, None, 0,
+                 did, st)
+            emu_round(y)
         if ctx is not None:
             if has_bn:
                 raise RuntimeError("dwconv: gradients through an eval-mode BatchNorm are not supported")
-            ctx.z, ctx.aff, ctx.y = None, None, y
+            ctx.z, ctx.aff, ctx.y = (z, None, None) if keep_z else (None, None, y)
     if tape is not None:
         tape.push(ctx)
     return y
@@ -1549,13 +1574,15 @@ def dwconv_backward(tape, dy, need_dx=True, dx_out=None, accumulate=False, add_s
     elif ctx.act == ACT_NONE and not need_bias:
         dz = dy
     else:
-        y = ctx.y
-        if not vec_ok(y):
-            t = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
-            copy_exact(y, t)
-            y = t
+        src = ctx.z                                         # SiLU: the pre-activation, a vector-padded buffer of the forward's
+        if src is None:
+            src = ctx.y
+            if not vec_ok(src):
+                t = _nhwc_like(B, Cc, Ho, Wo, dtype, dev)
+                copy_exact(src, t)
+                src = t
         dz = _nhwc_like(B, Cc, Ho, Wo, dtype, dev) if ctx.act != ACT_NONE else dy
-        _act_backward(tape, dy, y, ctx.bias, ctx.act, dz, pixels, cpad, Cc, did, st, dev, False)
+        _act_backward(tape, dy, src, ctx.bias, ctx.act, dz, pixels, cpad, Cc, did, st, dev, False)
     w32 = _w32(ctx.weight)
     shape = f"dw {Cc} k{k} s{stride} in {B}x{H}x{W}"
     flops = 2.0 * pixels * Cc * k * k

@@ -130,6 +130,9 @@ int dy_bn_act_fwd(const void* z, int64_t z_ld, const float* scale, const float* 
                   int64_t res_ld, void* y, int64_t y_ld, int64_t pixels, int C, int dtype, void* stream);
 /* backward pass 1: sums[0:C] = sum g, sums[C:2C] = sum g*zhat with g = dy*act'(u), u = z*scale+shift,
  * zhat = (z-mean)*invstd (has_bn) ; without BN only sum g (bias gradient).
+ * z must be the PRE-activation (with scale = shift = NULL: u = z = conv + bias): act' is evaluated at u.  Only for an activation
+ * that keeps the sign and whose slope depends on nothing else (none, LeakyReLU) may the caller pass the stored output y = act(u)
+ * as z without BatchNorm; for SiLU act'(y) != act'(u).
  * `sums` is [DY_BN_BWD_REPLICAS][2C] doubles, zeroed by the caller; thread blocks spread their atomics over the replicas
  * and dy_bn_act_bwd_apply adds them up. */
 int dy_bn_act_bwd_reduce(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, const float* scale,

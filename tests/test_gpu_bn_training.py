@@ -550,3 +550,129 @@ def test_unsuffixed_entries_treat_every_channel_as_real():
         outs.append((aff, r, fold))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
+
+
+# ----------------------------------------------------------------- (e) bias + activation backward of a conv without BatchNorm
+def _nobn_ref(x, w, b, gy, act, dtype, k, groups=1, round_w=True):
+    """fp64 autograd of act(conv2d(x, w) + b) on the operands as the kernels see them (the bias stays f32)"""
+    xd = x.to(dtype).double().requires_grad_(True)
+    wd = (w.detach().to(dtype) if round_w else w.detach()).double().requires_grad_(True)
+    bd = b.detach().double().requires_grad_(True)
+    y = _act(F.conv2d(xd, wd, bd, 1, k // 2, 1, groups), act)
+    y.backward(gy.to(dtype).double())
+    return dict(y=y.detach(), dx=xd.grad, dw=wd.grad, db=bd.grad)
+
+
+def _spy_calls(monkeypatch):
+    from dedark_yolo_amd import ops
+    names, real_call = [], ops.call
+
+    def spy(name, *a):
+        names.append(name)
+        return real_call(name, *a)
+    monkeypatch.setattr(ops, "call", spy)
+    return names
+
+
+def _nobn_check(got, want, dtype, what):
+    errs = {k_: _rel(got[k_], want[k_]) for k_ in got}
+    print(f"{what}: {errs}")
+    assert max(errs.values()) <= TOL[dtype], (what, errs)
+
+
+@pytest.mark.parametrize("act", [0, 2, 1], ids=["none", "leaky", "silu"])
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("Cout", [8, 20])
+@pytest.mark.parametrize("dtype", [F32, BF, FP], ids=["f32", "bf16", "f16"])
+def test_conv_bias_act_backward_without_bn(dtype, Cout, k, act, monkeypatch):
+    """ops.conv_forward(tape, x, w, bias, None, act, training=False) + ops.conv_backward (Detect heads, ASFF weight_levels, RFB, a
+    fused RepConv) against fp64 autograd of act(conv2d(x, w) + b): y, dx, dW, dbias at TOL.  The backward must see act' at the
+    pre-activation: for SiLU the forward keeps it (conv with the bias only, then dy_bn_act_fwd); none and LeakyReLU stay one
+    dy_conv2d_fwd launch."""
+    from dedark_yolo_amd import ops
+    ops.set_compute_dtype(dtype)
+    B, Cin, H, W = 2, 8, 9, 7
+    torch.manual_seed(Cout * 7 + k + act)
+    x, gy = torch.randn(B, Cin, H, W, device="cuda"), torch.randn(B, Cout, H, W, device="cuda")
+    w = (torch.randn(Cout, Cin, k, k, device="cuda") / (Cin * k * k) ** 0.5).requires_grad_(True)
+    b = (0.5 * torch.randn(Cout, device="cuda")).requires_grad_(True)
+    names = _spy_calls(monkeypatch)
+    tape = _Tape()
+    y = ops.conv_forward(tape, ops.as_nhwc(x, dtype), w, b, None, act, 1, k // 2, 1, False)
+    fwd = [n for n in names if n != "dy_pack_weight"]
+    dx = ops.conv_backward(tape, ops.as_nhwc(gy, dtype), need_dx=True)
+    torch.cuda.synchronize()
+    got = dict(y=y, dx=dx, dw=tape.pgrads[w], db=tape.pgrads[b])
+    _nobn_check(got, _nobn_ref(x, w, b, gy, act, dtype, k), dtype, f"conv {dtype} Cout={Cout} k={k} act={act}")
+    assert fwd == (["dy_conv2d_fwd", "dy_bn_act_fwd"] if act == 1 else ["dy_conv2d_fwd"]), fwd
+
+
+@pytest.mark.parametrize("act", [0, 2, 1], ids=["none", "leaky", "silu"])
+@pytest.mark.parametrize("dtype", [F32, BF, FP], ids=["f32", "bf16", "f16"])
+def test_conv_without_tape_stays_one_launch(dtype, act, monkeypatch):
+    """predict / val / the inference legs of the benchmark: no tape, one dy_conv2d_fwd with bias and activation in its epilogue"""
+    from dedark_yolo_amd import ops
+    ops.set_compute_dtype(dtype)
+    torch.manual_seed(act)
+    x = torch.randn(2, 8, 9, 7, device="cuda")
+    w, b = torch.randn(20, 8, 3, 3, device="cuda") / 72 ** 0.5, 0.5 * torch.randn(20, device="cuda")
+    names = _spy_calls(monkeypatch)
+    y = ops.conv_forward(None, ops.as_nhwc(x, dtype), w, b, None, act, 1, 1, 1, False)
+    dw = ops.dwconv_forward(None, ops.as_nhwc(x, dtype), w[:8, :1].contiguous(), b[:8], None, act, 1, False)
+    torch.cuda.synchronize()
+    assert [n for n in names if n != "dy_pack_weight"] == ["dy_conv2d_fwd", "dy_dwconv_fwd"], names
+    want = _act(F.conv2d(x.to(dtype).double(), w.to(dtype).double(), b.double(), 1, 1), act)
+    assert _rel(y, want) <= TOL[dtype]
+    want = _act(F.conv2d(x.to(dtype).double(), w[:8, :1].double(), b[:8].double(), 1, 1, 1, 8), act)
+    assert _rel(dw, want) <= TOL[dtype]
+
+
+@pytest.mark.parametrize("act", [0, 2, 1], ids=["none", "leaky", "silu"])
+@pytest.mark.parametrize("dtype", [F32, BF, FP], ids=["f32", "bf16", "f16"])
+def test_dwconv_bias_act_backward_without_bn(dtype, act, monkeypatch):
+    """the same through ops.dwconv_forward / dwconv_backward: depthwise 3x3 over 12 channels (16 wide in the 16-bit types) with a
+    bias and no BatchNorm; the depthwise weights stay f32"""
+    from dedark_yolo_amd import ops
+    ops.set_compute_dtype(dtype)
+    B, Cc, H, W = 2, 12, 9, 7
+    torch.manual_seed(40 + act)
+    x, gy = torch.randn(B, Cc, H, W, device="cuda"), torch.randn(B, Cc, H, W, device="cuda")
+    w = (torch.randn(Cc, 1, 3, 3, device="cuda") / 3.0).requires_grad_(True)
+    b = (0.5 * torch.randn(Cc, device="cuda")).requires_grad_(True)
+    names = _spy_calls(monkeypatch)
+    tape = _Tape()
+    y = ops.dwconv_forward(tape, ops.as_nhwc(x, dtype), w, b, None, act, 1, False)
+    fwd = list(names)
+    dx = ops.dwconv_backward(tape, ops.as_nhwc(gy, dtype), need_dx=True)
+    torch.cuda.synchronize()
+    got = dict(y=y, dx=dx, dw=tape.pgrads[w], db=tape.pgrads[b])
+    _nobn_check(got, _nobn_ref(x, w, b, gy, act, dtype, 3, groups=Cc, round_w=False), dtype, f"dwconv {dtype} act={act}")
+    assert fwd.count("dy_dwconv_fwd") == 1 and fwd.count("dy_bn_act_fwd") == (1 if act == 1 else 0), fwd
+
+
+def test_fused_repconv_backward_with_a_tape():
+    """RepConv after fuse_convs() is one 3x3 conv with a bias and SiLU in front of frozen weights; run with a tape its data
+    gradient must be that of SiLU(conv2d(x, W) + b)"""
+    from dedark_yolo_amd import ops
+    from dedark_yolo_amd.nn.modules import RepConv
+    dtype = F32
+    ops.set_compute_dtype(dtype)
+    torch.manual_seed(11)
+    m = RepConv(8, 8).cuda()
+    for br_ in (m.conv1, m.conv2):
+        with torch.no_grad():
+            br_.bn.weight.copy_(1.0 + 0.3 * torch.randn(8))
+            br_.bn.bias.copy_(0.3 * torch.randn(8))
+            br_.bn.running_mean.copy_(0.1 * torch.randn(8))
+            br_.bn.running_var.copy_(0.5 + torch.rand(8))
+            br_.conv.weight.mul_(3.0)
+    m.eval()
+    m.fuse_convs()
+    x, gy = torch.randn(2, 8, 9, 7, device="cuda"), torch.randn(2, 8, 9, 7, device="cuda")
+    tape = _Tape()
+    y = m._fwd(tape, ops.as_nhwc(x, dtype))
+    dx = m._bwd(tape, ops.as_nhwc(gy, dtype))
+    torch.cuda.synchronize()
+    assert not tape.stack and not tape.pgrads                   # the fused weights are frozen
+    want = _nobn_ref(x, m.conv.weight, m.conv.bias, gy, 1, dtype, 3)
+    _nobn_check(dict(y=y, dx=dx), {k_: want[k_] for k_ in ("y", "dx")}, dtype, "fused RepConv")
