@@ -55,6 +55,12 @@ class AugMixSample(C.Structure):
     _fields_ = [("a", AugSample), ("b", AugSample), ("r", C.c_double), ("r1", C.c_double), ("mix", i32)]
 
 
+class ClsSample(C.Structure):
+    """dy_cls_sample (include/dedark_yolo.h), 824 bytes"""
+    _fields_ = [("src", vp), ("pitch", i64), ("sh", i32), ("sw", i32), ("x0", i32), ("y0", i32), ("cw", i32), ("ch", i32),
+                ("fliplr", i32), ("flipud", i32), ("hsv", i32), ("reserved", i32), ("lut", (C.c_uint8 * 256) * 3)]
+
+
 class SegDesc(C.Structure):
     """dy_seg_desc (include/dedark_yolo.h)"""
     _fields_ = [("mc", vp), ("mc_ld", i64), ("proto", vp), ("proto_ld", i64), ("B", i32), ("A", i32), ("nm", i32), ("mh", i32),
@@ -162,6 +168,7 @@ _SIGS = {
     "dy_aug_letterbox": [vp, i32, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp],
     "dy_aug_mosaic_warp": [vp, i32, i32, i32, vp, vp],
     "dy_aug_mosaic_warp_mix": [vp, i32, i32, i32, vp, vp],
+    "dy_cls_render": [vp, i32, i32, vp, vp],
     "dy_dark_channel_prior": [vp, i32, i32, i32, vp, vp, vp],
     "dy_dfl_loss": [vp, vp, i64, vp, vp, vp],
     "dy_loss_fwd": [C.POINTER(DetMaps), vp, vp, vp, vp, vp, vp, vp],

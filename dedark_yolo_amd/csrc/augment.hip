@@ -117,7 +117,16 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
 }
 
 // ---- cv::cvtColor 8-bit BGR <-> HSV (color_hsv.cpp: RGB2HSV_b's 12-bit division tables, HSV2RGB_b's float path) ---------------------
-__device__ inline void bgr2hsv(int b, int g, int r, const int* sdiv, const int* hdiv, int& h, int& s, int& v) {
+// entry i of RGB2HSV_b's two division tables, computed where it is needed (a kernel without shared memory indexes these instead of a
+// table; load_hsv_tables fills its tables from them)
+struct SDiv {
+  __device__ int operator[](int i) const { return i ? rint_i((double)(255 << 12) / (1.0 * i)) : 0; }
+};
+struct HDiv180 {
+  __device__ int operator[](int i) const { return i ? rint_i((double)(180 << 12) / (6.0 * i)) : 0; }
+};
+template <class SDivT, class HDivT>
+__device__ inline void bgr2hsv(int b, int g, int r, const SDivT& sdiv, const HDivT& hdiv, int& h, int& s, int& v) {
   v = max(max(b, g), r);
   const int vmin = min(min(b, g), r);
   const int diff = v - vmin;
@@ -190,8 +199,8 @@ __device__ inline void warp_px(const dy_aug_sample& a, int wx, int wy, int* bgr)
 // the division tables of bgr2hsv and the three tables of the block's sample, one entry per thread (256 threads)
 __device__ inline void load_hsv_tables(const dy_aug_sample& a, int* sdiv, int* hdiv, uint8_t (*lut)[256]) {
   const int i = threadIdx.x;
-  sdiv[i] = i ? rint_i((double)(255 << 12) / (1.0 * i)) : 0;
-  hdiv[i] = i ? rint_i((double)(180 << 12) / (6.0 * i)) : 0;
+  sdiv[i] = SDiv()[i];
+  hdiv[i] = HDiv180()[i];
   lut[0][i] = a.lut[0][i]; lut[1][i] = a.lut[1][i]; lut[2][i] = a.lut[2][i];
 }
 
@@ -248,6 +257,45 @@ __global__ __launch_bounds__(256) void mosaic_warp_mix_kernel(const dy_aug_mix_s
     for (int c = 0; c < 3; ++c) bgr[c] = (int)(uint8_t)(__dadd_rn(__dmul_rn((double)bgr[c], r), __dmul_rn((double)pb[c], r1)));
   }
   hsv_store(a, bgr, sdiv, hdiv, lut, oh, ow, ox, oy, out);
+}
+
+// ---- classify: crop -> cv::resize(INTER_LINEAR) to S x S -> flips -> RandomHSV -> planar RGB, a whole batch per launch ---------------
+// out[b][.][oy][ox] is pixel (wy, wx) of cv2.resize(src[y0:y0+ch, x0:x0+cw], (S, S)) with wy / wx mirrored by the flips.  The crop is
+// handed to resize_axis / resize_px as an image of its own (base pointer at its first pixel, cw x ch), so every clamped tap clamps to
+// the CROP: cv2 sees a view and no pixel outside it can reach the output.  NPX = 4: a thread renders four neighbouring columns of one
+// row and writes one 32-bit word per plane (S % 4 == 0 and a 4-byte aligned `out`: the host picks); NPX = 1: byte stores.  The 64
+// lanes of a wave are neighbouring columns (groups) of a row, blockIdx.z is the sample.  No shared memory: the HSV division entries
+// are computed per pixel (SDiv / HDiv180), the three tables are read from the descriptor.
+template <int NPX>
+__global__ __launch_bounds__(256) void cls_render_kernel(const dy_cls_sample* __restrict__ samples, int S, uint8_t* __restrict__ out) {
+  const dy_cls_sample& a = samples[blockIdx.z];
+  const int ox0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * NPX, oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (ox0 >= S || oy >= S) return;
+  const uint8_t* crop = a.src + (long)a.y0 * a.pitch + (long)a.x0 * 3;
+  const ResizeAxis ay = resize_axis(a.flipud ? S - 1 - oy : oy, a.ch, S, false);
+  uint32_t word[3] = {0u, 0u, 0u};                                       // planes R, G, B: byte j is column ox0 + j
+#pragma unroll
+  for (int j = 0; j < NPX; ++j) {
+    const int ox = ox0 + j;
+    const ResizeAxis ax = resize_axis(a.fliplr ? S - 1 - ox : ox, a.cw, S, true);
+    int bgr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bgr[c] = resize_px(crop, a.pitch, ax, ay, c);
+    if (a.hsv) {
+      int h, s, v;
+      bgr2hsv(bgr[0], bgr[1], bgr[2], SDiv(), HDiv180(), h, s, v);
+      hsv2bgr(a.lut[0][h], a.lut[1][s], a.lut[2][v], bgr[0], bgr[1], bgr[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) word[k] |= (uint32_t)bgr[2 - k] << (8 * j);
+  }
+  const long plane = (long)S * S;
+  uint8_t* o = out + (long)blockIdx.z * 3 * plane + (long)oy * S + ox0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (NPX == 4) *reinterpret_cast<uint32_t*>(o + k * plane) = word[k];
+    else o[k * plane] = (uint8_t)word[k];
+  }
 }
 
 // ---- dark-channel prior of the trainer (models/yolo/detect/train.py:42-68), deterministic -----------------------------------------------
@@ -441,6 +489,38 @@ extern "C" int dy_aug_mosaic_warp_mix(const dy_aug_mix_sample* samples, int B, i
   DY_CHECK(B <= 65535, "dy_aug_mosaic_warp_mix: at most 65535 samples per launch");
   if (B == 0) return 0;
   mosaic_warp_mix_kernel<<<dim3(dy_cdiv(out_w, 64), dy_cdiv(out_h, 4), B), 256, 0, (hipStream_t)stream>>>(samples, out_h, out_w, out);
+  DY_LAUNCH_CHECK();
+  return 0;
+}
+
+static_assert(sizeof(dy_cls_sample) == 824, "descriptor layout: _C.ClsSample");
+
+extern "C" int dy_cls_render(const dy_cls_sample* samples, int B, int S, uint8_t* out, void* stream) {
+  DY_CHECK(B >= 0 && S > 0 && (B == 0 || (samples && out)), "dy_cls_render: bad arguments");
+  DY_CHECK(B <= 65535, "dy_cls_render: at most 65535 samples per launch");
+  if (B == 0) return 0;
+  // The descriptors are in device memory and a crop outside its image would make the kernel read outside the allocation, so they are
+  // read back and checked before anything is launched: one small copy and a wait on `stream` (the one entry of this file that waits).
+  static thread_local std::vector<dy_cls_sample> host;
+  host.resize(B);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(host.data(), samples, (size_t)B * sizeof(dy_cls_sample), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    dy_set_error("dy_cls_render: reading the descriptors back failed: %s", hipGetErrorString(e));
+    return 2;
+  }
+  for (int b = 0; b < B; ++b) {
+    const dy_cls_sample& a = host[b];
+    DY_CHECK(a.src && a.sh > 0 && a.sw > 0 && a.pitch >= 3L * a.sw, "dy_cls_render: sample %d: bad source image", b);
+    DY_CHECK(a.cw > 0 && a.ch > 0 && a.x0 >= 0 && a.y0 >= 0 && (long)a.x0 + a.cw <= a.sw && (long)a.y0 + a.ch <= a.sh,
+             "dy_cls_render: sample %d: crop (%d, %d, %d x %d) is empty or not inside its %d x %d image", b, a.x0, a.y0, a.cw, a.ch, a.sw,
+             a.sh);
+  }
+  if (S % 4 == 0 && ((uintptr_t)out & 3) == 0)
+    cls_render_kernel<4><<<dim3(dy_cdiv(S / 4, 64), dy_cdiv(S, 4), B), 256, 0, s>>>(samples, S, out);
+  else
+    cls_render_kernel<1><<<dim3(dy_cdiv(S, 64), dy_cdiv(S, 4), B), 256, 0, s>>>(samples, S, out);
   DY_LAUNCH_CHECK();
   return 0;
 }

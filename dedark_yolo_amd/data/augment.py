@@ -809,3 +809,134 @@ def dark_channel_prior(img):
     ica = torch.empty((B, 1, H, W), dtype=torch.float32, device=img.device)
     call("dy_dark_channel_prior", ptr(img), B, H, W, ptr(A), ptr(ica), stream())
     return A, ica
+
+
+# ---------------------------------------------------------------------------------------------------------------- classify
+# Pinned to the reference: center_crop_rect (CenterCrop, data/augment.py:879-891) and, through it, the val / predict / augment=False
+# transform classify_transforms = CenterCrop(size) + ToTensor() (:799-806, 894-907).  NOT pinned: the training augmentation.  The
+# reference's chain is classify_albumentations (:814-855: RandomResizedCrop, flips, ColorJitter) and needs a package that is absent, so
+# plan_cls_sample is this project's own rule over the parameters the reference hands to that chain.
+CLS_RATIO = (3.0 / 4.0, 4.0 / 3.0)                            # aspect-ratio interval of the random resized crop
+CLS_ATTEMPTS = 10
+
+
+def ClassifyHyp(**kw):
+    """the augmentation parameters of the classify training set: the cfg keys the reference passes to classify_albumentations
+    (scale -> (1 - scale, 1), fliplr, flipud, hsv_h / hsv_s / hsv_v) with cfg/default.yaml's values"""
+    d = dict(scale=0.5, fliplr=0.5, flipud=0.0, hsv_h=0.015, hsv_s=0.7, hsv_v=0.4)
+    d.update(kw)
+    return SimpleNamespace(**d)
+
+
+def center_crop_rect(h, w):
+    """the window of the reference's CenterCrop (data/augment.py:887-891) in an h x w image as (x0, y0, cw, ch): m = min(h, w),
+    top = (h - m) // 2, left = (w - m) // 2; the window is then resized to (size, size) with cv2.INTER_LINEAR"""
+    m = min(int(h), int(w))
+    return (int(w) - m) // 2, (int(h) - m) // 2, m, m
+
+
+def plan_cls_sample(shape, hyp, rnd=_random, nprnd=np.random):
+    """Random draws of ONE classify training sample.  This augmentation is the PROJECT'S OWN: the reference's training chain
+    (classify_albumentations) cannot run or be pinned here, so only its parameters are kept -- scale=(1 - hyp.scale, 1), hflip =
+    hyp.fliplr, vflip = hyp.flipud, and hsv_h / hsv_s / hsv_v, which it turns into ColorJitter(v, v, s, h) and which drive the detect
+    pipeline's RandomHSV tables (hsv_luts) here instead.  `shape` = (H, W) of the decoded image.  Draws, in this order, only from the
+    generators passed in:
+      1. random resized crop (skipped, with no draw, when hyp.scale == 0: the full image).  Up to 10 attempts, each two draws:
+         s = rnd.uniform(1 - hyp.scale, 1), r = exp(rnd.uniform(log 3/4, log 4/3)); w = round(sqrt(H W s r)), h = round(sqrt(H W s / r))
+         (Python's round); accepted when 0 < w <= W and 0 < h <= H, then y0 = rnd.randint(0, H - h), x0 = rnd.randint(0, W - w) and no
+         further attempt.  All ten refused: the central crop with the image's ratio W / H clamped to [3/4, 4/3] -- below 3/4:
+         w = W, h = round(W / (3/4)); above 4/3: h = H, w = round(H * 4/3); else the full image -- at y0 = (H - h) // 2, x0 = (W - w) // 2;
+      2. fliplr = rnd.random() < hyp.fliplr;  3. flipud = rnd.random() < hyp.flipud (both always drawn);
+      4. when any of hsv_h / hsv_s / hsv_v is non-zero: nprnd.uniform(-1, 1, 3) * [hsv_h, hsv_s, hsv_v] + 1 -> hsv_luts.
+    Returns a SimpleNamespace(rect=(x0, y0, cw, ch), fliplr, flipud, hsv_gains (None without gains), luts)."""
+    H, W = int(shape[0]), int(shape[1])
+    rect = None
+    if hyp.scale == 0:
+        rect = (0, 0, W, H)
+    else:
+        area, lo, hi = H * W, math.log(CLS_RATIO[0]), math.log(CLS_RATIO[1])
+        for _ in range(CLS_ATTEMPTS):
+            s = rnd.uniform(1 - hyp.scale, 1)
+            r = math.exp(rnd.uniform(lo, hi))
+            w, h = int(round(math.sqrt(area * s * r))), int(round(math.sqrt(area * s / r)))
+            if 0 < w <= W and 0 < h <= H:
+                y0 = rnd.randint(0, H - h)
+                rect = (rnd.randint(0, W - w), y0, w, h)
+                break
+        if rect is None:
+            ratio = W / H
+            if ratio < CLS_RATIO[0]:
+                w, h = W, int(round(W / CLS_RATIO[0]))
+            elif ratio > CLS_RATIO[1]:
+                w, h = int(round(H * CLS_RATIO[1])), H
+            else:
+                w, h = W, H
+            rect = ((W - w) // 2, (H - h) // 2, w, h)
+    p = SimpleNamespace(rect=rect, hsv_gains=None, luts=None)
+    p.fliplr = rnd.random() < hyp.fliplr
+    p.flipud = rnd.random() < hyp.flipud
+    if hyp.hsv_h or hyp.hsv_s or hyp.hsv_v:
+        p.hsv_gains = nprnd.uniform(-1, 1, 3) * [hyp.hsv_h, hyp.hsv_s, hyp.hsv_v] + 1
+        p.luts = hsv_luts(p.hsv_gains)
+    return p
+
+
+def center_plan(shape):
+    """the plan of the centre-crop transform: no flips, no colour gains"""
+    return SimpleNamespace(rect=center_crop_rect(*shape), fliplr=False, flipud=False, hsv_gains=None, luts=None)
+
+
+def cls_descriptors(n, buffer=None):
+    """numpy record view of n dy_cls_sample over `buffer` (a uint8 host tensor, e.g. a pinned staging slot) or over fresh memory"""
+    import ctypes as C
+    from .._C import ClsSample
+    dt = np.dtype(dict(names=["src", "pitch", "sh", "sw", "x0", "y0", "cw", "ch", "fliplr", "flipud", "hsv", "reserved", "lut"],
+                       formats=["<u8", "<i8"] + ["<i4"] * 10 + [("u1", (3, 256))],
+                       offsets=[getattr(ClsSample, f).offset for f, _ in ClsSample._fields_], itemsize=C.sizeof(ClsSample)))
+    if buffer is None:
+        return np.zeros(n, dtype=dt)
+    return buffer.numpy()[:n * dt.itemsize].view(dt)
+
+
+def fill_cls_descriptors(desc, images, plans):
+    """writes one dy_cls_sample per (image, plan): `images[k]` the uint8 HWC BGR device tensor plan k reads (any row pitch)"""
+    for k, (im, p) in enumerate(zip(images, plans)):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3 or not im.is_cuda:
+            raise ValueError("classify render: images must be device uint8 HWC tensors with 3 packed channels")
+        x0, y0, cw, ch = p.rect
+        if not (cw > 0 and ch > 0 and x0 >= 0 and y0 >= 0 and x0 + cw <= im.shape[1] and y0 + ch <= im.shape[0]):
+            raise ValueError(f"classify render: crop {p.rect} is empty or not inside its {im.shape[0]} x {im.shape[1]} image")
+        d = desc[k]
+        d["src"], d["pitch"], d["sh"], d["sw"] = im.data_ptr(), im.stride(0), im.shape[0], im.shape[1]
+        d["x0"], d["y0"], d["cw"], d["ch"] = x0, y0, cw, ch
+        d["fliplr"], d["flipud"], d["hsv"], d["reserved"] = int(p.fliplr), int(p.flipud), int(p.hsv_gains is not None), 0
+        if p.hsv_gains is not None:
+            d["lut"][0], d["lut"][1], d["lut"][2] = p.luts
+
+
+def cls_render(images, plans, imgsz, staging=None):
+    """uint8 [B, 3, S, S] planar RGB of B (image, plan) pairs: ONE dy_cls_render launch on the current stream.  `staging`: optional
+    pinned uint8 host tensor the descriptors are written into and copied from without blocking; without it they come from pageable
+    memory.  B == 0 gives an empty batch."""
+    from .._C import ClsSample, call
+    from ..ops import ptr, stream
+    import ctypes as C
+    B, S = len(plans), int(imgsz)
+    if len(images) != B:
+        raise ValueError("classify render: one image per plan")
+    dev = images[0].device if B else torch.device("cuda")
+    out = torch.empty((B, 3, S, S), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return out
+    nbytes = B * C.sizeof(ClsSample)
+    host = staging[:nbytes] if staging is not None else torch.empty(nbytes, dtype=torch.uint8)
+    fill_cls_descriptors(cls_descriptors(B, host), images, plans)
+    desc = host.to(dev, non_blocking=staging is not None)
+    call("dy_cls_render", ptr(desc), B, S, ptr(out), stream())
+    return out
+
+
+def center_crop_batch(images, imgsz):
+    """the reference's classify_transforms up to its / 255 (CenterCrop(imgsz) + ToTensor's HWC BGR -> CHW RGB) for a list of decoded
+    uint8 HWC BGR device images: uint8 [B, 3, imgsz, imgsz]"""
+    return cls_render(images, [center_plan(im.shape[:2]) for im in images], imgsz)

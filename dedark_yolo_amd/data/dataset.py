@@ -303,6 +303,84 @@ def load_split(data, split, task, args):
     return [lab["im_file"] for lab in labels], labels, counts
 
 
+# ---------------------------------------------------------------------------------------------------------------- classify: folder datasets
+# The classify task reads one folder per class (reference check_cls_dataset, data/utils.py:269-315, and torchvision's ImageFolder, which
+# the reference's dataset class would wrap).  read_labels / task_labels / TaskLabels keep refusing "classify": these are its own entries.
+CLS_IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")      # torchvision's IMG_EXTENSIONS
+
+
+def check_cls_dataset(path, split=""):
+    """A classification dataset directory as the reference's dict (check_cls_dataset, data/utils.py:269-315, without any download):
+      train = <root>/train; val = <root>/val if it exists, else None; test likewise; the dict carries `val or test` under 'val' and
+      `test or val` under 'test' (each falls back to the other); nc = number of directories under train/; names =
+      dict(enumerate(sorted(directory names))).  `split` 'val' / 'test' that is not on disk only logs the fallback, as the reference.
+    A missing root, or a root without train/, raises FileNotFoundError naming the path (the reference would try to download)."""
+    root = Path(path)
+    if not root.is_dir():
+        raise FileNotFoundError(f"classify dataset '{path}' does not exist (expected a directory with train/ and val/ or test/)")
+    root = root.resolve()
+    train = root / "train"
+    if not train.is_dir():
+        raise FileNotFoundError(f"classify dataset '{root}' has no train/ directory: {train}")
+    val = root / "val" if (root / "val").exists() else None
+    test = root / "test" if (root / "test").exists() else None
+    if split == "val" and not val:
+        LOGGER.info("WARNING dataset 'split=val' not found, using 'split=test' instead.")
+    elif split == "test" and not test:
+        LOGGER.info("WARNING dataset 'split=test' not found, using 'split=val' instead.")
+    names = sorted(x.name for x in train.iterdir() if x.is_dir())
+    return dict(train=train, val=val or test, test=test or val, nc=len(names), names=dict(enumerate(names)))
+
+
+def image_folder(root):
+    """(files, cls, classes) of a directory with one sub-directory per class, by the rule of torchvision's ImageFolder (the package is
+    absent; the rule is stated here):
+      * classes = the sorted names of the sub-directories of `root`; class id = position in that list;
+      * for each class in that order the tree below it is walked (links followed) with the directories and the file names of every
+        directory sorted; a file is kept when its lower-cased name ends in one of CLS_IMG_EXTENSIONS;
+      * no sub-directory at all, or a class without a kept file, raises FileNotFoundError naming the directory / the classes.
+    files: list of str; cls: int64 [n]; classes: list of str."""
+    root = str(root)
+    if not os.path.isdir(root):
+        raise FileNotFoundError(f"'{root}' is not a directory")
+    classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
+    if not classes:
+        raise FileNotFoundError(f"no class folders found in {root}")
+    files, cls, empty = [], [], []
+    for k, name in enumerate(classes):
+        n0 = len(files)
+        for d, dirs, fnames in os.walk(os.path.join(root, name), followlinks=True):
+            dirs.sort()                                        # os.walk descends in the order the list is left in
+            files += [os.path.join(d, f) for f in sorted(fnames) if f.lower().endswith(CLS_IMG_EXTENSIONS)]
+        if len(files) == n0:
+            empty.append(name)
+        cls += [k] * (len(files) - n0)
+    if empty:
+        raise FileNotFoundError(f"no valid image file in class folder(s) {', '.join(empty)} of {root} "
+                                f"(extensions: {', '.join(CLS_IMG_EXTENSIONS)})")
+    return files, np.array(cls, dtype=np.int64), classes
+
+
+def load_cls_split(data, split, args=None):
+    """(files, cls) of one split of a check_cls_dataset dict.  `fraction` < 1 (cfg / args) keeps the first round(n * fraction) samples
+    of the TRAINING split only.  A val / test split whose class folders are not exactly the training split's raises ValueError: the
+    class id is the position in the split's own sorted folder list, so a missing or extra folder would shift the ids silently."""
+    folder = data.get(split)
+    if not folder:
+        raise FileNotFoundError(f"the classify dataset has no '{split}' split")
+    files, cls, classes = image_folder(folder)
+    want = [data["names"][i] for i in range(len(data["names"]))]
+    if split != "train" and classes != want:
+        raise ValueError(f"{folder}: the class folders {classes} are not the training split's {want}: the class ids would not mean the same")
+    if split == "train":
+        fraction = float(getattr(args, "fraction", 1.0) or 1.0)
+        if fraction < 1:
+            n = round(len(files) * fraction)
+            files, cls = files[:n], cls[:n]
+    LOGGER.info(f"{split}: {len(files)} images in {len(classes)} classes")
+    return files, cls
+
+
 # ---------------------------------------------------------------------------------------------------------------- pixels
 def decode(im_file):
     """uint8 HWC BGR (cv2.imread's layout, the one dy_aug_sample documents): PIL open -> EXIF transpose -> RGB -> channel flip.

@@ -305,3 +305,160 @@ class DeviceValLoader:
             if self.task == "pose":
                 batch["keypoints"] = torch.from_numpy(np.concatenate([l[2] for l in lab], 0))
             yield batch
+
+
+# ---------------------------------------------------------------------------------------------------------------- classify
+class ClassifyTrainLoader:
+    """Training batches of the classify task: {img: uint8 [B, 3, S, S] RGB (device), cls: int64 [B] (device)}, the schema the
+    trainer's _preprocess_classify takes.  `images`: decoded uint8 HWC BGR arrays (dataset.decode), kept at their DECODED size --
+    resident=True in device memory, resident=False in pinned host memory with the sources of a batch uploaded for it; `cls`: one class
+    id per image.  Per batch the host plans every sample (plan_cls_sample: random resized crop, flips, RandomHSV tables -- the project's
+    own augmentation, see there; augment=False: the reference's centre crop, center_crop_rect), writes the descriptors into a pinned
+    ring and ONE dy_cls_render launch on the loader's stream crops, resizes, flips, recolours and transposes the whole batch; batch
+    k + 1 is issued while step k runs, as in DeviceAugmentLoader.  The generators are the loader's own (seed, seed + 1)."""
+
+    RING = 3
+
+    def __init__(self, images, cls, imgsz, batch_size, hyp=None, device="cuda", resident=True, seed=0, shuffle=True, drop_last=True,
+                 augment=True):
+        from .augment import ClassifyHyp
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ClassifyTrainLoader: the pixel pipeline only exists on the device")
+        self.imgsz, self.bs, self.hyp = int(imgsz), int(batch_size), hyp or ClassifyHyp()
+        self.augment, self.shuffle, self.drop_last, self.resident = bool(augment), shuffle, drop_last, bool(resident)
+        if len(images) != len(cls):
+            raise ValueError("ClassifyTrainLoader: one class id per image")
+        host = [im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)) for im in images]
+        for im in host:
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
+                raise ValueError("ClassifyTrainLoader: images must be contiguous uint8 HWC with 3 channels")
+        self.shapes = [(int(im.shape[0]), int(im.shape[1])) for im in host]
+        self.images = [im.to(self.device) for im in host] if self.resident else [im if im.is_cuda else im.pin_memory() for im in host]
+        self.cls = torch.as_tensor(np.asarray(cls), dtype=torch.int64).reshape(-1).to(self.device)
+        self.rnd = _random.Random(seed)
+        self.nprnd = np.random.RandomState(seed + 1)
+        self.uploaded_bytes = 0
+        self._ring = None
+
+    def __len__(self):
+        n = len(self.shapes)
+        return n // self.bs if self.drop_last else -(-n // self.bs)
+
+    def _slot(self):
+        import ctypes as C
+        from .._C import ClsSample
+        if self._ring is None:
+            self._ring = [dict(desc=torch.empty(self.bs * C.sizeof(ClsSample), dtype=torch.uint8).pin_memory(),
+                               idx=torch.empty(self.bs, dtype=torch.int64).pin_memory(), ev=torch.cuda.Event()) for _ in range(self.RING)]
+            self._turn = 0
+            self.stream = torch.cuda.Stream(device=self.device)
+        slot = self._ring[self._turn % self.RING]
+        self._turn += 1
+        slot["ev"].synchronize()
+        return slot
+
+    def _prepare(self, indices):
+        from .augment import center_plan, cls_render, plan_cls_sample
+        if self.augment:
+            plans = [plan_cls_sample(self.shapes[i], self.hyp, self.rnd, self.nprnd) for i in indices]
+        else:
+            plans = [center_plan(self.shapes[i]) for i in indices]
+        slot = self._slot()
+        slot["idx"][:len(indices)] = torch.as_tensor(indices, dtype=torch.int64)
+        with torch.cuda.stream(self.stream):
+            if self.resident:
+                srcs = [self.images[i] for i in indices]
+            else:
+                up = {i: self.images[i].to(self.device, non_blocking=True) for i in sorted(set(indices))}
+                self.uploaded_bytes += sum(t.numel() for t in up.values())
+                srcs = [up[i] for i in indices]
+            img = cls_render(srcs, plans, self.imgsz, staging=slot["desc"])
+            cls = self.cls[slot["idx"][:len(indices)].to(self.device, non_blocking=True)]
+            slot["ev"].record(self.stream)
+        return dict(img=img, cls=cls), slot["ev"], (img, cls)
+
+    def __iter__(self):
+        order = list(range(len(self.shapes)))
+        if self.shuffle:
+            self.rnd.shuffle(order)
+        chunks = [order[i:i + self.bs] for i in range(0, len(order), self.bs)]
+        if self.drop_last:
+            chunks = [c for c in chunks if len(c) == self.bs]
+        nxt = self._prepare(chunks[0]) if chunks else None
+        for k in range(len(chunks)):
+            batch, ev, tensors = nxt
+            cur = torch.cuda.current_stream()
+            cur.wait_event(ev)
+            for t in tensors:
+                t.record_stream(cur)
+            yield batch
+            nxt = self._prepare(chunks[k + 1]) if k + 1 < len(chunks) else None
+
+
+class ClassifyValLoader:
+    """Validation (and test) batches of the classify task: every file is decoded once, centre-cropped and resized on the device
+    (augment.center_crop_batch: the reference's classify_transforms, CenterCrop(imgsz) + ToTensor, data/augment.py:799-806) -- a batch
+    per launch -- and the rendered uint8 [b, 3, S, S] batches are kept between epochs; the decoded sources are not.  File order is kept,
+    the last batch may be smaller.  Batches: {img, cls int64 [b] (device), im_file}."""
+
+    def __init__(self, files, cls, imgsz, batch_size, device="cuda", workers=8):
+        from .augment import center_crop_batch
+        from .dataset import decode_all
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ClassifyValLoader: the pixel pipeline only exists on the device")
+        if len(files) != len(cls) or not len(files):
+            raise ValueError("ClassifyValLoader: one class id per image file, at least one")
+        self.imgsz, self.bs, self.im_files = int(imgsz), int(batch_size), [str(f) for f in files]
+        self.cls = torch.as_tensor(np.asarray(cls), dtype=torch.int64).reshape(-1).to(self.device)
+        self.ori_shapes, self.batches = [], []
+        with torch.cuda.device(self.device):
+            for o in range(0, len(self.im_files), self.bs):
+                decoded = decode_all(self.im_files[o:o + self.bs], workers)
+                self.ori_shapes += [(int(im.shape[0]), int(im.shape[1])) for im in decoded]
+                self.batches.append(center_crop_batch([torch.from_numpy(im).to(self.device) for im in decoded], self.imgsz))
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        for k, img in enumerate(self.batches):
+            o = k * self.bs
+            yield dict(img=img, cls=self.cls[o:o + len(img)], im_file=self.im_files[o:o + len(img)])
+
+
+def _classify_hyp(args):
+    from .augment import ClassifyHyp
+    return ClassifyHyp(**{k: getattr(args, k) for k in vars(ClassifyHyp()) if getattr(args, k, None) is not None})
+
+
+def build_cls_train_loader(args, data, device="cuda", rank=-1, world_size=1):
+    """The training split of a check_cls_dataset dict as a ClassifyTrainLoader (the reference: ClassificationTrainer.build_dataset /
+    get_dataloader, models/yolo/classify/train.py:69-85).  Files by dataset.image_folder (`fraction` applies), decoded once; kept in
+    device memory unless the decoded bytes exceed half of the free device memory, then in pinned host memory -- the rule and the log
+    line of build_train_loader.  world_size > 1: rank r takes the samples r::world_size."""
+    from .dataset import LOGGER, decode_all, load_cls_split
+    device = torch.device(device)
+    files, cls = load_cls_split(data, "train", args)
+    if world_size > 1:
+        files, cls = files[max(rank, 0)::world_size], cls[max(rank, 0)::world_size]
+    imgsz = int(args.imgsz)
+    decoded = decode_all(files, getattr(args, "workers", 8))
+    need = sum(im.size for im in decoded)
+    free = torch.cuda.mem_get_info(device)[0]
+    resident = need <= free // 2
+    LOGGER.info(f"train: {len(files)} images, {need / 2 ** 20:.1f} MiB at their decoded size; {free / 2 ** 20:.0f} MiB of device memory free -> "
+                f"{'resident in device memory' if resident else 'pinned host memory, uploaded per batch'}")
+    loader = ClassifyTrainLoader(decoded, cls, imgsz, int(args.batch), hyp=_classify_hyp(args), device=device, resident=resident,
+                                 seed=int(getattr(args, "seed", 0) or 0))
+    loader.im_files = files
+    return loader
+
+
+def build_cls_val_loader(args, data, device="cuda", split="val", batch=None):
+    """`split` ('val' or 'test'; check_cls_dataset has already let each fall back to the other) of a check_cls_dataset dict as a
+    ClassifyValLoader.  `batch`: the cfg's unless given (the trainer gives 2 x, classify/train.py:100-103)."""
+    from .dataset import load_cls_split
+    files, cls = load_cls_split(data, split, args)
+    return ClassifyValLoader(files, cls, int(args.imgsz), int(batch or args.batch), device=device, workers=getattr(args, "workers", 8))

@@ -130,32 +130,47 @@ class YOLO:
         ov.update(kwargs)
         return get_cfg(ov)
 
+    def _cls_imgsz(self, kwargs):
+        """the classify task's image size for the paths that read images from disk: 224 unless the call or the overrides give one
+        (reference models/yolo/classify/train.py:22-23)"""
+        if kwargs.get("imgsz") is None and self.overrides.get("imgsz") is None:
+            return dict(kwargs, imgsz=224)
+        return kwargs
+
     def train(self, loader=None, save_dir=None, **kwargs):
-        """model.train(data='dataset/data.yaml', epochs=..., imgsz=..., batch=..., ...): the training set of the data yaml through
+        """A classify model takes `data=<dataset directory>` (train/<class>/..., val/ or test/ likewise: data.check_cls_dataset,
+        ClassifyTrainLoader, ClassifyValLoader; imgsz 224 unless given; the head is rebuilt for the dataset's class count).
+        model.train(data='dataset/data.yaml', epochs=..., imgsz=..., batch=..., ...): the training set of the data yaml through
         data.build_train_loader (labels read and verified, images decoded once, augmentation on the device) and, with `val: True`, its
         val split through data.build_val_loader at twice the batch (the reference's trainer does the same) for the per-epoch
         validation.  Checkpoints are written to `save_dir`, or to project/name when either is given; otherwise nothing is written.
         `loader=<iterable of reference-schema batch dicts>` instead of `data=` is the path for batches that are already in memory."""
-        args = self._data_args(kwargs)
+        cls_data = self.task == "classify" and loader is None
+        args = self._data_args(self._cls_imgsz(kwargs) if cls_data else kwargs)
         self.trainer = DetectionTrainer(args)
         if loader is not None:
             self.trainer.setup(self.model, total_iterations=len(loader) * self.trainer.args.epochs)
             return self.trainer.train(loader)
         if not getattr(args, "data", None):
             raise ValueError("pass data=<path to a data yaml> (the dataset is read from disk) or loader=<iterable of batch dicts>")
-        if self.task == "classify":
-            raise NotImplementedError("the classify task reads one folder per class, not YOLO label files: pass loader=")
-        from ..data import build_train_loader, build_val_loader, check_det_dataset
-        data = check_det_dataset(args.data)
+        from ..data import (build_cls_train_loader, build_cls_val_loader, build_train_loader, build_val_loader, check_cls_dataset,
+                            check_det_dataset)
+        # classify: `data` is a directory with one folder per class under train/ and val/ or test/ (check_cls_dataset)
+        data = check_cls_dataset(args.data) if cls_data else check_det_dataset(args.data)
         self._attach_data(data)
         tr = self.trainer
         torch.cuda.set_device(tr.device)                      # the loaders launch their resize kernels on the current device's stream
-        loader = build_train_loader(args, data, self.task, tr.device, tr.rank, tr.world_size)
+        if cls_data:
+            loader = build_cls_train_loader(args, data, tr.device, tr.rank, tr.world_size)
+        else:
+            loader = build_train_loader(args, data, self.task, tr.device, tr.rank, tr.world_size)
         if len(loader) == 0:
             raise ValueError(f"the training set holds {len(loader.shapes)} images, fewer than one batch of {args.batch}")
         tr.setup(self.model, total_iterations=len(loader) * args.epochs)
         val_loader = None
-        if getattr(args, "val", True) and tr.rank in (-1, 0):
+        if getattr(args, "val", True) and tr.rank in (-1, 0) and cls_data:
+            val_loader = build_cls_val_loader(args, data, tr.device, "val", batch=2 * int(args.batch))
+        elif getattr(args, "val", True) and tr.rank in (-1, 0):
             stride = max(int(self.model.stride.max()), 32)
             val_loader = build_val_loader(args, data, self.task, tr.device, "val", batch=2 * int(args.batch), stride=stride)
         if save_dir is None and (getattr(args, "project", None) or getattr(args, "name", None)):
@@ -165,20 +180,23 @@ class YOLO:
     def val(self, loader=None, **kwargs):
         """model.val(data='dataset/data.yaml', split='val', ...): the split as rect batches of the cfg's `batch` (data.DeviceValLoader);
         `loader=` as before.  The model must be on the GPU."""
-        args = self._data_args(kwargs)
+        cls_data = self.task == "classify" and loader is None
+        args = self._data_args(self._cls_imgsz(kwargs) if cls_data else kwargs)
         if loader is None and getattr(args, "data", None):
-            if self.task == "classify":
-                raise NotImplementedError("the classify task reads one folder per class, not YOLO label files: pass loader=")
-            from ..data import build_val_loader, check_det_dataset
-            data = check_det_dataset(args.data)
+            from ..data import build_cls_val_loader, build_val_loader, check_cls_dataset, check_det_dataset
+            split = getattr(args, "split", None) or "val"
+            # classify: a dataset directory; 'val' falls back to test/ and 'test' to val/ (check_cls_dataset)
+            data = check_cls_dataset(args.data, split) if cls_data else check_det_dataset(args.data)
             dev = next(self.model.parameters()).device
             if len(data["names"]) != len(self.model.names):
                 raise ValueError(f"val(data=): the dataset has {len(data['names'])} classes, the model {len(self.model.names)}: "
                                  "their class ids do not mean the same")
             self.model.names = dict(data["names"])
             torch.cuda.set_device(dev)
-            loader = build_val_loader(args, data, self.task, dev, getattr(args, "split", None) or "val",
-                                      stride=max(int(self.model.stride.max()), 32))
+            if cls_data:
+                loader = build_cls_val_loader(args, data, dev, split)
+            else:
+                loader = build_val_loader(args, data, self.task, dev, split, stride=max(int(self.model.stride.max()), 32))
         self.validator = all_tasks()[self.task][2](args)        # kept: confusion_matrix, nt_per_class, stats, print_results()
         return self.validator(self.model, loader)
 
@@ -192,7 +210,8 @@ class YOLO:
           * an image file, a directory of images, or a list of files / decoded uint8 HWC BGR arrays: every image is letter-boxed on the
             device to the stride-multiple shape of its own aspect ratio (data.augment.letterbox_auto: the predictor's
             LetterBox(imgsz, auto=True), scaleup, linear resize; `imgsz=` in the call or the cfg's), one image per forward (files are
-            decoded one at a time); detect / segment / pose only; `orig_shapes` is filled from the images and `Results.path` from the files.
+            decoded one at a time); `orig_shapes` is filled from the images and `Results.path` from the files.  A classify model
+            centre-crops and resizes instead (_predict_classify) and forwards chunks of the cfg's `batch`.
         Returns one `Results` per image.  A segment model also fills
         `Results.masks` (segment_postprocess; `retina_masks` defaults to the cfg's).  Plotting
         and the mask contours (`Masks.xy`) are outside the hot path.  A classify model returns `Results.probs` (the eval soft-max row
@@ -205,8 +224,6 @@ class YOLO:
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("predict() needs the model on a GPU (there is no CPU path)")
-        if self.task == "classify":
-            raise NotImplementedError("predict(path): the classify transform (resize + centre crop) is not implemented: pass a tensor")
         items = source if isinstance(source, (list, tuple)) else [source]
         images, paths = [], []
         for it in items:
@@ -219,6 +236,8 @@ class YOLO:
                 files = get_img_files(str(it)) if Path(str(it)).is_dir() else [str(it)]
                 images += files                                # decoded one at a time, below
                 paths += files
+        if self.task == "classify":
+            return self._predict_classify(images, paths, kw, dev, decode)
         imgsz = int(kw.get("imgsz") or getattr(get_cfg(dict(self.overrides)), "imgsz", 640))
         stride = max(int(self.model.stride.max()), 32)
         out = []
@@ -226,6 +245,23 @@ class YOLO:
             im = decode(im) if isinstance(im, str) else im
             boxed = letterbox_auto(torch.from_numpy(im).to(dev), imgsz, stride)[0]
             out += self._predict_batch(boxed[None], conf, iou, max_det, agnostic_nms, [tuple(im.shape[:2])], retina_masks, augment)
+        for r, p in zip(out, paths):
+            r.path = p
+        return out
+
+    def _predict_classify(self, images, paths, kw, dev, decode):
+        """predict() of a classify model for files / arrays: the predictor's transform (classify/predict.py:18-21 = classify_transforms:
+        CenterCrop(imgsz) + ToTensor) -- data.augment.center_crop_batch, one dy_cls_render launch per chunk -- and one forward per
+        chunk of the cfg's `batch` images; imgsz 224 unless the call or the overrides give one."""
+        from ..data.augment import center_crop_batch
+        args = get_cfg(dict(self.overrides))
+        imgsz = int(self._cls_imgsz(kw).get("imgsz") or args.imgsz)
+        step, out = max(int(getattr(args, "batch", 1) or 1), 1), []
+        torch.cuda.set_device(dev)
+        for o in range(0, len(images), step):
+            chunk = [decode(im) if isinstance(im, str) else im for im in images[o:o + step]]
+            batch = center_crop_batch([torch.from_numpy(im).to(dev) for im in chunk], imgsz)
+            out += self._predict_batch(batch, None, None, None, None, [tuple(im.shape[:2]) for im in chunk], None, False)
         for r, p in zip(out, paths):
             r.path = p
         return out

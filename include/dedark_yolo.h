@@ -4,7 +4,9 @@
  * ATen op sequence issued by one reference function (cited as U/<file>:<lines>, U = ultralytics/ in the reference
  * tree).  Signatures are plain pointers and sizes -- no torch types.  All pointers are DEVICE pointers unless
  * named host_*.  Every function enqueues on `stream` (a hipStream_t passed as void*), never synchronises, never
- * allocates, and returns 0 on success; on failure it returns non-zero and dy_last_error() describes it.
+ * allocates, and returns 0 on success; on failure it returns non-zero and dy_last_error() describes it.  (Where an entry
+ * departs from this -- dy_aug_resize_area_u8 allocates stream-ordered, dy_cls_render waits for its descriptor check -- its
+ * own comment says so.)
  *
  * Layouts: activations are NHWC ("pixel-major"); a tensor view is (pointer to element [n=0,h=0,w=0,c=c0], ld) where
  * `ld` is the pixel stride in ELEMENTS, so a channel slice of a wider concat buffer is a view with ld = total width.
@@ -638,6 +640,23 @@ typedef struct dy_aug_mix_sample {
   int32_t mix;
 } dy_aug_mix_sample;
 int dy_aug_mosaic_warp_mix(const dy_aug_mix_sample* samples, int B, int out_h, int out_w, uint8_t* out, void* stream);
+/* The classify task's transform for B samples in one launch: out[b] = Format(RandomHSV(flips(cv2.resize(src[y0:y0+ch, x0:x0+cw], (S, S),
+ * INTER_LINEAR)))), uint8 [B, 3, S, S] planar RGB.  With the centre crop (m = min(h, w), top = (h - m) // 2, left = (w - m) // 2), no flips
+ * and hsv = 0 this is the reference's classify_transforms = CenterCrop(size) + ToTensor() before its / 255 (data/augment.py:799-806,
+ * 879-907), the transform of the classify predictor and of the train / val sets when albumentations is absent; a random crop, flips and
+ * the RandomHSV tables (augment.py:493-497) make the training augmentation.  Clamped resize taps clamp to the crop (cv2 sees a view),
+ * never to the image around it.  samples: DEVICE array of B descriptors.  The descriptors are read back and checked before the launch
+ * (one copy and a wait on `stream`: this entry does wait): a null source, pitch < 3 * sw, or a crop that is empty or not inside its image
+ * is an argument error (1), as are B < 0, S <= 0 and a null pointer with B > 0.  B == 0 succeeds and writes nothing. */
+typedef struct dy_cls_sample {
+  const uint8_t* src;      /* decoded image, uint8 HWC BGR, at its decoded size */
+  int64_t pitch;           /* bytes per row */
+  int32_t sh, sw;
+  int32_t x0, y0, cw, ch;  /* the crop, in pixels of src */
+  int32_t fliplr, flipud, hsv, reserved;
+  uint8_t lut[3][256];     /* RandomHSV's hue / saturation / value tables, read when hsv != 0 */
+} dy_cls_sample;
+int dy_cls_render(const dy_cls_sample* samples, int B, int S, uint8_t* out, void* stream);
 /* DarkChannel / AtmLight / DarkIcA of preprocess_batch (train.py:42-68,81-96) without the device->host copy and the Python loop:
  * img f32 [B,3,H,W] in [0,1] (the darkened batch) -> A [B,3] (0..255 scale, as train.py:95), ica [B,1,H,W].  Deterministic: ties of the
  * reference's unstable argsort go by pixel index, the rows DarkIcA leaves uninitialised use the per-channel formula. */

@@ -15,6 +15,8 @@ what the last timed step computed as DIR/*.npy (bench.dump_outputs), to compare 
 a 640-pixel long side, 10 instances each: 5..12-vertex polygons, or 17 keypoints) is fed through
 DeviceAugmentLoader(task=...) -- mosaic, affine, HSV, flips, and for the segment task the polygon rasteriser -- so the step time
 includes the host's label bookkeeping and the loader's kernels.  The JSON line then also carries the label rows per batch.
+For classify the dataset is folder-shaped instead: 3 x batch decoded images whose sides vary between 256 and 500 pixels, one class id
+each, resident, fed through ClassifyTrainLoader (random resized crop, flips, HSV tables, one dy_cls_render launch per batch).
 """
 import argparse
 import json
@@ -80,11 +82,23 @@ def loader_dataset(task, n, S, per_image=10, K=17):
 COCO_FLIP_IDX = [0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15]
 
 
-def loader_batches(task, B, S):
+def classify_dataset(n, nc, lo=256, hi=500):
+    """n decoded images with sides in [lo, hi] (what a folder of photographs decodes to) and one class id each"""
+    import numpy as np
+    g = np.random.default_rng(301)
+    ims = [g.integers(0, 256, (int(g.integers(lo, hi + 1)), int(g.integers(lo, hi + 1)), 3), dtype=np.uint8) for _ in range(n)]
+    return ims, g.integers(0, nc, n).astype(np.int64)
+
+
+def loader_batches(task, B, S, nc=None):
     """endless stream of loader batches (epoch after epoch)"""
-    from dedark_yolo_amd.data import DeviceAugmentLoader
-    ims, labels = loader_dataset(task, 3 * B, S)
-    ld = DeviceAugmentLoader(ims, labels, S, B, seed=0, task=task, flip_idx=COCO_FLIP_IDX if task == "pose" else None)
+    from dedark_yolo_amd.data import ClassifyTrainLoader, DeviceAugmentLoader
+    if task == "classify":
+        ims, cls = classify_dataset(3 * B, nc)
+        ld = ClassifyTrainLoader(ims, cls, S, B, seed=0, resident=True)
+    else:
+        ims, labels = loader_dataset(task, 3 * B, S)
+        ld = DeviceAugmentLoader(ims, labels, S, B, seed=0, task=task, flip_idx=COCO_FLIP_IDX if task == "pose" else None)
     while True:
         yield from ld
 
@@ -118,20 +132,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR")
-    ap.add_argument("--loader", action="store_true", help="feed the steps from DeviceAugmentLoader over a synthetic resident dataset")
+    ap.add_argument("--loader", action="store_true",
+                    help="feed the steps from DeviceAugmentLoader (classify: ClassifyTrainLoader) over a synthetic resident dataset")
     a = ap.parse_args()
     model, steps, add_labels, model_cls = TASKS[a.task]
     model, steps = a.model or model, a.steps or steps
     cls_task = a.task == "classify"
     nc, S, B = (1000 if cls_task else 20), a.imgsz or (224 if cls_task else 640), a.batch or (128 if cls_task else 32)
-    if cls_task and a.loader:
-        ap.error("--loader: there is no classify data pipeline (DeviceAugmentLoader serves detect, segment and pose)")
     torch.manual_seed(0)          # the initial weights: with the seeded batches, two runs start from the same state
     tr = DetectionTrainer(get_cfg(dict(model=model, dtype=a.dtype, optimizer="SGD", batch=B, imgsz=S, deterministic=a.deterministic)))
     tr.setup(getattr(tasks, model_cls)(tasks.yaml_model_load(model), nc=nc))
     rows, host = [], []
     if a.loader:
-        stream = loader_batches(a.task, B, S)
+        stream = loader_batches(a.task, B, S, nc)
 
         def batch(i):
             t0 = time.perf_counter()
@@ -169,7 +182,8 @@ def main():
     print(json.dumps(dict(metric=f"{a.task} training img/s", model=model, imgsz=S, batch=B, dtype=a.dtype, steps=steps,
                           warmup=a.warmup, ms_per_step=round(ms, 3), value=round(B * 1000.0 / ms, 2),
                           items=[round(float(v), 4) for v in items.reshape(-1)],
-                          **(dict(loader=True, dataset_instances_per_image=10, label_rows_per_batch=round(sum(rows) / len(rows), 1),
+                          **(dict(loader=True, dataset_instances_per_image=1 if cls_task else 10,
+                                  label_rows_per_batch=round(sum(rows) / len(rows), 1),
                                   host_loader_ms_per_step=round(1e3 * sum(host) / len(host), 3)) if a.loader else {}))))
 
 
